@@ -15,12 +15,15 @@ launch, action blocks staged in HBM, every step's outputs written, the state in 
 step, up to 64 launches in a hipGraph (an RL loop with a policy between steps; reported under `one_launch_per_step` as well);
 `eager` = one host launch per step (`python_step_loop`).
 
-What is timed: the K steps of `--steps` form one SCHEDULE (K // 64 launches of 64 steps + one of K % 64), repeated back to back
-until the timed region lasts >= `--min-time`; `ms_per_step` / `value` / `roofline.achieved` come from ONE clock, HIP events on the
-launch stream (max over ranks); the host wall clock around the same region is printed beside it.  Weak scaling: every rank owns its
-aviaries, no data-path collective unless a workload names the optional RCCL all-gather of the observation shards.
-The line also carries `hbm_saturating`, `dropin_single_env`, `parity`, `cpu_baseline` and, for N > 1, the `suite` (BASELINE configs
-4 and 5).  Checker code: oracle/bench_checks.py; one-world, policy and history-row workloads: bench_extra.py.  ONE JSON line, rank 0.
+What is timed: the K steps of `--steps` form one SCHEDULE (K // 64 launches of 64 steps + one of K % 64), timed once after the W warm-up steps
+and, on one rank, a fixed count of further launches (`settle_launches`: the clock of an idle GPU settles; the stream waits ~0.1 ms before the
+first timed launch, so its submission is not timed) -- or, with `--min-time T`, after one untimed pass of the schedule, repeated back to back
+until the timed region lasts >= T; `ms_per_step` / `value` / `roofline.achieved` come from ONE clock, HIP events on the launch stream (max
+over ranks); the host wall clock around the same region is printed beside it. Weak scaling: every rank owns its aviaries, no data-path
+collective unless a workload names the optional RCCL all-gather of the observation shards. `--dump-outputs DIR`: the timed path's outputs of
+its last step, DIR/<name>.npy. `--full` (T = 0.25 s by default) adds `one_launch_per_step`, `python_step_loop`, `hbm_saturating`,
+`dropin_single_env`, `parity`, `cpu_baseline` and, for N > 1, the `suite` (BASELINE configs 4 and 5). Checker code: oracle/bench_checks.py;
+one-world, policy and history-row workloads: bench_extra.py. ONE JSON line, rank 0.
 """
 import argparse
 import ctypes
@@ -132,6 +135,12 @@ def groups_of(k, pool):
     return [pool] * (k // pool) + ([k % pool] if k % pool else [])
 
 
+def settle_launches(K, N):
+    """A plain single-rank run's extra warm-up between the W steps and the timed ones: launches of min(K, POOL) steps, 2^33 drone-steps
+    in all (at most 2^18 steps; ~0.1 s at the headline's 65 536 drones), a count fixed by K and the drone count N alone."""
+    return [min(K, POOL)] * max(1, min(2 ** 18, 2 ** 33 // N) // min(K, POOL))
+
+
 def launch_rollout(e, a, n):
     """One rollout launch of n env steps of the aviaries of `e` with the action blocks a[:n] -- THE timed call of rollout mode (also
     what the parity leg replays).  Returns (obs12 [n,N,12], reward, terminated, truncated[, actions])."""
@@ -141,7 +150,7 @@ def launch_rollout(e, a, n):
     return e.core.rollout(a[:n], update_latest=False)
 
 
-def measure(mode, args, env, actions, gather, device, world):
+def measure(mode, args, env, actions, gather, device, world, keep_outputs=False):
     """Time `repeats` x K env steps of every aviary on this rank.  mode 'graph': one kernel launch per env step, up to POOL steps
     captured in a hipGraph; 'eager': one host launch per step; 'rollout': `gpd_rollout`, up to POOL steps per launch (actions
     pre-staged, every step's obs/reward/flags written)."""
@@ -165,8 +174,11 @@ def measure(mode, args, env, actions, gather, device, world):
         for n in sorted(sizes):             # one larger collective per rollout; every length shares the ONE communicator of `gather`
             gathers[n] = gather.sized(n * core.N * 12)
 
+    last = {}
+
     def one_rollout(n):
-        out = launch_rollout(env, actions, n)
+        out = last["out"] = launch_rollout(env, actions, n)
+        last["n"] = n
         if n in gathers:
             gathers[n](out[0].reshape(-1, 12))
 
@@ -214,6 +226,8 @@ def measure(mode, args, env, actions, gather, device, world):
             torch.distributed.barrier()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
+        if reps == 1:         # (one pass: the stream waits ~0.1 ms, so the first launch is queued before ev0 fires; the host clock includes it)
+            torch.cuda._sleep(1 << 18)
         t0 = time.perf_counter()
         ev0.record()          # on the current stream = the stream every gpd_* launch above goes to
         marks.clear()
@@ -236,10 +250,20 @@ def measure(mode, args, env, actions, gather, device, world):
         return gdist.max_over_ranks(mine, device=device), gdist.max_over_ranks(t1 - t0, device=device)
 
     run(W)                                          # W untimed warm-up steps, as requested
-    run(K)                                          # + one untimed pass of the schedule itself
-    cal, _ = timed(1)                               # calibration pass (untimed in the result): how long is one schedule?
-    repeats = int(min(max(1, math.ceil(args.min_time / max(cal, 1e-7))), 1 << 20))
+    repeats = 1                                     # --min-time 0 (a plain run): the K steps of --steps, timed once ...
+    if args.min_time == 0 and world == 1 and not getattr(env, "reset_each_pass", False):
+        for n in settle_launches(K, core.N):        # ... after a fixed count of the same launches: an idle GPU's clock settles first
+            run(n)
+    else:
+        run(K)                                      # + one untimed pass of the schedule itself
+    if args.min_time > 0:
+        cal, _ = timed(1)                           # calibration pass (untimed in the result): how long is one schedule?
+        repeats = int(min(max(1, math.ceil(args.min_time / max(cal, 1e-7))), 1 << 20))
     ev_s, wall_s = timed(repeats)
+    outputs = None
+    if keep_outputs:                                # what the timed path returned for its last step, copied before anything else runs
+        last_step = [x[last["n"] - 1] for x in last["out"]] if mode == "rollout" else [core.obs12, core.reward, core.terminated, core.truncated]
+        outputs = {k: x.cpu() for k, x in zip(("obs", "reward", "terminated", "truncated", "actions"), last_step)}
     timed_steps = K * repeats
     # roofline of the dominant kernel: algorithmic bytes of all launches of the timed region / its HIP-event time
     extra = getattr(env, "bench_extra_bytes", lambda n, rollout: 0)
@@ -267,7 +291,7 @@ def measure(mode, args, env, actions, gather, device, world):
                     "rest_steps_per_s": (n_e - n_h) * K / max(t_e - t_h, 1e-12) if n_e > n_h else None,
                     "slowest_over_fastest_segment": min(per) / max(per)}
     return {
-        "K": K, "W": W, "repeats": repeats, "timed_steps": timed_steps, "ev_s": ev_s, "wall_s": wall_s, "segments": segments,
+        "outputs": outputs, "K": K, "W": W, "repeats": repeats, "timed_steps": timed_steps, "ev_s": ev_s, "wall_s": wall_s, "segments": segments,
         "value": n_total * core.S * timed_steps / ev_s, "value_wall": n_total * core.S * timed_steps / wall_s,
         "env_steps_per_s": n_total * timed_steps / ev_s, "us_per_step": ev_s * 1e6 / timed_steps,
         "per_gpu": [core.N * core.S * timed_steps / t for t in per_rank_s],
@@ -331,58 +355,6 @@ def attach_counters(roof, key, m, core, clock_ghz):
     return issue
 
 
-def dropin_single_env(device, steps=2420):
-    """BASELINE config 1's shape through the DROP-IN class: `HoverAviary()` with its defaults (30 Hz control / 240 Hz physics,
-    Physics.PYB = explicit integrator + ground plane here), ActionType.ONE_D_RPM, a ~ U(-1, 1) of shape (1, 1), 2 420 `step()` calls
-    with a reset at every episode end (examples/learn.py:54-58; envs/BaseAviary.py:509-519 is the per-step read-back the reference
-    pays).  Wall clock per call -- this path is latency, not bandwidth: the aviary's state lives in host-visible memory, a step is
-    one gpd_step_sync call (the launch + a spin on the word the kernel writes when it is done) + numpy reads -- and where it goes."""
-    import warnings
-    from gym_pybullet_drones_amd.envs import HoverAviary
-    from gym_pybullet_drones_amd.utils.enums import ActionType
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        env = HoverAviary(act=ActionType.ONE_D_RPM, device=device)
-    acts = np.random.default_rng(0).uniform(-1, 1, size=(steps, 1, 1)).astype(np.float32)
-    env.reset(seed=0)
-    for k in range(64):
-        env.step(acts[k])
-    env.reset(seed=0)
-    torch.cuda.synchronize()
-    episodes, t0 = 0, time.perf_counter()
-    for k in range(steps):
-        _, _, term, trunc, _ = env.step(acts[k])
-        if term or trunc:
-            env.reset()
-            episodes += 1
-    dt = time.perf_counter() - t0
-    core = env._core
-
-    def per_call_us(fn, n=1000):
-        t = time.perf_counter()
-        for _ in range(n):
-            fn()
-        return (time.perf_counter() - t) / n * 1e6
-    parts = {"gpd_step_sync_launch_and_wait": per_call_us(core.step_host), "numpy_kinematic_refresh": per_call_us(env._updateAndStoreKinematicInformation),
-             "observation_row_with_history": per_call_us(env._computeObs)}
-    S = int(env.PYB_STEPS_PER_CTRL)
-    out = {"us_per_step": dt / steps * 1e6, "env_steps_per_s": steps / dt, "value": steps * S / dt, "unit": "drone-steps/s", "steps": steps,
-           "episodes_ended": episodes, "state_memory": "host-visible (page-locked, device-mapped)" if core.host_visible else "HBM",
-           "breakdown_us": parts,
-           "what": "for k in range(2420): HoverAviary(act=ONE_D_RPM).step(a[k]) (+ reset at episode ends), wall clock; one gpd_step_sync call "
-                   "(launch + wait on the kernel's completion word) per step, no device-to-host copy, no second launch"}
-    env.close()
-    try:        # the reference's OWN Python on the same schedule (quoted: /root/reference does not exist on this box)
-        rec = json.load(open(os.path.join(REPO, "profiles", "r05_reference_python_dyn_cpu.json")))
-        out["reference_python_us_per_step"] = 1e6 * S / rec["value"]
-        out["speedup_over_reference_python"] = out["value"] / rec["value"]
-        out["reference_python_note"] = ("the reference's unmodified HoverAviary(physics=Physics.DYN) over oracle/pybullet_shim.py, same schedule, "
-                                        f"1 core of {rec.get('host_cpu')}, timed in the build container (profiles/r05_reference_python_dyn_cpu.json)")
-    except Exception as e:      # noqa: BLE001
-        out["reference_python_note"] = f"no committed figure ({type(e).__name__})"
-    return out
-
-
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -390,7 +362,11 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=256)
     ap.add_argument("--workload", default="hover65536_240hz", choices=sorted(WORKLOADS))
     ap.add_argument("--mode", default="rollout", choices=["rollout", "graph", "eager"], help="see the module docstring")
-    ap.add_argument("--min-time", type=float, default=0.25, help="repeat the K-step schedule until the timed region lasts this long [s]")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (one_launch_per_step, python_step_loop, parity, "
+                    "cpu_baseline, dropin_single_env, hbm_saturating, the clock probe; the suite for N > 1); without it, the K timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned for its last step as DIR/<name>.npy")
+    ap.add_argument("--min-time", type=float, default=None, help="repeat the K-step schedule until the timed region lasts this long [s] "
+                    "(default: 0, exactly --steps timed steps; 0.25 with --full)")
     ap.add_argument("--no-parity", action="store_true", help="skip the replay of one schedule through the float64 C oracle")
     ap.add_argument("--allgather", action="store_true", help="all-gather the obs shards over RCCL")
     ap.add_argument("--allgather-impl", default="auto", choices=["auto", "native", "torch"], help="native: gpd_allgather_obs (ncclAllGather); torch: torch.distributed")
@@ -413,6 +389,9 @@ def parse_args(argv=None):
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if not args.full:           # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_parity = args.no_cpu_baseline = args.no_second_leg = args.no_dropin_leg = args.no_hbm_leg = True
+    args.min_time = (0.25 if args.full else 0.0) if args.min_time is None else args.min_time
     return args
 
 
@@ -519,8 +498,10 @@ def main(argv=None):
             torch.distributed.barrier()
             torch.distributed.destroy_process_group()
         raise SystemExit(rc)
-    suite = (args.scale_suite or (job.world > 1 and args.workload == "hover65536_240hz")) and not args.no_suite
+    suite = (args.scale_suite or (args.full and job.world > 1 and args.workload == "hover65536_240hz")) and not args.no_suite
     out = run_workload(args, job)
+    if args.dump_outputs and job.rank == 0:
+        dump_outputs(args.dump_outputs, job.last_outputs)
     if args.workload == "hover65536_240hz" and not args.no_hbm_leg:
         hbm_leg(args, job, out)
     if suite:
@@ -531,6 +512,18 @@ def main(argv=None):
     if job.world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(d, outputs, limit=64 << 20):
+    """`--dump-outputs DIR`: DIR/<name>.npy in float32 (float64 stays float64); above `limit` bytes in all, the same seeded sample of
+    rows (drones / aviaries) of every array, in every run."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {k: x.numpy().astype(np.float64 if x.dtype == torch.float64 else np.float32) for k, x in outputs.items()}
+    frac = min(1.0, limit / max(sum(a.nbytes for a in arrs.values()), 1))
+    for k, a in arrs.items():
+        if frac < 1.0:
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False))]
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 class Watchdog:
@@ -562,7 +555,7 @@ def hbm_leg(args, job, out):
     next to it is a fabric-side rate.  This leg puts a number beside it that the cache cannot serve: the same kernel, the same
     schedule, 4 194 304 drones per GPU (13.9 GB of observation rows per 64-step launch, 218 MB of state)."""
     a = argparse.Namespace(**vars(args))
-    a.workload, a.no_cpu_baseline, a.no_second_leg, a.no_dropin_leg, a.allgather = "hover4m_240hz", True, True, True, False
+    a.workload, a.no_cpu_baseline, a.no_second_leg, a.no_dropin_leg, a.allgather, a.dump_outputs = "hover4m_240hz", True, True, True, False, None
     a.placement_search = not os.environ.get("GPD_BENCH_NO_PLACEMENT_SEARCH")       # (the A/B: the driver's allocation as it comes)
     # >= 2 s of timed region, seen in 48 pieces (0.1 s = 32 launches cannot tell a boost clock from a steady one); --hbm-leg-time shortens it for tests
     a.min_time = float(getattr(args, "hbm_leg_time", 2.2))
@@ -582,16 +575,16 @@ def hbm_leg(args, job, out):
     finally:
         dog.done()
     # The extras have their own guard and their own budget: a failure or a time-out in them leaves `on_fresh_allocations` partial and
-    # the leg's figure -- already measured -- in the line.  Every rank re-runs on its own (no collective inside): the same
-    # environment, its rollout blocks freed and placed again -- a new arena searched (or, without the search, new plain allocations).
+    # the leg's figure -- already measured -- in the line.  Rank 0 alone re-runs, the line carries its figures (no other rank
+    # may outlive a budget of its own while rank 0 goes on to a collective): the same environment, its rollout blocks freed and placed
+    # again -- a new arena searched (or, without the search, new plain allocations).  The other ranks wait for it in run_suite's barrier.
     copy, again, again_note = None, [], None
-    if (r is None or "error" not in r) and getattr(job, "last_env", None) is not None:
+    if job.rank == 0 and "error" not in r and getattr(job, "last_env", None) is not None:
         n_again, budget = int(getattr(args, "hbm_leg_reallocations", 10)), min(90.0, args.suite_timeout)
         dog2 = Watchdog(budget, job, out, lambda o: o.__setitem__("hbm_saturating", hbm_block(r, copy, again, f"the re-runs on fresh allocations were cut after {budget:.0f} s")))
         try:
             import gc
-            if job.rank == 0:
-                copy = copy_probe(job.device)
+            copy = copy_probe(job.device)
             env, core = job.last_env, job.last_env.core
             for _ in range(n_again):
                 env.placement_arena = acts = None
@@ -614,7 +607,11 @@ def hbm_leg(args, job, out):
             again_note = f"stopped after {len(again)} re-runs: {type(e).__name__}: {e}"[:300]
         finally:
             dog2.done()
-            job.last_env = None
+    job.last_env = None
+    if job.world > 1:       # the other ranks wait here for rank 0's re-runs; when its budget fires and it leaves, this watchdog lets them leave too
+        dog3 = Watchdog(min(90.0, args.suite_timeout) + 60.0, job, out, lambda o: None)
+        torch.distributed.barrier()
+        dog3.done()
     if job.rank == 0:
         out["hbm_saturating"] = r if "error" in r else hbm_block(r, copy, again, again_note)
         if "error" not in r:
@@ -700,10 +697,12 @@ def run_suite(args, job, out):
         out["suite"] = results
     dog = Watchdog(args.suite_timeout, job, out,
                    lambda o: results.__setitem__("error", f"suite not finished after {args.suite_timeout:.0f} s: line printed without the rest"))
+    if job.world > 1:                       # (armed first: a rank waiting here for rank 0 leaves with the others when the suite's budget runs out)
+        torch.distributed.barrier()
     try:
         for name in SUITE:
             a = argparse.Namespace(**vars(args))
-            a.workload, a.no_cpu_baseline, a.no_hbm_leg, a.no_dropin_leg, a.allgather = name, True, True, True, False
+            a.workload, a.no_cpu_baseline, a.no_hbm_leg, a.no_dropin_leg, a.allgather, a.dump_outputs = name, True, True, True, False, None
             t0 = time.perf_counter()
             try:
                 r = run_workload(a, job)
@@ -798,8 +797,8 @@ def run_workload(args, job):
         # BASELINE config 4 asks for both: first the same schedule WITHOUT the collective
         plain = measure(mode, args, env, actions, None, device, world)
         env.reset()
-    m = measure(mode, args, env, actions, gather, device, world)
-    job.last_env = env                      # (the hbm leg re-places this environment's blocks for its re-runs)
+    m = measure(mode, args, env, actions, gather, device, world, keep_outputs=bool(getattr(args, "dump_outputs", None)))
+    job.last_env, job.last_outputs = env, m["outputs"]                     # (the hbm leg re-places this environment's blocks for its re-runs)
 
     parity = None
     if w.get("parity"):                     # (bench_extra.py's workloads bring their own checker; collective where the world is shared)
@@ -814,13 +813,14 @@ def run_workload(args, job):
     clock_ghz = None
     try:        # the shader clock a one-wave-per-SIMD FMA chain runs at right after the timed region (diagnostics)
         ghz, nsf = ctypes.c_double(), ctypes.c_double()
-        if core.lib.gpd_clock_probe(ctypes.byref(ghz), ctypes.byref(nsf), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)) == 0:
+        if args.full and core.lib.gpd_clock_probe(ctypes.byref(ghz), ctypes.byref(nsf), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)) == 0:
             clock_ghz = ghz.value
     except Exception:       # noqa: BLE001
         pass
     dropin = None
     if rank == 0 and world == 1 and args.workload == "hover65536_240hz" and not args.no_dropin_leg:
         try:
+            from bench_extra import dropin_single_env           # (a leg of --full only: kept beside the other workloads)
             dropin = dropin_single_env(device)
         except Exception as e:          # noqa: BLE001
             dropin = {"error": f"{type(e).__name__}: {e}"[:300]}

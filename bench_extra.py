@@ -4,22 +4,82 @@
   * ONE aviary of any size (`swarm65536_ext_240hz`, `swarm1m_ext_240hz`): pairwise downwash over the whole world, `--gpus N` shares the
     world among N ranks (strong scaling: halo exchange or all-gather of positions per sub-step);
   * the policy inside the rollout kernel (`*_policy*`, gpd_rollout_policy) -- frozen since round 4;
-  * materialised history rows / the action ring pushed in the kernel (`*_fullobs`, `*_history`).
+  * materialised history rows / the action ring pushed in the kernel (`*_fullobs`, `*_history`);
+  * `dropin_single_env`, the drop-in `HoverAviary().step()` leg of `bench.py --full`.
 
     python bench_extra.py --workload swarm65536_ext_240hz [--gpus N] [--steps K] [--warmup W] ...
 
-The driver runs bench.py; nothing here is part of the headline.  The losing experiments of rounds 3 - 5 (`--split`, `--stagger`,
+The driver runs bench.py; nothing here is part of the headline.  Through bench.main these workloads take bench.py's flags as they are: a
+plain run times the K steps only (no parity, no second or eager leg, no CPU baseline, no 0.25 s repeat target); `--full` brings them back.  The losing experiments of rounds 3 - 5 (`--split`, `--stagger`,
 `--cu-mask`, `--rollout-graph`) are not carried: `git show d596b96:bench.py` has their last form, profiles/HISTORY.md their results.
 """
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
 
 import bench
 from bench import NUM_SIMDS, PEAK_CLOCK_GHZ, REPO
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the drop-in class, one aviary (bench.py --full: `dropin_single_env`)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+
+def dropin_single_env(device, steps=2420):
+    """BASELINE config 1's shape through the DROP-IN class: `HoverAviary()` with its defaults (30 Hz control / 240 Hz physics,
+    Physics.PYB = explicit integrator + ground plane here), ActionType.ONE_D_RPM, a ~ U(-1, 1) of shape (1, 1), 2 420 `step()` calls
+    with a reset at every episode end (examples/learn.py:54-58; envs/BaseAviary.py:509-519 is the per-step read-back the reference
+    pays).  Wall clock per call -- this path is latency, not bandwidth: the aviary's state lives in host-visible memory, a step is
+    one gpd_step_sync call (the launch + a spin on the word the kernel writes when it is done) + numpy reads -- and where it goes."""
+    import warnings
+    from gym_pybullet_drones_amd.envs import HoverAviary
+    from gym_pybullet_drones_amd.utils.enums import ActionType
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        env = HoverAviary(act=ActionType.ONE_D_RPM, device=device)
+    acts = np.random.default_rng(0).uniform(-1, 1, size=(steps, 1, 1)).astype(np.float32)
+    env.reset(seed=0)
+    for k in range(64):
+        env.step(acts[k])
+    env.reset(seed=0)
+    torch.cuda.synchronize()
+    episodes, t0 = 0, time.perf_counter()
+    for k in range(steps):
+        _, _, term, trunc, _ = env.step(acts[k])
+        if term or trunc:
+            env.reset()
+            episodes += 1
+    dt = time.perf_counter() - t0
+    core = env._core
+
+    def per_call_us(fn, n=1000):
+        t = time.perf_counter()
+        for _ in range(n):
+            fn()
+        return (time.perf_counter() - t) / n * 1e6
+    parts = {"gpd_step_sync_launch_and_wait": per_call_us(core.step_host), "numpy_kinematic_refresh": per_call_us(env._updateAndStoreKinematicInformation),
+             "observation_row_with_history": per_call_us(env._computeObs)}
+    S = int(env.PYB_STEPS_PER_CTRL)
+    out = {"us_per_step": dt / steps * 1e6, "env_steps_per_s": steps / dt, "value": steps * S / dt, "unit": "drone-steps/s", "steps": steps,
+           "episodes_ended": episodes, "state_memory": "host-visible (page-locked, device-mapped)" if core.host_visible else "HBM",
+           "breakdown_us": parts,
+           "what": "for k in range(2420): HoverAviary(act=ONE_D_RPM).step(a[k]) (+ reset at episode ends), wall clock; one gpd_step_sync call "
+                   "(launch + wait on the kernel's completion word) per step, no device-to-host copy, no second launch"}
+    env.close()
+    try:        # the reference's OWN Python on the same schedule (a committed figure: the reference is not part of this repository)
+        rec = json.load(open(os.path.join(REPO, "profiles", "r05_reference_python_dyn_cpu.json")))
+        out["reference_python_us_per_step"] = 1e6 * S / rec["value"]
+        out["speedup_over_reference_python"] = out["value"] / rec["value"]
+        out["reference_python_note"] = ("the reference's unmodified HoverAviary(physics=Physics.DYN) over oracle/pybullet_shim.py, same schedule, "
+                                        f"1 core of {rec.get('host_cpu')}, timed in the build container (profiles/r05_reference_python_dyn_cpu.json)")
+    except Exception as e:      # noqa: BLE001
+        out["reference_python_note"] = f"no committed figure ({type(e).__name__})"
+    return out
+
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # one world of any size

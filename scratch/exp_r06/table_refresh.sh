@@ -2,7 +2,7 @@
 # DESIGN.md section 5's table on the final library: every rollout row once (64 steps per launch) with its one-launch-per-step leg
 O=gpurun_out/r06t; mkdir -p $O
 for w in hover65536_240hz hover65536_30hz hover65536_pid_240hz hover65536_ext_240hz hover4096_240hz stack8x8192_ext_240hz multihover2x16384_240hz hover65536_240hz_termobs hover65536_ext_pid_240hz stack8x8192_ext_pid_240hz multihover2x16384_pid_240hz hover4096_30hz hover4096_pid_240hz; do
-  python bench.py --workload $w --steps 64 --warmup 64 --no-cpu-baseline --no-hbm-leg --no-dropin-leg --min-time 0.5 > $O/$w.json 2>/dev/null
+  python bench.py --full --workload $w --steps 64 --warmup 64 --no-cpu-baseline --no-hbm-leg --no-dropin-leg --min-time 0.5 > $O/$w.json 2>/dev/null
   python - "$O/$w.json" "$w" <<'P'
 import json,sys
 j=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

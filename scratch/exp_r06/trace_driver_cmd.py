@@ -19,7 +19,7 @@ R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 OUT = os.path.join(R, "gpurun_out", "r06_final")
 os.makedirs(OUT, exist_ok=True)
 ENV = dict(os.environ, TMPDIR="/tmp")
-CMD = ["--steps", "20", "--warmup", "5"]
+CMD = ["--full", "--steps", "20", "--warmup", "5"]
 
 
 def bench(tag, prefix=(), extra=()):

@@ -175,3 +175,77 @@ def test_committed_counter_profiles_hold_the_keys_the_bench_line_reads():
         assert c[key]["slots_per_wave_env_step"] > c[key]["valu_per_wave_env_step"] > 0, key
     for wl in ("swarm65536_ext_240hz", "swarm1m_ext_240hz"):
         assert s[wl]["valu_wave_instructions_per_substep"] > 0 and s[wl]["replay_waves"] > 0, wl
+
+
+def test_a_plain_run_is_the_headline_only_and_full_brings_the_legs_back():
+    """`bench.py --steps K --warmup W` times exactly K steps and nothing beside them; `--full` runs every leg as before."""
+    a = bench.parse_args(["--steps", "20", "--warmup", "5"])
+    assert not a.full and a.min_time == 0.0 and a.dump_outputs is None
+    assert a.no_parity and a.no_cpu_baseline and a.no_second_leg and a.no_dropin_leg and a.no_hbm_leg
+    f = bench.parse_args(["--full"])
+    assert f.full and f.min_time == 0.25
+    assert not (f.no_parity or f.no_cpu_baseline or f.no_second_leg or f.no_dropin_leg or f.no_hbm_leg)
+    assert bench.parse_args(["--full", "--no-parity", "--min-time", "0.05"]).no_parity
+    assert bench.parse_args(["--min-time", "0.05"]).min_time == 0.05
+    # the plain run's extra warm-up: a launch count fixed by K and the drone count, nothing measured or estimated
+    assert bench.settle_launches(100, 65536) == [64] * 2048 and bench.settle_launches(20, 65536) == [20] * 6553
+    assert sum(bench.settle_launches(64, 16777216)) == 512 and bench.settle_launches(1, 1 << 40) == [1]
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_the_same_rows(tmp_path):
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    outs = {"obs": torch.rand((1000, 12), generator=g), "reward": torch.rand((1000,), generator=g, dtype=torch.float64),
+            "terminated": torch.rand((1000,), generator=g) > 0.5}
+    bench.dump_outputs(str(tmp_path / "all"), outs)
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in outs}
+    assert got["obs"].dtype == np.float32 and got["reward"].dtype == np.float64 and got["terminated"].dtype == np.float32
+    assert all(np.array_equal(got[k], outs[k].numpy()) for k in outs)
+    for d in ("a", "b"):                 # above the limit: a seeded sample of rows, the same in every run and in every array
+        bench.dump_outputs(str(tmp_path / d), outs, limit=20000)
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in outs}
+    b = {k: np.load(tmp_path / "b" / (k + ".npy")) for k in outs}
+    assert sum(x.nbytes for x in a.values()) <= 20000 and len(a["obs"]) == len(a["reward"]) > 100
+    assert all(np.array_equal(a[k], b[k]) for k in outs)
+    rows = [i for i in range(1000) if (outs["obs"][i].numpy() == a["obs"]).all(axis=1).any()]
+    assert len(rows) == len(a["obs"]) and np.array_equal(a["reward"], outs["reward"].numpy()[rows])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_its_steps_and_dumps_the_same_outputs_twice(gpu_device, tmp_path):
+    """The driver's command with `--dump-outputs`: exactly --steps timed steps, the headline fields, none of the --full legs, the
+    last step's outputs of two runs bit for bit the same -- and the same as the last step of the run's launch schedule replayed here
+    (buffer allocation, the W warm-up steps, `settle_launches`, the K timed steps), not some other step of it."""
+    import subprocess
+    import numpy as np
+    lines = []
+    for d in ("one", "two"):
+        res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "100", "--warmup", "10",
+                              "--dump-outputs", str(tmp_path / d)], cwd=REPO, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        lines.append(json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1]))
+    j = lines[0]
+    assert j["steps"] == 100 and j["warmup"] == 10 and j["repeats"] == 1 and j["timed_steps"] == 100
+    assert j["metric"] == bench.BASELINE_METRIC and j["unit"] == "drone-steps/s" and j["higher_is_better"] and j["dtype"] == "f32"
+    assert j["ms_per_step"] == pytest.approx(j["timed_region_ms"] / 100) and j["value"] > 0
+    for leg in ("one_launch_per_step", "python_step_loop", "hbm_saturating", "dropin_single_env", "parity", "cpu_baseline", "suite"):
+        assert leg not in j, leg
+    for name, shape in (("obs", (65536, 12)), ("reward", (65536,)), ("terminated", (65536,)), ("truncated", (65536,))):
+        a, b = np.load(tmp_path / "one" / (name + ".npy")), np.load(tmp_path / "two" / (name + ".npy"))
+        assert a.shape == shape and a.dtype == np.float32 and np.array_equal(a, b) and np.isfinite(a).all(), name
+    import torch
+    w = bench.WORKLOADS["hover65536_240hz"]
+    env = bench.make_env(w, gpu_device, seed=1000)                  # (rank 0's seeds in bench.run_workload)
+    acts = bench.make_actions(w, env, gpu_device, seed=2000, pool=bench.POOL)
+    K, W = 100, 10
+    schedule = (sorted(set(bench.groups_of(K, bench.POOL)) | set(bench.groups_of(W, bench.POOL)), reverse=True) + bench.groups_of(W, bench.POOL)
+                + bench.settle_launches(K, env.core.N) + bench.groups_of(K, bench.POOL))
+    for n in schedule:
+        out = bench.launch_rollout(env, acts, n)
+    torch.cuda.synchronize()
+    n = schedule[-1]
+    for name, x in zip(("obs", "reward", "terminated", "truncated"), out):
+        got = np.load(tmp_path / "one" / (name + ".npy"))
+        assert np.array_equal(got, x[n - 1].cpu().numpy().astype(np.float32)), name
+    assert not np.array_equal(np.load(tmp_path / "one" / "obs.npy"), out[0][n - 2].cpu().numpy())

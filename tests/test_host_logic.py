@@ -8,7 +8,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ASSETS, REPO, urdf
+from conftest import ASSETS, GOLDEN, REPO, urdf
 
 
 def test_constants_match_survey_appendix_d():
@@ -50,14 +50,17 @@ def test_name_based_and_positional_parsers_agree(model):
     np.testing.assert_array_equal(a.PROP_OFFSETS, b.PROP_OFFSETS)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout not present")
 @pytest.mark.parametrize("model", ["cf2x", "cf2p", "racer"])
 def test_shipped_assets_carry_the_reference_constants(model):
+    """tests/golden/reference_urdf_constants.npz: every field of `UrdfConstants` read from the reference's own
+    assets/<model>.urdf, recorded as `<model>/<field>`."""
     from oracle.aviary_oracle import UrdfConstants
     mine = UrdfConstants(urdf(model), model)
-    ref = UrdfConstants(f"/root/reference/gym_pybullet_drones/assets/{model}.urdf", model)
-    for k, v in vars(ref).items():
-        np.testing.assert_array_equal(getattr(mine, k), v, err_msg=k)
+    ref = np.load(os.path.join(GOLDEN, "reference_urdf_constants.npz"))
+    keys = [k for k in ref.files if k.startswith(model + "/")]
+    assert len(keys) == len(vars(mine)) > 20
+    for k in keys:
+        np.testing.assert_array_equal(getattr(mine, k.split("/", 1)[1]), ref[k], err_msg=k)
 
 
 def test_enums_are_value_compatible():
