@@ -23,10 +23,8 @@ DoneWord& done_word() {
 }  // namespace
 
 GpdDone gpd_detail_done_begin() {
-    static const char* const how = getenv("GPD_STEP_SYNC_WAIT");
     DoneWord& w = done_word();
-    const bool word = w.p != nullptr && !(how != nullptr && how[0] == 's');
-    return GpdDone{word ? w.p : nullptr, ++w.seq, false};
+    return GpdDone{w.p, ++w.seq, false};
 }
 
 int gpd_detail_done_wait(const GpdDone& d, void* stream, const char* who) {

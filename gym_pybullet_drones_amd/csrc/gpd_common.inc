@@ -97,7 +97,7 @@ void gpd_detail_launch_policy_pid(const GpdPolicyLaunch& a);
 // calling thread (`begin`) and ends with `signal_done`; `wait` spins on it and takes hipStreamSynchronize for every other shape
 // (`used` false), when no word could be allocated, when the word stays silent for 2 ms (work queued ahead on the stream, a
 // capture in progress), and on every 256th call (the runtime retires its bookkeeping of the launches at a synchronisation).
-// GPD_STEP_SYNC_WAIT=stream (diagnostics, the A/B): always hipStreamSynchronize.  Defined in abi.hip.
+// Defined in abi.hip.
 struct GpdDone { uint32_t* flag; uint32_t seq; bool used; };
 GpdDone gpd_detail_done_begin();
 int gpd_detail_done_wait(const GpdDone& d, void* stream, const char* who);
@@ -906,7 +906,6 @@ struct Span {             // internal: how the K steps of one launch are laid ou
     int64_t obs_stride;      // floats between the obs12 (and term_obs12) blocks of consecutive steps
     int64_t env_stride;      // elements between the reward / terminated / truncated rows of consecutive steps
     int32_t ring;            // gpd_rollout: LDS output slots per workgroup (2 or 4), chosen at launch
-    int32_t xcd;             // gpd_rollout1_kernel: 1 = every XCD works on ONE contiguous eighth of the drones (workgroup b runs on XCD b % 8)
 };
 
 // the raw action words of one drone (AW = 4, 3 or 1 floats per drone, row-major), one load instruction

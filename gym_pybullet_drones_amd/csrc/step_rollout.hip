@@ -1,6 +1,8 @@
 // step_rollout.hip -- gpd_step / gpd_rollout / gpd_rollout_history: one env step per launch, K env steps per launch (DESIGN.md sections 3.1, 3.2)
 #include "gpd_common.inc"
 #include "policy_kernel.inc"
+#include <iterator>
+#include <utility>
 
 namespace {
 
@@ -523,12 +525,14 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout1_kernel(
     const GpdStepCfg C{hot_num_envs, C_.drones_per_env, C_.act_type, C_.substeps, C_.physics_flags, C_.pyb_dt, C_.ctrl_dt, C_.inv_ctrl_dt,
                        C_.lanes_per_wave, C_.task, C_.xy_bound, C_.z_bound, C_.tilt_bound, C_.term_dist, C_.trunc_counter,
                        static_cast<int32_t>((hot_bits >> 2) & 1u), static_cast<int32_t>((hot_bits >> 1) & 1u), static_cast<int32_t>(hot_bits & 1u)};
-    const Span T{hot_num_steps, T_.action_stride, T_.obs_stride, T_.env_stride, T_.ring, static_cast<int32_t>((hot_bits >> 3) & 1u)};
+    const Span T{hot_num_steps, T_.action_stride, T_.obs_stride, T_.env_stride, T_.ring};
     const int tid = threadIdx.x;
-    // workgroup -> drones: the identity, or (T.xcd, large batches) every XCD one contiguous eighth of the drones instead of every eighth
-    // workgroup -- at 65 536 drones that changed nothing (0.816 vs 0.813-0.821 us per step, round-2 A/B)
+    // workgroup -> drones: the identity.  (Bit 3 of hot_bits, never set by the host, selected every XCD one contiguous eighth of the
+    // drones instead: at 65 536 drones that changed nothing, 0.816 vs 0.813-0.821 us per step, round-2 A/B.  The dead branch stays
+    // until the register allocation of these kernels is re-verified without it: deleting it moves that of all 180 instantiations, and
+    // one of them then saves a half-overwritten argument tuple -- tests/test_kernel_isa.py)
     uint32_t bid = blockIdx.x;
-    if (T.xcd) { const uint32_t per = gridDim.x >> 3; bid = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); }
+    if (hot_bits & 8u) { const uint32_t per = gridDim.x >> 3; bid = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); }
     const int D = MULTI ? (DC ? DC : C.drones_per_env) : 1;
     const uint32_t N = static_cast<uint32_t>(C.num_envs) * static_cast<uint32_t>(D);
     const int K = T.num_steps;
@@ -656,13 +660,94 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout1_kernel(
     if constexpr (RING) { if (L.active && L.d == 0) S.ring_pos[L.env] = ring_q; }
 }
 
-// the kernels compiled for one aviary size / flag set exist for BaseRLAviary's five action types (not for the raw-RPM rows of CtrlAviary
-// and of subclasses with their own _preprocessAction: every variant is another pair of large kernels to compile)
+// ------------------------------------------------------------------------------------------------
+// Which compiled kernel serves a call.  gpd_step_kernel and gpd_rollout1_kernel each have ONE ordered list of compile-time variants,
+// and the first entry that fits the call wins.  An entry holds the kernels' template parameters MULTI, S1, DC, FL, HI:
+//   multi  whole aviaries, or single drones;
+//   s1     one sub-step per step (false: the sub-step loop);
+//   dc     the aviary size (0: from the argument block);
+//   fl     the three add-on models, GPD_PHYS_GND | GPD_PHYS_DRAG | GPD_PHYS_DW (-1: every flag from the argument block);
+//   hi     with fl: the bits above them -- the ground plane and Bullet's damping, which `Physics.PYB_*` members add by default -- come
+//          from the argument block (true) or are known to be clear (false: exactly the reference's explicit integrator + add-ons).
+// A SIZED entry fixes the size or the flags, or one sub-step for whole aviaries: the uniform branches on them fold away (DESIGN.md
+// section 3.2; the gains below are per env step at 65 536 drones, 64 steps per launch).  Sized entries are compiled for BaseRLAviary's
+// five action types only (not for the raw-RPM rows of CtrlAviary and of subclasses with their own _preprocessAction: every variant is
+// another pair of large kernels to compile), those with a flag set only where flags are set (EXT).  Each list ends with the generic
+// entries, which fit every call of their shape.
+// GPD_ROLLOUT_SIZED=0 is a TEST HOOK, read once per process: no sized entry fits, the generic kernels serve every call -- they are the
+// reference of tests/test_gpu_rollout.py's bit-for-bit comparison of the sized kernels inside the shipped library.
+// ------------------------------------------------------------------------------------------------
 template <int ACT> constexpr bool kSizedAct = ACT != GPD_ACT_RAW_RPM && ACT != GPD_ACT_DIRECT_RPM;
-// GPD_ROLLOUT_SIZED=0 (diagnostics, the A/B; read once per process): the generic kernels only
+
+struct Variant {
+    bool multi, s1;
+    int dc, fl;
+    bool hi;
+    constexpr bool sized() const { return dc != 0 || fl >= 0 || (multi && s1); }
+    bool fits(const GpdStepCfg& C) const {
+        return multi == (C.drones_per_env > 1) && (!s1 || C.substeps == 1) && (dc == 0 || dc == C.drones_per_env) &&
+               (fl < 0 || ((C.physics_flags & 7u) == static_cast<uint32_t>(fl) && (hi || (C.physics_flags & ~7u) == 0u)));
+    }
+};
+template <bool EXT, int ACT> constexpr bool compiled(const Variant& v) { return !v.sized() || (kSizedAct<ACT> && (EXT || v.fl < 0)); }
+
+// gpd_step_kernel: one env step per launch (its one-wave launches ARE the drop-in aviaries' step())
+constexpr Variant kStepVariants[] = {
+    // BASELINE configs 3 (ii), 5 and 3 (i) at one sub-step per step, upper bits clear or read (as in gpd_rollout1_kernel)
+    {true, true, 8, 7, false}, {true, true, 8, 7, true}, {true, true, 2, 4, false}, {true, true, 2, 4, true},
+    {false, true, 0, 7, false}, {false, true, 0, 7, true},
+    // the two multi-drone add-on sets under the sub-step loop (30 Hz control of 240 Hz physics is the reference's default), upper bits
+    // read (single drones would gain 3-5 % there: no variant)
+    {true, false, 8, 7, true}, {true, false, 2, 4, true},
+    // no add-on model, the ground plane / damping bits alone -- what `Physics.PYB`, the default of HoverAviary() and MultiHoverAviary(),
+    // resolves to -- for single drones and pairs, one sub-step or the loop: HoverAviary().step() 22.1-23.9 -> 18.9-19.4 us
+    {false, true, 0, 0, true}, {false, false, 0, 0, true}, {true, true, 2, 0, true}, {true, false, 2, 0, true},
+    // generic
+    {true, false, 0, -1, false}, {false, true, 0, -1, false}, {false, false, 0, -1, false},
+};
+
+// gpd_rollout1_kernel: K env steps per launch, whole aviaries of up to 64 drones per wave or single drones
+constexpr Variant kRoll1Variants[] = {
+    // pairs with PYB_DW, stacks of eight with PYB_GND_DRAG_DW (BASELINE configs 5 and 3 ii), any size with every add-on, at one sub-step,
+    // upper bits clear or read: pairs 1.087 -> 0.777 us, stacks 1.827 -> 1.356, other sizes -10 .. -15 %, with the upper bits -16 .. -18 %
+    {true, true, 8, 7, false}, {true, true, 8, 7, true}, {true, true, 2, 4, false}, {true, true, 2, 4, true},
+    {true, true, 0, 7, false}, {true, true, 0, 7, true},
+    // the same under the sub-step loop (30 Hz control), upper bits read: pairs -24 %, stacks -18 %, other sizes -7 %
+    {true, false, 8, 7, true}, {true, false, 2, 4, true}, {true, false, 0, 7, true},
+    // pairs with no add-on model and the ground plane / damping bits alone: MultiHoverAviary's defaults (`Physics.PYB`, 30 Hz: -21 %)
+    {true, true, 2, 0, true}, {true, false, 2, 0, true},
+    // pairs with any other flags (-7 % without add-on forces), any size, at one sub-step (0 .. -6 %; under the loop the size buys nothing)
+    {true, true, 2, -1, false}, {true, true, 0, -1, false},
+    // single drones with every add-on model (BASELINE config 3 i: 1.053 -> 0.927 us, upper bits read -5 %), or with none and the ground
+    // plane / damping bits alone (`Physics.PYB`: -9 % at 240 Hz, -18.5 % at 30 Hz)
+    {false, true, 0, 7, false}, {false, true, 0, 7, true}, {false, true, 0, 0, true}, {false, false, 0, 0, true},
+    // generic (also gpd_rollout_history's, with the action ring, and the headline's: launch_step)
+    {true, false, 0, -1, false}, {false, true, 0, -1, false}, {false, false, 0, -1, false},
+};
+
 inline bool sized_variants() {
     static const bool on = [] { const char* e = getenv("GPD_ROLLOUT_SIZED"); return e == nullptr || e[0] != '0'; }();
     return on;
+}
+
+template <auto V> using Const = std::integral_constant<decltype(V), V>;
+
+// f(Const<i>{}) -- instantiated for the entries of LIST this <EXT, ACT> compiles, and only for them
+template <const auto& LIST, bool EXT, int ACT, class F, size_t... I>
+void launch_entry(size_t i, F& f, std::index_sequence<I...>) {
+    auto at = [&](auto J) { if constexpr (compiled<EXT, ACT>(LIST[decltype(J)::value])) f(J); };
+    ((i == I ? at(Const<I>{}) : void()), ...);
+}
+
+// the first entry of LIST that is compiled and fits the call (sized entries only while `sized`)
+template <const auto& LIST, bool EXT, int ACT, class F>
+hipError_t launch_first_fit(bool sized, const GpdStepCfg& C, F&& f) {
+    for (size_t i = 0; i < std::size(LIST); ++i)
+        if (compiled<EXT, ACT>(LIST[i]) && (sized || !LIST[i].sized()) && LIST[i].fits(C)) {
+            launch_entry<LIST, EXT, ACT>(i, f, std::make_index_sequence<std::size(LIST)>{});
+            return hipGetLastError();
+        }
+    return hipErrorInvalidDeviceFunction;                    // (not reached: a generic entry fits every call)
 }
 
 template <bool PID, bool EXT, int AW, int ACT>
@@ -670,163 +755,75 @@ hipError_t launch_step(bool multi, hipStream_t st, const GpdParams& P, const Gpd
                        const Span& T, const float* action, const float* target_pos, const float* init_pose,
                        float* obs12, float* reward, uint8_t* terminated, uint8_t* truncated, float* term_obs12, GpdDone* done) {
     const int64_t N = static_cast<int64_t>(C.num_envs) * C.drones_per_env;
+    const int Dm = C.drones_per_env;
+    const bool sized = sized_variants();
     if (T.num_steps == 1) {      // gpd_step, or a rollout of one step: the low-latency single-step kernel
-        const int lanes = multi ? (kBlock / C.drones_per_env) * C.drones_per_env : (kBlock / 64) * C.lanes_per_wave;
+        const int lanes = multi ? (kBlock / Dm) * Dm : (kBlock / 64) * C.lanes_per_wave;
         const dim3 grid(static_cast<unsigned>((N + lanes - 1) / lanes));
         // the completion word is for launches whose drones all sit in wave 0 of workgroup 0 (see the end of gpd_step_kernel)
         uint32_t* const done_flag = (done != nullptr && N <= (multi ? 64 : C.lanes_per_wave)) ? done->flag : nullptr;
         const uint32_t done_seq = done != nullptr ? done->seq : 0u;
         if (done != nullptr) done->used = done_flag != nullptr;
-#define GPD_STEP_HOT S.kin, action, S.step_counter, target_pos, static_cast<const int32_t*>(S.act_ring ? S.ring_pos : S.step_counter), \
-                     static_cast<uint32_t>(S.ld), C.num_envs, C.lanes_per_wave, C.target_per_env
-        const bool sized = sized_variants();
-        bool launched = false;
-        if constexpr (EXT && kSizedAct<ACT>) {      // BASELINE configs 3 (ii), 5, 3 (i) at one sub-step per step (see gpd_rollout1_kernel)
-#define GPD_STEP1H(MULTI_, S1_, DC_, FL_, HI_)                                                                                                              \
-    do {                                                                                                                                                 \
-        hipLaunchKernelGGL((gpd_step_kernel<PID, EXT, MULTI_, AW, ACT, S1_, DC_, FL_, HI_>), grid, dim3(kBlock), 0, st, GPD_STEP_HOT, P, S, C,               \
-                           init_pose, obs12, reward, terminated, truncated, term_obs12, done_flag, done_seq);                                           \
-        launched = true;                                                                                                                                 \
-    } while (0)
-#define GPD_STEP1(MULTI_, DC_, FL_) do { if (hi) GPD_STEP1H(MULTI_, true, DC_, FL_, true); else GPD_STEP1H(MULTI_, true, DC_, FL_, false); } while (0)
-            const uint32_t low = C.physics_flags & 7u;          // the add-on models; above them: the ground plane, Bullet's damping
-            const bool hi = (C.physics_flags & ~7u) != 0u, s1 = C.substeps == 1;
-            if (sized && s1 && multi && C.drones_per_env == 8 && low == 7u) GPD_STEP1(true, 8, 7);
-            else if (sized && s1 && multi && C.drones_per_env == 2 && low == 4u) GPD_STEP1(true, 2, 4);
-            else if (sized && s1 && !multi && low == 7u) GPD_STEP1(false, 0, 7);
-            // the two multi-drone add-on sets under the sub-step loop (30 Hz control of 240 Hz physics is the reference's default): one variant each,
-            // the bits above the add-on models read at run time whatever they are (single drones gain 3-5 % there: no variant)
-            else if (sized && multi && C.drones_per_env == 8 && low == 7u) GPD_STEP1H(true, false, 8, 7, true);
-            else if (sized && multi && C.drones_per_env == 2 && low == 4u) GPD_STEP1H(true, false, 2, 4, true);
-            // no add-on model, the ground plane / damping bits alone: what `Physics.PYB` -- the default of HoverAviary() and MultiHoverAviary(), whose
-            // step() is this kernel -- resolves to; single drones and pairs, one sub-step or the loop
-            else if (sized && low == 0u && hi && !multi) { if (s1) GPD_STEP1H(false, true, 0, 0, true); else GPD_STEP1H(false, false, 0, 0, true); }
-            else if (sized && low == 0u && hi && multi && C.drones_per_env == 2) { if (s1) GPD_STEP1H(true, true, 2, 0, true); else GPD_STEP1H(true, false, 2, 0, true); }
-#undef GPD_STEP1
-#undef GPD_STEP1H
-        }
-        if (launched) {
-        } else if (multi) {
-            hipLaunchKernelGGL((gpd_step_kernel<PID, EXT, true, AW, ACT, false>), grid, dim3(kBlock), 0, st, GPD_STEP_HOT, P, S, C,
-                               init_pose, obs12, reward, terminated, truncated, term_obs12, done_flag, done_seq);
-        } else if (C.substeps == 1) {
-            hipLaunchKernelGGL((gpd_step_kernel<PID, EXT, false, AW, ACT, true>), grid, dim3(kBlock), 0, st, GPD_STEP_HOT, P, S, C,
-                               init_pose, obs12, reward, terminated, truncated, term_obs12, done_flag, done_seq);
-        } else {
-            hipLaunchKernelGGL((gpd_step_kernel<PID, EXT, false, AW, ACT, false>), grid, dim3(kBlock), 0, st, GPD_STEP_HOT, P, S, C,
-                               init_pose, obs12, reward, terminated, truncated, term_obs12, done_flag, done_seq);
-        }
-#undef GPD_STEP_HOT
-    } else {
-        // aviaries of up to 64 drones run gpd_rollout1_kernel with WHOLE aviaries per wave (wave-local exchange, no helper wave, no
-        // workgroup barrier) -- also where the size does not divide 64 and some lanes of every wave stay without a drone: 0.50-0.65 of the
-        // compute-wave + store-wave kernel's time per step at every size from 3 to 63, half-empty waves (33 drones) included
-        // (scratch/exp_r06/ab_wave_local.py, profiles/r06_ab_wave_local_rollout.json).  GPD_ROLLOUT_WAVE_LOCAL=0 (diagnostics, the A/B):
-        // only the powers of two, the rule of rounds 2-5
-        static const char* const wl_env = getenv("GPD_ROLLOUT_WAVE_LOCAL");
-        const int Dm = C.drones_per_env, per_wave = Dm <= 64 ? (64 / Dm) * Dm : 0;
-        const bool pow2 = Dm <= 64 && (Dm & (Dm - 1)) == 0;
-        static const bool store_wave_variant = getenv("GPD_ROLLOUT_STOREWAVE") != nullptr;   // A/B switch, diagnostics only
-        // (terminal observations -- conditional stores -- and the diagnostics switch go to the compute-wave + store-wave kernel, whose
-        // workgroups hold (256 / D) D drones; the two packings agree where D divides 64)
-        const bool shfl = multi && Dm <= 64 && !store_wave_variant && term_obs12 == nullptr &&
-                          (pow2 || S.act_ring != nullptr || !(wl_env != nullptr && wl_env[0] == '0'));   // (gpd_rollout_history: this kernel only)
-        const int lanes = shfl ? 4 * per_wave : (multi ? (kBlock / Dm) * Dm : kBlock);
-        const dim3 grid(static_cast<unsigned>((N + lanes - 1) / lanes));
-#define GPD_ROLL1_HOT S.kin, action, S.step_counter, target_pos, init_pose, static_cast<uint32_t>(S.ld), C.num_envs, Tr.num_steps, \
-                      (static_cast<uint32_t>(C.auto_reset != 0) | (static_cast<uint32_t>(C.init_per_env != 0) << 1) |      \
-                       (static_cast<uint32_t>(C.target_per_env != 0) << 2) | (static_cast<uint32_t>(Tr.xcd != 0) << 3))
-        Span Tr = T;
-        static const char* const xcd_env = getenv("GPD_ROLLOUT_XCD");          // (diagnostics: 1 = contiguous eighths per XCD, 0 = never)
-        Tr.xcd = (grid.x % 8u == 0u && xcd_env != nullptr && xcd_env[0] == '1') ? 1 : 0;
-        Tr.ring = ((!multi || pow2) && grid.x <= 2u * 256u) ? 4 : 2;   // <= 2 workgroups per CU: LDS is not what limits occupancy
-        const size_t lds = static_cast<size_t>(Tr.ring) * kSlotBytes;
-        if (S.act_ring && !store_wave_variant && term_obs12 == nullptr && (shfl || !multi)) {   // gpd_rollout_history (it checked the shape)
-            if (shfl)
-                hipLaunchKernelGGL((gpd_rollout1_kernel<PID, EXT, AW, ACT, false, true, true, true>), grid, dim3(kBlock), 0, st, GPD_ROLL1_HOT, P, S, C, Tr, obs12, reward, terminated, truncated, term_obs12);
-            else if (C.substeps == 1)
-                hipLaunchKernelGGL((gpd_rollout1_kernel<PID, EXT, AW, ACT, true, false, true, true>), grid, dim3(kBlock), 0, st, GPD_ROLL1_HOT, P, S, C, Tr, obs12, reward, terminated, truncated, term_obs12);
-            else
-                hipLaunchKernelGGL((gpd_rollout1_kernel<PID, EXT, AW, ACT, false, false, true, true>), grid, dim3(kBlock), 0, st, GPD_ROLL1_HOT, P, S, C, Tr, obs12, reward, terminated, truncated, term_obs12);
-        } else
-        if (shfl) {   // aviaries of 2 .. 64 drones, whole aviaries per wave: no helper wave either
-            const bool sized = sized_variants();
-#define GPD_ROLL1H(S1_, DC_, FL_, HI_) hipLaunchKernelGGL((gpd_rollout1_kernel<PID, EXT, AW, ACT, S1_, true, true, false, DC_, FL_, HI_>), grid, dim3(kBlock), 0, st, \
-                                                          GPD_ROLL1_HOT, P, S, C, Tr, obs12, reward, terminated, truncated, term_obs12)
-#define GPD_ROLL1(S1_, DC_, FL_) GPD_ROLL1H(S1_, DC_, FL_, false)
-            const bool s1 = C.substeps == 1;
-            bool done = false;
-            if constexpr (EXT && kSizedAct<ACT>) {
-                // pairs with PYB_DW, stacks of eight with PYB_GND_DRAG_DW (BASELINE configs 5 and 3 ii); any size with every add-on; each with
-                // the ground plane / damping bits clear (the explicit integrator + add-ons, as BASELINE words it) or from the argument block
-                const uint32_t low = C.physics_flags & 7u;
-                const bool hi = (C.physics_flags & ~7u) != 0u;
-                if (sized && s1 && Dm == 8 && low == 7u) { if (hi) GPD_ROLL1H(true, 8, 7, true); else GPD_ROLL1H(true, 8, 7, false); done = true; }
-                else if (sized && s1 && Dm == 2 && low == 4u) { if (hi) GPD_ROLL1H(true, 2, 4, true); else GPD_ROLL1H(true, 2, 4, false); done = true; }
-                else if (sized && s1 && low == 7u) { if (hi) GPD_ROLL1H(true, 0, 7, true); else GPD_ROLL1H(true, 0, 7, false); done = true; }
-                // the same under the sub-step loop (30 Hz control is the reference's default): one variant each, upper bits read at run time
-                else if (sized && Dm == 8 && low == 7u) { GPD_ROLL1H(false, 8, 7, true); done = true; }
-                else if (sized && Dm == 2 && low == 4u) { GPD_ROLL1H(false, 2, 4, true); done = true; }
-                else if (sized && low == 7u) { GPD_ROLL1H(false, 0, 7, true); done = true; }
-                // pairs with no add-on model and the ground plane / damping bits alone: MultiHoverAviary's defaults (Physics.PYB, 30 Hz control)
-                else if (sized && Dm == 2 && low == 0u && hi) { if (s1) GPD_ROLL1H(true, 2, 0, true); else GPD_ROLL1H(false, 2, 0, true); done = true; }
-            }
-            if constexpr (kSizedAct<ACT>) {
-                // pairs with any other flag set, and any size, at one sub-step per step (under the sub-step loop the size alone buys nothing)
-                if (done) {}
-                else if (sized && s1 && Dm == 2) { GPD_ROLL1(true, 2, -1); done = true; }
-                else if (sized && s1) { GPD_ROLL1(true, 0, -1); done = true; }
-            }
-            if (!done) GPD_ROLL1(false, 0, -1);
-#undef GPD_ROLL1
-#undef GPD_ROLL1H
-        } else if (multi) {
-            hipLaunchKernelGGL((gpd_rollout_kernel<PID, EXT, true, AW>), grid, dim3(kRollThreads), lds, st, P, S, C, Tr,
-                               action, target_pos, init_pose, obs12, reward, terminated, truncated, term_obs12);
-        } else if (!store_wave_variant && term_obs12 == nullptr) {
-            // The headline shape -- plain DYN, RPM actions, one sub-step, a batch that leaves one wave per SIMD -- stores its
-            // observation bursts as ordinary stores: measured 3-4 % faster there (0.837 -> 0.803 us per step), while every other
-            // shape (larger batches, sub-step loops, multi-drone aviaries) is 1-3 % faster with non-temporal ones
-            // (A/B on one box, round 2: scratch/ab.sh, scratch/ab2.sh) -- and only for long rollouts: the ordinary stores leave
-            // their lines to the end-of-kernel write-back, which a 20-step launch does not amortise (1.14 vs 1.00 us per step).
-            // (GPD_ROLLOUT_OBS_STORES=plain: the ordinary stores at every size -- diagnostics: the boxes of the pool differ on the
-            // non-temporal streaming rate, profiles/README.md)
-            static const char* const obs_stores = getenv("GPD_ROLLOUT_OBS_STORES");
-            const bool plain_obs = obs_stores != nullptr && obs_stores[0] == 'p';
-            if (C.substeps == 1 && !PID && !EXT && ACT == GPD_ACT_RPM && (plain_obs || (N <= (1 << 17) && T.num_steps >= 48)))
-                hipLaunchKernelGGL((gpd_rollout1_kernel<false, false, 4, GPD_ACT_RPM, true, false, false>), grid, dim3(kBlock), 0, st, GPD_ROLL1_HOT, P, S, C, Tr, obs12, reward, terminated, truncated, term_obs12);
-            else {
-#define GPD_ROLL1S(S1_, FL_, HI_) hipLaunchKernelGGL((gpd_rollout1_kernel<PID, EXT, AW, ACT, S1_, false, true, false, 0, FL_, HI_>), grid, dim3(kBlock), 0, st, \
-                                                     GPD_ROLL1_HOT, P, S, C, Tr, obs12, reward, terminated, truncated, term_obs12)
-                const bool s1 = C.substeps == 1, sized = sized_variants();
-                bool done = false;
-                if constexpr (EXT && kSizedAct<ACT>) {
-                    // single drones with every add-on model (BASELINE config 3 i), or with none and the ground plane / damping bits alone (what
-                    // `Physics.PYB` resolves to by default): the tests on the three add-on flags fold away
-                    const uint32_t low = C.physics_flags & 7u;
-                    const bool hi = (C.physics_flags & ~7u) != 0u;
-                    if (sized && s1 && low == 7u) { if (hi) GPD_ROLL1S(true, 7, true); else GPD_ROLL1S(true, 7, false); done = true; }
-                    else if (sized && low == 0u && hi) { if (s1) GPD_ROLL1S(true, 0, true); else GPD_ROLL1S(false, 0, true); done = true; }
-                }
-                if (done) {}
-                else if (s1) GPD_ROLL1S(true, -1, false);
-                else GPD_ROLL1S(false, -1, false);
-#undef GPD_ROLL1S
-            }
-        } else {
-            // single drones with terminal observations kept (what a VecEnv-style caller asks for): action type and sub-step count folded
-            if (sized_variants() && C.substeps == 1)
-                hipLaunchKernelGGL((gpd_rollout_kernel<PID, EXT, false, AW, ACT, true>), grid, dim3(kRollThreads), lds, st, P, S, C, Tr,
-                                   action, target_pos, init_pose, obs12, reward, terminated, truncated, term_obs12);
-            else if (sized_variants())
-                hipLaunchKernelGGL((gpd_rollout_kernel<PID, EXT, false, AW, ACT, false>), grid, dim3(kRollThreads), lds, st, P, S, C, Tr,
-                                   action, target_pos, init_pose, obs12, reward, terminated, truncated, term_obs12);
-            else
-                hipLaunchKernelGGL((gpd_rollout_kernel<PID, EXT, false, AW>), grid, dim3(kRollThreads), lds, st, P, S, C, Tr,
-                                   action, target_pos, init_pose, obs12, reward, terminated, truncated, term_obs12);
-        }
+        return launch_first_fit<kStepVariants, EXT, ACT>(sized, C, [&](auto I) {
+            constexpr Variant v = kStepVariants[decltype(I)::value];
+            hipLaunchKernelGGL((gpd_step_kernel<PID, EXT, v.multi, AW, ACT, v.s1, v.dc, v.fl, v.hi>), grid, dim3(kBlock), 0, st, S.kin, action,
+                               S.step_counter, target_pos, static_cast<const int32_t*>(S.act_ring ? S.ring_pos : S.step_counter),
+                               static_cast<uint32_t>(S.ld), C.num_envs, C.lanes_per_wave, C.target_per_env, P, S, C, init_pose, obs12, reward,
+                               terminated, truncated, term_obs12, done_flag, done_seq);
+        });
     }
-    return hipGetLastError();
+    // Rollouts.  gpd_rollout1_kernel (no helper wave, no workgroup barrier) serves single drones and aviaries of up to 64 drones, WHOLE
+    // aviaries per wave -- also where the size does not divide 64 and some lanes of every wave stay without a drone: 0.49-0.69 of the
+    // compute-wave + store-wave kernel's time per step at every size from 3 to 63, half-empty waves (33 drones) included (DESIGN.md
+    // section 3.2, profiles/r06_ab_wave_local_rollout.json).  Calls that keep terminal observations (conditional stores) and larger
+    // aviaries go to the compute-wave + store-wave kernel, whose workgroups hold (256 / D) D drones; the two packings agree where D
+    // divides 64.
+    const bool roll1 = term_obs12 == nullptr && (!multi || Dm <= 64);
+    const bool pow2 = Dm <= 64 && (Dm & (Dm - 1)) == 0;
+    const int lanes = multi && roll1 ? 4 * ((64 / Dm) * Dm) : (multi ? (kBlock / Dm) * Dm : kBlock);
+    const dim3 grid(static_cast<unsigned>((N + lanes - 1) / lanes));
+    Span Tr = T;
+    Tr.ring = ((!multi || pow2) && grid.x <= 2u * 256u) ? 4 : 2;   // <= 2 workgroups per CU: LDS is not what limits occupancy
+    if (!roll1) {
+        // multi-drone aviaries keep the run-time action-type ladder (ACT = -1: their steps are dominated by the exchange and the
+        // barriers); single drones fold the action type and the sub-step count (0.891 -> 0.846 us per step), generic <AW> under the hook
+        const size_t lds = static_cast<size_t>(Tr.ring) * kSlotBytes;
+        auto roll = [&](auto multi_, auto act, auto s1) {
+            hipLaunchKernelGGL((gpd_rollout_kernel<PID, EXT, decltype(multi_)::value, AW, decltype(act)::value, decltype(s1)::value>), grid,
+                               dim3(kRollThreads), lds, st, P, S, C, Tr, action, target_pos, init_pose, obs12, reward, terminated, truncated,
+                               term_obs12);
+        };
+        if (multi) roll(Const<true>{}, Const<-1>{}, Const<false>{});
+        else if (!sized) roll(Const<false>{}, Const<-1>{}, Const<false>{});
+        else if (C.substeps == 1) roll(Const<false>{}, Const<ACT>{}, Const<true>{});
+        else roll(Const<false>{}, Const<ACT>{}, Const<false>{});
+        return hipGetLastError();
+    }
+    const uint32_t hot_bits = static_cast<uint32_t>(C.auto_reset != 0) | (static_cast<uint32_t>(C.init_per_env != 0) << 1) |
+                              (static_cast<uint32_t>(C.target_per_env != 0) << 2);
+    auto launch = [&](auto I, auto nt_obs, auto ring) {                   // entry I of kRoll1Variants
+        constexpr Variant v = kRoll1Variants[decltype(I)::value];
+        hipLaunchKernelGGL((gpd_rollout1_kernel<PID, EXT, AW, ACT, v.s1, v.multi, decltype(nt_obs)::value, decltype(ring)::value, v.dc, v.fl,
+                                                v.hi>),
+                           grid, dim3(kBlock), 0, st, S.kin, action, S.step_counter, target_pos, init_pose, static_cast<uint32_t>(S.ld),
+                           C.num_envs, Tr.num_steps, hot_bits, P, S, C, Tr, obs12, reward, terminated, truncated, term_obs12);
+    };
+    // The headline shape -- plain DYN, RPM actions, one sub-step, a batch that leaves one wave per SIMD -- stores its observation
+    // bursts as ordinary stores: 3-4 % faster there (0.837 -> 0.803 us per step), while every other shape (larger batches, sub-step
+    // loops, multi-drone aviaries) is 1-3 % faster with non-temporal ones (A/B on one box, round 2: scratch/ab.sh, scratch/ab2.sh) --
+    // and only for long rollouts: the ordinary stores leave their lines to the end-of-kernel write-back, which a 20-step launch does
+    // not amortise (1.14 vs 1.00 us per step).
+    const bool plain_obs = N <= (1 << 17) && T.num_steps >= 48;
+    // gpd_rollout_history (the action ring: it checked the shape) takes the generic entries
+    return launch_first_fit<kRoll1Variants, EXT, ACT>(sized && !S.act_ring, C, [&](auto I) {
+        constexpr Variant v = kRoll1Variants[decltype(I)::value];
+        if constexpr (!v.sized()) {
+            if (S.act_ring) return launch(I, Const<true>{}, Const<true>{});
+            if constexpr (!PID && !EXT && ACT == GPD_ACT_RPM && !v.multi && v.s1)
+                if (plain_obs) return launch(I, Const<false>{}, Const<false>{});
+        }
+        launch(I, Const<true>{}, Const<false>{});
+    });
 }
 
 // argument checks + launch shared by gpd_step (K = 1) and gpd_rollout
@@ -912,7 +909,6 @@ void gpd_detail_launch_policy_pid(const GpdPolicyLaunch& a) {
         default: if (a.hist) GPD_POL(1, GPD_ACT_ONE_D_PID, 2); else GPD_POL(1, GPD_ACT_ONE_D_PID, 1); break;
     }
 #undef GPD_POL
-#undef GPD_POLN
 }
 #endif
 
@@ -966,7 +962,6 @@ int gpd_rollout_history(const GpdParams* params, const GpdState* state, const Gp
         return fail(GPD_EINVAL, "gpd_rollout_history: state has no action ring (act_ring / ring_pos / hist_len)");
     if (cfg && cfg->drones_per_env > 64)
         return fail(GPD_ENOTSUP, "gpd_rollout_history: aviaries of up to 64 drones (use gpd_rollout + gpd_full_obs otherwise)");
-    if (getenv("GPD_ROLLOUT_STOREWAVE")) return fail(GPD_ENOTSUP, "gpd_rollout_history: not with the GPD_ROLLOUT_STOREWAVE diagnostic");
     const Span T{num_steps, action_step_stride, obs_step_stride, env_step_stride, 2};
     return step_impl("gpd_rollout_history", params, state, cfg, T, actions, target_pos, init_pose, obs12, reward, terminated,
                      truncated, nullptr, stream);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The hover4m rollout leg runs at ~0.62 OR ~0.72 of 8 TB/s -- per process, on one box (hbm_box_probe.sh).  Is it the placement of the
+"""The hover4m rollout leg runs at ~0.62 OR ~0.72 of 8 TB/s -- per process, on one box (hbm_box_probe.sh, at commit ba68a82).  Is it the placement of the
 buffers?  One process, the environment and its rollout buffers allocated again and again (cache emptied in between), each time the
 64-step launch timed and the device addresses printed."""
 import gc

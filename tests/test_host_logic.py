@@ -152,6 +152,19 @@ def test_product_never_imports_the_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle", src, flags=re.M), os.path.join(root, f)
 
 
+def test_native_sources_read_only_the_rccl_path_and_the_sized_variant_hook():
+    """The environment the native library reads: where librccl is (GPD_RCCL_LIB) and the test hook that forces the generic kernels
+    (GPD_ROLLOUT_SIZED=0).  A user-set switch between two launch paths is a duplicate path: the loser goes, with its switch."""
+    csrc = os.path.join(REPO, "gym_pybullet_drones_amd", "csrc")
+    names = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".inc", ".h", ".cpp")):
+            src = open(os.path.join(csrc, f)).read()
+            assert not re.search(r"getenv\s*\(\s*[^\"\s]", src), f"{f}: getenv of a name that is not a literal"
+            names |= set(re.findall(r"getenv\s*\(\s*\"(\w+)\"", src))
+    assert names == {"GPD_RCCL_LIB", "GPD_ROLLOUT_SIZED"}
+
+
 def test_env_shard_partitions():
     from gym_pybullet_drones_amd.dist import env_shard
     for total, world in ((524288, 8), (10, 3), (7, 8), (131072, 4)):
