@@ -32,7 +32,7 @@ MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 HIPCC_FLAGS = COMMON_FLAGS + MAX_ILP + ["-shared"]        # (kept under this name for the ISA tests)
 UNITS = (("step_rollout.hip", MAX_ILP + KERNARG_PRELOAD), ("policy.hip", []), ("swarm.hip", MAX_ILP + KERNARG_PRELOAD), ("abi.hip", MAX_ILP))
-HEADERS = ("gpd_common.inc", "policy_kernel.inc")
+HEADERS = ("gpd_common.inc", "policy_kernel.inc", "step_kernel_body.inc", "rollout_kernel_body.inc", "rollout1_kernel_body.inc")
 
 
 class GpdError(RuntimeError):
@@ -132,6 +132,10 @@ _SIGNATURES = {
     "gpd_rollout_history": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg),
                                            ctypes.c_int32, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, _P,
                                            ctypes.c_int64, _P]),
+    "gpd_plant_derive": (ctypes.c_int, [ctypes.POINTER(GpdParams), _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _P, _P]),
+    "gpd_rollout_plant": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg),
+                                         ctypes.c_int32, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, _P,
+                                         ctypes.c_int64, _P, _P, _P]),
     "gpd_rollout_policy": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg), _P,
                                           ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P,
                                           ctypes.POINTER(ctypes.c_float), _P, _P, _P]),
@@ -166,6 +170,14 @@ _SIGNATURES = {
 }
 COMM_ID_BYTES = 128
 GPD_EINVAL, GPD_ERANGE, GPD_ENOTSUP = -1, -2, -3
+
+#: the plant path (include/gpd.h): the nine per-drone scale factors, in the order of GPD_SCALE_* ...
+SCALE_FIELDS = ("mass", "ixx", "iyy", "izz", "kf", "km", "drag_xy", "drag_z", "gnd_eff")
+#: ... and the derived plant rows, in the order of GPD_PLANT_* (the GpdParams field each row replaces; the last two are new)
+PLANT_ROW_FIELDS = ("M", "inv_M", "KF", "GRAVITY", "J[0]", "J[1]", "J[2]", "J_INV[0]", "J_INV[1]", "J_INV[2]", "km_over_kf",
+                    "gnd_eff_coeff", "drag_coeff[0]", "drag_coeff[1]", "drag_coeff[2]", "hover_thrust", "hover_resid", "norm_thrust",
+                    "norm_gap")
+PLANT_ROWS = len(PLANT_ROW_FIELDS)
 
 
 def lib() -> ctypes.CDLL:

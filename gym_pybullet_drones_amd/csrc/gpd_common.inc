@@ -399,6 +399,25 @@ __device__ __forceinline__ float thrust_dev(const GpdParams& P, float rpm) {
 __device__ __forceinline__ float thrust_dev_norm(const GpdParams& P, float e) {
     return P.hover_thrust * (e * (2.0f + e));
 }
+__device__ __forceinline__ fp2 thrust_dev_norm2(const GpdParams& P, fp2 e) {     // (two rotors as a packed pair)
+    return splat(P.hover_thrust) * (e * (splat(2.0f) + e));
+}
+
+// The plant path (gpd_rollout_plant, include/gpd.h GPD_PLANT_*): a lane-local copy of the nominal struct whose plant fields hold the
+// lane's own drone (overwritten BY NAME from its row: the copy then lives in VGPRs, never in scratch).  `hover_thrust` is the drone's
+// F_h = GRAVITY/4, the ground effect's KF*rpm^2 - g_i.  The normalised action types fly rpm = HOVER_RPM*(1 + e) of the NOMINAL airframe,
+// whose thrust is T = s_kf * F_h,nominal (not the drone's F_h): their deviation is T*e*(2 + e) - (F_h - T).  The residual is SUBTRACTED:
+// x - (+0) is x for every x, -0 included, so a nominal row (residual exactly 0) gives the uniform kernels' bits.
+struct PlantParams : GpdParams {
+    float norm_thrust;     // T = s_kf * F_h,nominal
+    float norm_gap;        // F_h - T
+};
+__device__ __forceinline__ float thrust_dev_norm(const PlantParams& P, float e) {
+    return P.norm_thrust * (e * (2.0f + e)) - P.norm_gap;
+}
+__device__ __forceinline__ fp2 thrust_dev_norm2(const PlantParams& P, fp2 e) {
+    return splat(P.norm_thrust) * (e * (splat(2.0f) + e)) - splat(P.norm_gap);
+}
 
 // One physics sub-step (envs/BaseAviary.py:831-877 + :879-892), state in registers.
 //   g[4]        rotor thrusts minus the hover thrust (KF*rpm_i^2 - GRAVITY/4), constant over the sub-steps
@@ -543,6 +562,52 @@ __device__ __forceinline__ void substep(const GpdParams& P, float h, uint32_t fl
 __device__ __forceinline__ float ld_row(const float* __restrict__ base, int64_t ld, int r, uint32_t off4) {
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base + r * ld) + off4);
 }
+// The plant path: the lane's drone's row of the plant table ([GPD_PLANT_ROWS][ld], include/gpd.h) over a lane-local copy of the
+// nominal struct -- the plant fields overwritten by name, everything else (the controller, the action mapping, the geometry) nominal.
+// plant_of<false> is P itself: the uniform kernels' code does not change.
+template <bool PLANT> using plant_t = std::conditional_t<PLANT, PlantParams, const GpdParams&>;
+template <bool PLANT>
+__device__ __forceinline__ plant_t<PLANT> plant_of(const GpdParams& P, const float* __restrict__ rows, int64_t ld, uint32_t off4) {
+    if constexpr (PLANT) {
+        PlantParams Q;
+        static_cast<GpdParams&>(Q) = P;
+        Q.M = ld_row(rows, ld, GPD_PLANT_M, off4);
+        Q.inv_M = ld_row(rows, ld, GPD_PLANT_INV_M, off4);
+        Q.KF = ld_row(rows, ld, GPD_PLANT_KF, off4);
+        Q.GRAVITY = ld_row(rows, ld, GPD_PLANT_GRAVITY, off4);
+        Q.J[0] = ld_row(rows, ld, GPD_PLANT_J, off4);
+        Q.J[1] = ld_row(rows, ld, GPD_PLANT_J + 1, off4);
+        Q.J[2] = ld_row(rows, ld, GPD_PLANT_J + 2, off4);
+        Q.J_INV[0] = ld_row(rows, ld, GPD_PLANT_J_INV, off4);
+        Q.J_INV[1] = ld_row(rows, ld, GPD_PLANT_J_INV + 1, off4);
+        Q.J_INV[2] = ld_row(rows, ld, GPD_PLANT_J_INV + 2, off4);
+        Q.km_over_kf = ld_row(rows, ld, GPD_PLANT_KM_OVER_KF, off4);
+        Q.gnd_eff_coeff = ld_row(rows, ld, GPD_PLANT_GND_EFF, off4);
+        Q.drag_coeff[0] = ld_row(rows, ld, GPD_PLANT_DRAG, off4);
+        Q.drag_coeff[1] = ld_row(rows, ld, GPD_PLANT_DRAG + 1, off4);
+        Q.drag_coeff[2] = ld_row(rows, ld, GPD_PLANT_DRAG + 2, off4);
+        Q.hover_thrust = ld_row(rows, ld, GPD_PLANT_HOVER_THRUST, off4);
+        Q.hover_resid = ld_row(rows, ld, GPD_PLANT_HOVER_RESID, off4);
+        Q.norm_thrust = ld_row(rows, ld, GPD_PLANT_NORM_THRUST, off4);
+        Q.norm_gap = ld_row(rows, ld, GPD_PLANT_NORM_GAP, off4);
+        return Q;
+    } else {
+        (void)rows; (void)ld; (void)off4;
+        return P;
+    }
+}
+// the row's values live here (a kernel that claims its loads with an explicit wait names them before it)
+template <bool PLANT>
+__device__ __forceinline__ void plant_live(const plant_t<PLANT>& Q) {
+    if constexpr (PLANT)
+        asm volatile("" :: "v"(Q.M), "v"(Q.inv_M), "v"(Q.KF), "v"(Q.GRAVITY), "v"(Q.J[0]), "v"(Q.J[1]), "v"(Q.J[2]), "v"(Q.J_INV[0]),
+                           "v"(Q.J_INV[1]), "v"(Q.J_INV[2]), "v"(Q.km_over_kf), "v"(Q.gnd_eff_coeff), "v"(Q.drag_coeff[0]),
+                           "v"(Q.drag_coeff[1]), "v"(Q.drag_coeff[2]), "v"(Q.hover_thrust), "v"(Q.hover_resid), "v"(Q.norm_thrust),
+                           "v"(Q.norm_gap) : "memory");
+    else
+        (void)Q;
+}
+
 template <bool NT = false>   // NT: non-temporal (a working set far beyond the caches is streamed, not kept)
 __device__ __forceinline__ void st_row(float* __restrict__ base, int64_t ld, int r, uint32_t off4, float v) {
     float* p = reinterpret_cast<float*>(reinterpret_cast<char*>(base + r * ld) + off4);
@@ -620,8 +685,8 @@ struct StepOut {          // what one env step hands to the stores
 
 // action -> RPM (computed ONCE per env step from the cached state, BaseAviary.py:341) and the rotor thrusts minus the
 // hover thrust.  DSLPID action types advance the controller members in c.s and read the cached rpy in c.
-template <bool PID, int AW, int ACT>
-__device__ __forceinline__ void map_action(const GpdParams& P, const GpdStepCfg& C, const float4 act, Carry& c,
+template <bool PID, int AW, int ACT, class PP>          // PP: GpdParams, or PlantParams (the plant path)
+__device__ __forceinline__ void map_action(const PP& P, const GpdStepCfg& C, const float4 act, Carry& c,
                                            float rpm[4], float g[4]) {
     const Kin& k = c.k;
     const int act_type = ACT >= 0 ? ACT : C.act_type;
@@ -635,7 +700,7 @@ __device__ __forceinline__ void map_action(const GpdParams& P, const GpdStepCfg&
             // rpm = HOVER_RPM*(1 + 0.05 a), g = thrust_dev_norm(0.05 a): rotors (0,1) and (2,3) as packed pairs
             const fp2 e01 = splat(0.05f) * fp2{act.x, act.y}, e23 = splat(0.05f) * fp2{act.z, act.w};
             const fp2 r01 = fma2(splat(P.hover_rpm), e01, splat(P.hover_rpm)), r23 = fma2(splat(P.hover_rpm), e23, splat(P.hover_rpm));
-            const fp2 g01 = splat(P.hover_thrust) * (e01 * (splat(2.0f) + e01)), g23 = splat(P.hover_thrust) * (e23 * (splat(2.0f) + e23));
+            const fp2 g01 = thrust_dev_norm2(P, e01), g23 = thrust_dev_norm2(P, e23);
             rpm[0] = r01.x; rpm[1] = r01.y; rpm[2] = r23.x; rpm[3] = r23.y;
             g[0] = g01.x; g[1] = g01.y; g[2] = g23.x; g[3] = g23.y;
         } else {           // GPD_ACT_RAW_RPM (clipped to [0, MAX_RPM], envs/CtrlAviary.py:140) or GPD_ACT_DIRECT_RPM (as is)
@@ -693,8 +758,8 @@ __device__ __forceinline__ float pair_mate(float v) {
 }
 
 // ACT >= 0: the action type is a compile-time constant; S1: so is substeps == 1
-template <bool PID, bool EXT, bool MULTI, int AW, int ACT = -1, bool S1 = false>
-__device__ __forceinline__ void env_step(const GpdParams& P, const GpdStepCfg& C, const uint32_t flags, const int D,
+template <bool PID, bool EXT, bool MULTI, int AW, int ACT = -1, bool S1 = false, class PP = GpdParams>
+__device__ __forceinline__ void env_step(const PP& P, const GpdStepCfg& C, const uint32_t flags, const int D,
                                          const Lane& L, const float4 act, const float tgx, const float tgy,
                                          const float tgz, const bool ip_regs, const float* __restrict__ ipose,
                                          const float ip0, const float ip1, const float ip2, const float ip3,

@@ -332,6 +332,9 @@ class SimCore:
         # (an eager loop is bound by this function, not by the kernel -- 9.3 us of host time per call against 3-4 us of GPU
         # time, scratch/host_overhead.py: the structs' references and the persistent buffers' addresses are built once, the
         # stream comes from torch's raw-handle accessor, the device guard is skipped when the device is current already)
+        if self.plant_rows is not None:
+            self._plant_step(action)
+            return self.obs12, self.reward, self.terminated, self.truncated
         a = self._step_args
         if a is None:
             a = self._step_args = (ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg),
@@ -389,7 +392,13 @@ class SimCore:
         self.pushed_history = False
         self.state_version += 1
         with torch.cuda.device(self.device):
-            if push_history and getattr(self, "act_ring", None) is not None and tobs is None:
+            if self.plant_rows is not None:       # (the per-drone plant: gpd_rollout_plant; a history is pushed by full_obs())
+                rc = self.lib.gpd_rollout_plant(ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg),
+                                                K, _ptr(actions), a_stride, _ptr(self.target), _ptr(self.init_pose),
+                                                _ptr(obs), o_stride, _ptr(rew), _ptr(term), _ptr(trunc), e_stride,
+                                                _ptr(tobs), _ptr(self.plant_rows), self._stream())
+                _native.check(rc, "gpd_rollout_plant")
+            elif push_history and getattr(self, "act_ring", None) is not None and tobs is None:
                 # the kernel pushes every step's action into the ring itself (`gpd_rollout_history`)
                 rc = self.lib.gpd_rollout_history(ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg),
                                                   K, _ptr(actions), a_stride, _ptr(self.target), _ptr(self.init_pose),
@@ -397,7 +406,7 @@ class SimCore:
                 if rc != _native.GPD_ENOTSUP:     # only "no fused variant for this shape" falls through (nothing was launched);
                     _native.check(rc, "gpd_rollout_history")     # a real failure must not be retried on an already advanced state
                     self.pushed_history = True
-            if not self.pushed_history:           # (no fused variant for this shape: the caller updates the ring with full_obs())
+            if not self.pushed_history and self.plant_rows is None:   # (no fused variant: the caller updates the ring with full_obs())
                 rc = self.lib.gpd_rollout(ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg),
                                           K, _ptr(actions), a_stride, _ptr(self.target), _ptr(self.init_pose),
                                           _ptr(obs), o_stride, _ptr(rew), _ptr(term), _ptr(trunc), e_stride,
@@ -425,6 +434,9 @@ class SimCore:
         episode that ends inside the launch: `terminal_observations(K)` returns the `[K,N,12]` block (rows of step t of the
         aviaries that ended at step t; the flags say which), and `term_obs12` holds those of the last step -- what SB3's
         `VecEnv` hands its PPO as `infos[i]["terminal_observation"]` (examples/learn.py:61-95)."""
+        if self.plant_rows is not None:
+            raise _native.GpdError("rollout_policy: the policy kernel flies the nominal airframe only; a per-drone plant table is set "
+                                   "(clear_plant() first, or step()/rollout() with the policy outside the kernel)")
         K = int(num_steps)
         if K < 1:
             raise ValueError("num_steps must be >= 1")
@@ -570,6 +582,8 @@ class SimCore:
             state += 4 * 4
         ka = 1 if action_stride_zero else K
         ko = 1 if last_only else K
+        if self.plant_rows is not None:
+            state += _native.PLANT_ROWS * 4               # the drone's plant row, read once per launch
         per_drone = state + ka * self.A * 4 + ko * 12 * 4
         per_env = 2 * 4 + ko * (4 + 2)
         return per_drone * self.N + per_env * self.E
@@ -600,12 +614,97 @@ class SimCore:
             raise ValueError("built without nan_guard=True")
         return self.bad.view(self.E, self.D).any(dim=1)
 
+    # ---- domain randomisation: a plant of its own per drone (include/gpd.h GPD_SCALE_* / GPD_PLANT_*) ----------------------------
+    #: [9, ld] float32 scale factors (rows in `_native.SCALE_FIELDS` order) and the [19, ld] derived rows the kernels read; None until
+    #: the first `set_plant()`
+    plant_scales = None
+    plant_rows = None
+
+    def set_plant(self, scales, mask=None):
+        """Give every drone its own airframe: nine scale factors relative to the nominal one (`_native.SCALE_FIELDS`: mass, ixx,
+        iyy, izz, kf, km, drag_xy, drag_z, gnd_eff).  `scales`: a tensor `[9, E, D]` or `[9, E]` (one airframe per aviary), or a
+        dict {field: tensor [E, D] / [E] / scalar} -- fields it leaves out keep their current values (1.0 on first use).  `mask`
+        (bool/uint8 [E]): only those aviaries change.  The plant changes; what the agent and the controller know does not (the action
+        mapping's HOVER_RPM, the MAX_RPM clip, DSLPID's model and gains stay nominal).  From now on `step()` / `rollout()` run the
+        plant kernels (`gpd_rollout_plant`); `clear_plant()` goes back.  Validated once per call (finite, > 0): one host sync."""
+        if self.host_visible:
+            raise _native.GpdError("set_plant: the host-visible single aviaries fly the nominal airframe only")
+        if self._state.dw_force:
+            raise _native.GpdError("set_plant: a core whose downwash is computed outside the kernel (SwarmAviary) flies the nominal airframe only")
+        full = self._plant_input(scales)
+        bad = ~(torch.isfinite(full) & (full > 0))
+        if bool(bad.any()):
+            raise ValueError("set_plant: every scale must be finite and > 0")
+        self._apply_plant(full, mask)
+
+    def clear_plant(self):
+        """Back to the uniform airframe (the tables are freed)."""
+        self.plant_scales = self.plant_rows = None
+
+    def plant_view(self) -> torch.Tensor:
+        """[9, E, D] VIEW of the scale table (None without one)."""
+        return None if self.plant_scales is None else self.plant_scales[:, :self.N].view(-1, self.E, self.D)
+
+    def _plant_input(self, scales) -> torch.Tensor:
+        """The user's scales as a [9, E, D] float32 device tensor (a new one: the table is written with the mask only)"""
+        F, E, D = len(_native.SCALE_FIELDS), self.E, self.D
+        if isinstance(scales, dict):
+            unknown = set(scales) - set(_native.SCALE_FIELDS)
+            if unknown:
+                raise ValueError(f"set_plant: unknown fields {sorted(unknown)} (fields: {', '.join(_native.SCALE_FIELDS)})")
+            cur = self.plant_view()
+            full = cur.clone() if cur is not None else torch.ones((F, E, D), dtype=torch.float32, device=self.device)
+            for k, v in scales.items():
+                t = torch.as_tensor(v, dtype=torch.float32, device=self.device)
+                if t.ndim == 1 and t.shape[0] == E:
+                    t = t.view(E, 1)
+                if t.ndim > 2 or not all(a in (1, b) for a, b in zip(t.shape[::-1], (D, E))):
+                    raise ValueError(f"set_plant: {k} must be a scalar, [E] or [E, D] (E={E}, D={D}), got {tuple(t.shape)}")
+                full[_native.SCALE_FIELDS.index(k)] = t.expand(E, D)
+            return full
+        t = torch.as_tensor(scales, dtype=torch.float32, device=self.device)
+        if tuple(t.shape) == (F, E):
+            t = t.unsqueeze(2)
+        elif tuple(t.shape) != (F, E, D):
+            raise ValueError(f"set_plant: scales must be [{F}, E, D] or [{F}, E] (E={E}, D={D}), or a dict; got {tuple(t.shape)}")
+        return t.expand(F, E, D).contiguous()
+
+    def _apply_plant(self, full, mask=None):
+        """Write [9, E, D] scales into the table (masked aviaries only) and re-derive their rows -- no validation, no host sync."""
+        first = self.plant_scales is None
+        if first:             # ones (nominal); the padding past N is never read (a lane without a drone reads drone 0)
+            self.plant_scales = torch.ones((len(_native.SCALE_FIELDS), self.ld), dtype=torch.float32, device=self.device)
+            self.plant_rows = torch.empty((_native.PLANT_ROWS, self.ld), dtype=torch.float32, device=self.device)
+        view = self.plant_view()
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+            torch.where(mask.view(1, self.E, 1).bool(), full, view, out=view)
+        else:
+            view.copy_(full)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gpd_plant_derive(ctypes.byref(self._params), _ptr(self.plant_scales), _ptr(None if first else mask), self.E,
+                                           self.D, self.ld, _ptr(self.plant_rows), self._stream())
+        _native.check(rc, "gpd_plant_derive")
+
+    def _plant_step(self, action):
+        """step() with a plant table: a one-step gpd_rollout_plant (the single-step kernel), then the action into the ring"""
+        with torch.cuda.device(self.device):
+            rc = self.lib.gpd_rollout_plant(ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg), 1,
+                                            _ptr(action), 0, _ptr(self.target), _ptr(self.init_pose), _ptr(self.obs12), 0,
+                                            _ptr(self.reward), _ptr(self.terminated), _ptr(self.truncated), 0, _ptr(self.term_obs12),
+                                            _ptr(self.plant_rows), self._stream())
+            _native.check(rc, "gpd_rollout_plant")
+            if getattr(self, "act_ring", None) is not None:       # (gpd_step pushes inside its kernel; the plant path after it)
+                rc = self.lib.gpd_full_obs(ctypes.byref(self._state), 1, self.N, self.D, self.A, _ptr(None), self.N * 12,
+                                           _ptr(action), 0, _ptr(None), 0, self._stream())
+                _native.check(rc, "gpd_full_obs")
+
     # ---- checkpoint / resume (host <-> device copies, off the hot path) ------------------------------
     #: everything a later step can depend on: the integrator state, the controllers' members, the last applied RPMs (drag), the
     #: episode clocks, the latest observation rows and task outputs (a policy rollout starts from `obs12`), and -- with an action
     #: history -- the ring with its positions (the reference's never-reset `action_buffer`, envs/BaseRLAviary.py:65-67)
     _STATE_FIELDS = ("kin", "last_rpm", "pid", "step_counter", "obs12", "reward", "terminated", "truncated", "term_obs12",
-                     "act_ring", "ring_pos", "bad")
+                     "act_ring", "ring_pos", "bad", "plant_scales")
 
     def get_state(self) -> dict:
         """Snapshot (device clones) of the complete simulator state: `set_state(**get_state())` later -- on this core or on
@@ -615,7 +714,7 @@ class SimCore:
         for name in self._STATE_FIELDS:
             t = getattr(self, name, None)
             if t is not None:
-                out[name] = (t[:, :n] if name in ("kin", "last_rpm", "pid") else t).clone()      # (`kin`: the logical rows)
+                out[name] = (t[:, :n] if name in ("kin", "last_rpm", "pid", "plant_scales") else t).clone()      # (`kin`: the logical rows)
         return out
 
     def set_state(self, kin=None, last_rpm=None, pid=None, step_counter=None, **rest):
@@ -626,6 +725,12 @@ class SimCore:
         unknown = set(given) - set(self._STATE_FIELDS)
         if unknown:
             raise TypeError(f"set_state() got unknown state fields {sorted(unknown)}")
+        scales = given.pop("plant_scales", None)
+        if scales is not None:             # [9, N]: the airframes of the snapshot, rows re-derived
+            scales = torch.as_tensor(scales, device=self.device)
+            if tuple(scales.shape) != (len(_native.SCALE_FIELDS), n):
+                raise ValueError(f"set_state: plant_scales has shape {tuple(scales.shape)}, expected ({len(_native.SCALE_FIELDS)}, {n})")
+            self.set_plant(scales.view(-1, self.E, self.D))
         for name, v in given.items():
             t = getattr(self, name, None)
             if v is None or t is None:       # (a snapshot of a core with more optional parts than this one: the rest applies)
@@ -658,4 +763,6 @@ class SimCore:
         if getattr(self, "act_ring", None) is not None:           # action pushed into both halves of the double ring
             per_drone += 2 * self.A * 4
             per_env += 2 * 4                                      # ring position r/w
+        if self.plant_rows is not None:
+            per_drone += _native.PLANT_ROWS * 4                   # the drone's plant row
         return per_drone * self.N + per_env * self.E

@@ -600,6 +600,9 @@ class SwarmAviary:
         The forces a sub-step uses are computed right AFTER the sub-step before it, on the snapshot it left (the same
         positions: `envs/BaseAviary.py:346-347, 785-811`).  After a reset, a `set_state` or any other change of the state behind
         this class's back (call `invalidate()` then -- on every rank of a shared world), the first sub-step computes its own."""
+        if self.core.plant_rows is not None:
+            raise _native.GpdError("SwarmAviary.step: the one-world kernels fly the nominal airframe only, and a per-drone plant table is "
+                                   "set on the core (core.clear_plant())")
         rpm = self._kernel_action(action).contiguous()
         vectors = torch.empty((self.NUM_DRONES, 20), dtype=torch.float32, device=self.device)
         dw = bool(self.flags & PHYS_DW)

@@ -12,10 +12,12 @@ reference, a reset neither clears the action history nor the embedded PID state
 Everything stays on the GPU: actions come in and observations / rewards / flags go out as torch
 tensors on the aviary's device, nothing synchronises with the host.
 """
+import math
+
 import numpy as np
 import torch
 
-from .. import engine
+from .. import _native, engine
 from ..params import DroneParams
 from ..utils.enums import ACT_RAW_RPM, ActionType, DroneModel, ObservationType, Physics
 
@@ -45,9 +47,15 @@ class VectorAviary:
                  track_rpm: bool = False,
                  pyb_like: bool = None,
                  nan_guard: bool = False,
+                 randomize: dict = None,
                  device=None):
+        """`randomize`: domain randomisation of the plant, {field: r} with a field of `_native.SCALE_FIELDS` (mass, ixx, iyy, izz,
+        kf, km, drag_xy, drag_z, gnd_eff) and 0 <= r < 1 -- every drone's scale of that field is drawn from U(1 - r, 1 + r) at
+        construction, for the aviaries `reset()` resets (seeded by its `seed`), and for the aviaries that end and auto-reset in
+        `step()`.  See `set_physical_params` for what the scales change and what stays nominal."""
         if obs != ObservationType.KIN:
             raise NotImplementedError("only ObservationType.KIN is on the MI355X hot path")
+        self.randomize = self._check_randomize(randomize)      # (before any device work)
         self.NUM_ENVS, self.NUM_DRONES = int(num_envs), int(num_drones)
         self.DRONE_MODEL, self.PHYSICS = drone_model, physics
         self.PYB_FREQ, self.CTRL_FREQ = pyb_freq, ctrl_freq
@@ -89,6 +97,10 @@ class VectorAviary:
         self.OBS_DIM = 12 + (self.ACTION_BUFFER_SIZE * self.ACT_DIM if self.full_obs else 0)
         if full_obs:
             self.core.enable_history(self.ACTION_BUFFER_SIZE)
+        if self.randomize:
+            self._rng = torch.Generator(device=self.device)
+            self._rng.seed()
+            self._resample(None)
 
     # ---- gymnasium-VectorEnv-like surface ----------------------------------------------------
     @property
@@ -118,6 +130,10 @@ class VectorAviary:
     def reset(self, seed=None, options=None, mask=None):
         """Reset all aviaries (or those selected by the boolean/uint8 tensor `mask` [E]).  As in the reference the
         action history (and the embedded PID state) survives a reset."""
+        if self.randomize:     # the reset aviaries fly new airframes
+            if seed is not None:
+                self._rng.manual_seed(int(seed))
+            self._resample(mask)
         self.core.reset(mask=mask)
         if self.full_obs:      # rows of the reset poses with the unchanged history tail (ring not advanced)
             self.core.history_rows()
@@ -126,6 +142,8 @@ class VectorAviary:
     def step(self, action: torch.Tensor):
         """action: float32 tensor (E, D, A) on `self.device` -> (obs, reward[E], terminated[E], truncated[E], info)."""
         _, reward, terminated, truncated = self.core.step(action)      # (pushes the action into the ring, if there is one)
+        if self.randomize and self.core.auto_reset:          # the aviaries that ended were reset by the step: new airframes
+            self._resample(terminated | truncated)
         if self.full_obs:
             self.core.history_rows()                         # row assembly: one more launch
         info = {}
@@ -139,6 +157,10 @@ class VectorAviary:
         K = actions.shape[0]
         # (lazy history: the rollout kernel pushes the actions into the ring itself when it has a variant for the shape)
         obs, reward, terminated, truncated = self.core.rollout(actions, push_history=bool(self.lazy_history) and not self.full_obs)
+        if self.randomize and self.core.auto_reset:
+            # an aviary that auto-resets INSIDE the launch keeps its airframe until the launch ends (the kernel has no random numbers);
+            # the aviaries that ended at any of the K steps fly new airframes from the next call on
+            self._resample((terminated | truncated).any(dim=0))
         if self.full_obs:
             obs = self.core.full_obs(actions, obs12=obs, num_steps=K)
             if self.core.obs_full is None:
@@ -165,6 +187,48 @@ class VectorAviary:
     def state_vectors(self) -> torch.Tensor:
         """(E, D, 20) `_getDroneStateVector`-ordered states (needs `track_rpm=True` for the RPM columns)."""
         return self.core.state_vectors().view(self.NUM_ENVS, self.NUM_DRONES, 20)
+
+    # ---- domain randomisation: the plant of every drone (include/gpd.h GPD_SCALE_*; SimCore.set_plant) ------------------------
+    def set_physical_params(self, mask=None, **scales):
+        """Scale the plant of every drone (or of the aviaries in the bool/uint8 `mask` [E]) relative to the nominal airframe:
+        fields of `_native.SCALE_FIELDS` (mass, ixx, iyy, izz, kf, km, drag_xy, drag_z, gnd_eff), each a scalar, an [E] or an [E, D]
+        tensor of finite factors > 0; fields left out keep their values.  The plant changes; what the agent and the controller know
+        does not: the action mapping (HOVER_RPM, the MAX_RPM clip), DSLPID's model and gains, SPEED_LIMIT, the geometry and the task
+        stay nominal -- a drone with mass 1.2 that receives action 0 sinks.  All factors 1.0 is the nominal airframe bit for bit."""
+        self.core.set_plant(scales, mask=mask)
+
+    def physical_params(self) -> torch.Tensor:
+        """(E, D, 9) scale factors of every drone's plant, in `_native.SCALE_FIELDS` order (privileged / asymmetric-critic inputs):
+        a VIEW of the table when there is one, else ones."""
+        v = self.core.plant_view()
+        if v is None:
+            return torch.ones((self.NUM_ENVS, self.NUM_DRONES, len(_native.SCALE_FIELDS)), dtype=torch.float32, device=self.device)
+        return v.permute(1, 2, 0)
+
+    @staticmethod
+    def _check_randomize(randomize):
+        if not randomize:
+            return {}
+        out = {}
+        for k, r in dict(randomize).items():
+            if k not in _native.SCALE_FIELDS:
+                raise ValueError(f"randomize: unknown field {k!r} (fields: {', '.join(_native.SCALE_FIELDS)})")
+            r = float(r)
+            if not (math.isfinite(r) and 0.0 <= r < 1.0):
+                raise ValueError(f"randomize: the range of {k} must satisfy 0 <= r < 1, got {r}")
+            out[k] = r
+        return out
+
+    def _resample(self, mask):
+        """New scales U(1 - r, 1 + r) for the randomised fields of the aviaries in `mask` (None: all): one torch.rand and one
+        gpd_plant_derive, no host sync."""
+        E, D = self.NUM_ENVS, self.NUM_DRONES
+        cur = self.core.plant_view()
+        full = cur.clone() if cur is not None else torch.ones((len(_native.SCALE_FIELDS), E, D), dtype=torch.float32, device=self.device)
+        u = torch.rand((len(self.randomize), E, D), generator=self._rng, device=self.device)
+        for i, (k, r) in enumerate(self.randomize.items()):
+            full[_native.SCALE_FIELDS.index(k)] = 1.0 + r * (2.0 * u[i] - 1.0)
+        self.core._apply_plant(full, mask)
 
     # ---- checkpoint / resume; non-finite guard (SURVEY.md section 5: both absent upstream) ----------------------
     def get_state(self) -> dict:

@@ -304,6 +304,69 @@ int gpd_rollout_history(const GpdParams* params, const GpdState* state, const Gp
                         int64_t env_step_stride, void* stream);
 
 /*
+ * Domain randomisation: a plant of its own for every drone.  GpdParams is one airframe for the whole launch; the plant path gives
+ * each drone NINE SCALE FACTORS relative to that nominal airframe, [GPD_NUM_SCALES][ld] floats (drone n at scales + s*ld + n):
+ */
+enum {
+    GPD_SCALE_MASS = 0,    /* M                          */
+    GPD_SCALE_IXX = 1,     /* J[0]                       */
+    GPD_SCALE_IYY = 2,     /* J[1]                       */
+    GPD_SCALE_IZZ = 3,     /* J[2]                       */
+    GPD_SCALE_KF = 4,      /* KF                         */
+    GPD_SCALE_KM = 5,      /* KM                         */
+    GPD_SCALE_DRAG_XY = 6, /* DRAG_COEFF[0], DRAG_COEFF[1] */
+    GPD_SCALE_DRAG_Z = 7,  /* DRAG_COEFF[2]              */
+    GPD_SCALE_GND_EFF = 8, /* GND_EFF_COEFF              */
+    GPD_NUM_SCALES = 9
+};
+/*
+ * Everything derived from them follows (GRAVITY = G*M, inv_M, J_INV, KM/KF, the hover-thrust terms).  THE PLANT CHANGES, WHAT THE
+ * AGENT AND THE CONTROLLER KNOW DOES NOT: HOVER_RPM of the action mapping, the MAX_RPM clip, DSLPID's model and gains (pid_*), the
+ * speed limit, arm length and rotor positions, the downwash coefficients, gnd_eff_h_clip and ground_z stay those of GpdParams.  A
+ * drone with mass 1.2 that receives action 0 sinks.  Scales are finite and > 0; a drone whose scales are all 1.0 flies the nominal
+ * airframe bit for bit.
+ *
+ * The DERIVED PLANT ROWS are what the kernels read: [GPD_PLANT_ROWS][ld] floats, the state's SoA convention (drone n at
+ * rows + r*ld + n, indexed like GpdState.kin), 16-byte aligned.  Row r replaces, in the plant, the GpdParams field named: */
+enum {
+    GPD_PLANT_M = 0,            /* M                 (Bullet damping)                 M_n * s_mass                        */
+    GPD_PLANT_INV_M = 1,        /* inv_M                                              inv_M_n / s_mass                    */
+    GPD_PLANT_KF = 2,           /* KF                (raw-RPM and DSLPID thrust)      KF_n * s_kf                         */
+    GPD_PLANT_GRAVITY = 3,      /* GRAVITY                                            GRAVITY_n * s_mass                  */
+    GPD_PLANT_J = 4,            /* J[0..2]           rows 4, 5, 6                     J_n[k] * s_ixx / s_iyy / s_izz      */
+    GPD_PLANT_J_INV = 7,        /* J_INV[0..2]       rows 7, 8, 9                     J_INV_n[k] / s_ixx / s_iyy / s_izz  */
+    GPD_PLANT_KM_OVER_KF = 10,  /* km_over_kf                                         km_over_kf_n * s_km / s_kf          */
+    GPD_PLANT_GND_EFF = 11,     /* gnd_eff_coeff                                      gnd_eff_coeff_n * s_gnd_eff         */
+    GPD_PLANT_DRAG = 12,        /* drag_coeff[0..2]  rows 12, 13, 14                  drag_n[k] * s_drag_xy / s_drag_z    */
+    GPD_PLANT_HOVER_THRUST = 15,/* hover_thrust      F_h = GRAVITY/4 of the drone     hover_thrust_n * s_mass             */
+    GPD_PLANT_HOVER_RESID = 16, /* hover_resid       KF*float(HOVER_RPM_n)^2 - F_h    hover_resid_n*s_kf + (s_kf - s_mass)*hover_thrust_n */
+    GPD_PLANT_NORM_THRUST = 17, /* (new) T = KF*HOVER_RPM_n^2: thrust of the normalised action 0   hover_thrust_n * s_kf      */
+    GPD_PLANT_NORM_GAP = 18,    /* (new) F_h - T: what the normalised action types' deviation subtracts   (s_mass - s_kf)*hover_thrust_n */
+    GPD_PLANT_ROWS = 19         /* 76 bytes per drone */
+};
+/*
+ * (The rows are derived from the nominal struct's fp32 fields in float64 and rounded once, so that a row of 1.0 scales reproduces
+ * them exactly: every formula above is the nominal field times or over 1.0, plus 0.)
+ *
+ * gpd_plant_derive: rows <- derive(nominal, scales) for the drones of the aviaries whose env_mask byte is non-zero (env_mask == NULL:
+ * all num_envs * drones_per_env drones; drone n belongs to aviary n / drones_per_env, as in gpd_reset).  Rows of other drones are
+ * left untouched.  No check of the scales' values on the device (the caller validates them once).
+ *
+ * gpd_rollout_plant: gpd_rollout with the plant rows (pitch state.ld, like the state) -- one entry for step() (num_steps = 1: the
+ * single-step kernel, as gpd_rollout routes a one-step rollout) and rollout().  Every other argument as in gpd_rollout; the action
+ * ring of `state` is ignored (gpd_full_obs pushes after the call).  Served by generic kernels of their own (gpd_step_plant_kernel, gpd_rollout1_plant_kernel,
+ * gpd_rollout_plant_kernel) for every shape gpd_rollout serves, except state.dw_force (one aviary of more than 256 drones,
+ * gpd_downwash_global): GPD_ENOTSUP.
+ * Both entries validate before any device work: NULL pointers, ld < num_envs * drones_per_env, rows not 16-byte aligned.
+ */
+int gpd_plant_derive(const GpdParams* nominal, const float* scales, const uint8_t* env_mask, int32_t num_envs,
+                     int32_t drones_per_env, int64_t ld, float* rows, void* stream);
+int gpd_rollout_plant(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, int32_t num_steps,
+                      const float* actions, int64_t action_step_stride, const float* target_pos, const float* init_pose,
+                      float* obs12, int64_t obs_step_stride, float* reward, uint8_t* terminated, uint8_t* truncated,
+                      int64_t env_step_stride, float* term_obs12, const float* plant_rows, void* stream);
+
+/*
  * A deterministic MLP policy evaluated INSIDE the rollout kernel: the actor of Stable-Baselines3's default `MlpPolicy`
  * (features -> Linear(in_dim, 64) -> tanh -> Linear(64, 64) -> tanh -> Linear(64, act_dim), `model.predict(obs,
  * deterministic=True)` incl. its clip to the action space [-1, 1]) -- what examples/learn.py:157-192 evaluates between two
