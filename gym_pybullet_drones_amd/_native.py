@@ -151,6 +151,9 @@ _SIGNATURES = {
     "gpd_swarm_pack": (ctypes.c_int, [ctypes.POINTER(GpdState), ctypes.POINTER(GpdSwarm), _P, _P, _P]),
     "gpd_swarm_bin": (ctypes.c_int, [ctypes.POINTER(GpdSwarm), _P]),
     "gpd_swarm_forces": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdSwarm), ctypes.c_int32, _P]),
+    "gpd_neighbors": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _P]),
     "gpd_reset": (ctypes.c_int, [ctypes.POINTER(GpdState), _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32,
                                  ctypes.c_int32, _P, _P]),
     "gpd_pid": (ctypes.c_int, [ctypes.POINTER(GpdParams), _P, ctypes.c_int64, ctypes.c_float, _P, _P, _P, _P, _P, _P,

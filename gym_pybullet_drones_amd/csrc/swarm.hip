@@ -1,5 +1,7 @@
 // swarm.hip -- ONE aviary of any size: binning, the downwash force kernel with its wake lists, the one-world step
 #include "gpd_common.inc"
+#include <algorithm>
+#include <cmath>
 
 namespace {
 
@@ -887,6 +889,201 @@ __global__ __launch_bounds__(kBlock) void gpd_swarm_pack_kernel(const GpdState S
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Neighbour queries (gpd_neighbors; envs/BaseAviary.py:658-675 `_getAdjacencyMatrix`, generalised to the K nearest): who is within
+// `radius` of a drone, how many, and the nearest K of them in the order (squared distance, row).  The K best of a lane live in
+// registers as 64-bit keys -- the bits of the squared distance (a non-negative float orders like its bit pattern) above the row --
+// so that "nearer, ties to the lower row" is ONE unsigned comparison and the list is the same whatever order the candidates
+// arrive in (the counting sort leaves the drones of a cell in the order its atomics decide).  Every index into the key array is a
+// compile-time constant (K is a template parameter: 4, 8, 16, 32; a request is rounded up and the first k are stored).
+// ------------------------------------------------------------------------------------------------
+constexpr unsigned long long kNbNone = ~0ull;              // (no key of a real pair: its distance bits are below 0x7f800000)
+struct NbOut {
+    int* count;            // [query_count]
+    int* idx;              // [query_count][k] or NULL
+    float4* rel;           // [query_count][k] or NULL
+    uint8_t* adj;          // [query_count / D][D][D] or NULL
+    int qf, qc, k;         // rows query_first .. query_first + query_count - 1 are answered
+};
+// sorted insertion, straight-line: slot i takes its upper neighbour's key when the new one goes in front of that, the new key
+// when it goes in front of its own only
+template <int K>
+__device__ __forceinline__ void nb_insert(unsigned long long (&best)[K], unsigned long long key) {
+#pragma unroll
+    for (int i = K - 1; i > 0; --i) best[i] = key < best[i - 1] ? best[i - 1] : (key < best[i] ? key : best[i]);
+    best[0] = key < best[0] ? key : best[0];
+}
+__device__ __forceinline__ float nb_dist2(const float4& c, const float4& me) {
+    const float dx = c.x - me.x, dy = c.y - me.y, dz = c.z - me.z;
+    return (dx * dx + dy * dy) + dz * dz;                  // (NaN for a padding candidate or a drone without a position: fails every test)
+}
+// the answer of query q (relative to query_first): `pos` is the array the keys' row numbers index
+template <int K>
+__device__ __forceinline__ void nb_store(const NbOut& O, int q, int cnt, const unsigned long long (&best)[K], const float4& me,
+                                         const float4* __restrict__ pos) {
+    O.count[q] = cnt;
+    if (!O.idx && !O.rel) return;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        if (i < O.k) {
+            const bool has = best[i] != kNbNone;
+            const int row = has ? static_cast<int>(static_cast<uint32_t>(best[i])) : -1;
+            const size_t at = static_cast<size_t>(q) * O.k + i;
+            if (O.idx) O.idx[at] = row;
+            if (O.rel) {
+                float4 r = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(0x7f800000));
+                if (has) {
+                    const float4 p = pos[row];
+                    r = make_float4(p.x - me.x, p.y - me.y, p.z - me.z, sqrtf(__uint_as_float(static_cast<uint32_t>(best[i] >> 32))));
+                }
+                O.rel[at] = r;
+            }
+        }
+    }
+}
+
+// ONE world: a wave per 64 CONSECUTIVE slots of the array the counting sort left (lane = query drone, so the lanes of a wave share
+// one or a few cells of one grid row), and its candidates are the three grid rows around it from one cell left of its first
+// to one cell right of its last cell -- at most six contiguous stretches of the sorted array (dwg_force_kernel's runs), staged 64 at
+// a time in LDS with the row number in w.  Per tile: (A) every lane tests all 64 candidates -- a broadcast LDS read, three
+// subtractions, three multiply-adds, one compare, one bit -- and counts its bits; (B) the lanes pop their bits, one per round, and
+// insert: the rounds of a tile are the LARGEST number of hits of any lane, not the number of candidates some lane hits.  The grid
+// is periodic and the search wider than a lane's own 3 x 3 cells, which is harmless: every drone occupies one slot, the stretches
+// of a segment never overlap (whole rows once nx columns are covered), and a pair counts by its exact distance only.
+template <int K>
+__global__ __launch_bounds__(64) void nbr_world_kernel(const float4* __restrict__ pos4, const int* __restrict__ order,
+                                                       const float4* __restrict__ sorted, const int* __restrict__ start,
+                                                       const int n_rows, const int nx, const int ny, const float r2, const NbOut O,
+                                                       int* __restrict__ cursor) {
+    __shared__ float4 tile[64];
+    const int keys = nx * ny;
+    // the sort's per-key counters / cursors are done with: leave them zeroed for the next call (no memset node per call)
+    for (int c = blockIdx.x * 64 + threadIdx.x; c < 2 * (keys + 1); c += gridDim.x * 64) cursor[c] = 0;
+    const int lane = threadIdx.x;
+    const int base = 64 * blockIdx.x, s = base + lane;
+    const int sorted_n = min(start[keys], n_rows);         // rows with a finite position (the others sit behind them in `order`)
+    const bool exists = s < n_rows;
+    int my_row = order[min(s, n_rows - 1)];
+    GPD_DBG(my_row >= 0 && my_row < n_rows, GPD_DBG_SLOT_ROW, my_row); my_row = GPD_DBG_CLAMP(my_row, 0, n_rows - 1);
+    const bool own = exists && my_row >= O.qf && my_row < O.qf + O.qc;
+    if (__builtin_amdgcn_ballot_w64(own) == 0) return;     // (a rank of a shared world answers for its slab only)
+    const float nan = __int_as_float(0x7fc00000);
+    unsigned long long best[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) best[i] = kNbNone;
+    int cnt = 0;
+    float4 me = make_float4(nan, nan, nan, 0.0f);
+    if (base < sorted_n) {
+        const bool have = own && s < sorted_n;             // a query with a position
+        const float4 me_l = sorted[min(s, sorted_n - 1)];
+        int key_l = __float_as_int(me_l.w);
+        GPD_DBG(key_l >= 0 && key_l < keys, GPD_DBG_SORT_KEY, key_l); key_l = GPD_DBG_CLAMP(key_l, 0, keys - 1);
+        if (have) me = me_l;
+        const int my_cell = have ? key_l : -1;
+        const int c_first = __builtin_amdgcn_readlane(key_l, 0);
+        const int c_last = __builtin_amdgcn_readlane(key_l, __builtin_amdgcn_readfirstlane(min(63, sorted_n - 1 - base)));
+        for (int cs = c_first; cs <= c_last;) {            // row segments of the wave's cells (nearly always one)
+            const int cy = cs / nx;
+            const int ce = min(c_last, cy * nx + nx - 1);
+            const int cxa = cs - cy * nx, w = ce - cs + 3; // columns cxa - 1 .. cxb + 1, periodic
+            const bool active = have && my_cell >= cs && my_cell <= ce;
+            int run0[6], pre[7];
+            pre[0] = 0;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                int gy = cy + r - 1;                       // (ny >= 3: three different rows, one period at most)
+                gy = gy < 0 ? gy + ny : gy >= ny ? gy - ny : gy;
+                const int row = gy * nx;
+                int a0, a1, b1c;                           // run A: cells a0 .. a1; run B (the wrapped part): cells 0 .. b1c, or empty
+                if (w >= nx) { a0 = 0; a1 = nx - 1; b1c = -1; }
+                else {
+                    const int a = cxa > 0 ? cxa - 1 : nx - 1;
+                    a0 = a; a1 = min(a + w - 1, nx - 1);
+                    b1c = a + w - 1 - nx;                  // (< 0: no wrap)
+                }
+                run0[2 * r] = start[row + a0];
+                pre[2 * r + 1] = pre[2 * r] + (start[row + a1 + 1] - run0[2 * r]);
+                run0[2 * r + 1] = start[row];
+                pre[2 * r + 2] = pre[2 * r + 1] + (b1c >= 0 ? start[row + b1c + 1] - run0[2 * r + 1] : 0);
+            }
+            const int total = pre[6];
+            for (int v0 = 0; v0 < total; v0 += 64) {
+                const int v = v0 + lane;
+                float4 c = make_float4(nan, nan, nan, __int_as_float(-1));     // (padding of the last tile)
+                if (v < total) {
+                    int src = run0[0] + v;                 // position in the concatenated stretches -> sorted slot
+#pragma unroll
+                    for (int q = 1; q < 6; ++q) src = (v >= pre[q]) ? run0[q] + (v - pre[q]) : src;
+                    GPD_DBG(src >= 0 && src < sorted_n, GPD_DBG_SORT_KEY, src); src = GPD_DBG_CLAMP(src, 0, sorted_n - 1);
+                    const float4 p = sorted[src];
+                    c = make_float4(p.x, p.y, p.z, __int_as_float(order[src]));
+                }
+                __syncthreads();                           // (the previous tile has been read)
+                tile[lane] = c;
+                __syncthreads();
+                unsigned long long mask = 0ull;
+#pragma unroll 8
+                for (int j = 0; j < 64; ++j) {
+                    const float4 o = tile[j];
+                    const bool hit = nb_dist2(o, me) < r2 && __float_as_int(o.w) != my_row;
+                    mask |= static_cast<unsigned long long>(hit) << j;
+                }
+                if (!active) mask = 0ull;
+                cnt += __builtin_popcountll(mask);
+                while (__builtin_amdgcn_ballot_w64(mask != 0ull) != 0) {
+                    if (mask != 0ull) {
+                        const int j = __builtin_ctzll(mask);
+                        mask &= mask - 1ull;
+                        const float4 o = tile[j];
+                        const unsigned long long key = (static_cast<unsigned long long>(__float_as_uint(nb_dist2(o, me))) << 32) |
+                                                       static_cast<uint32_t>(__float_as_int(o.w));
+                        if (key < best[K - 1]) nb_insert<K>(best, key);
+                    }
+                }
+            }
+            cs = ce + 1;
+        }
+    }
+    if (own) nb_store<K>(O, my_row - O.qf, cnt, best, me, pos4);
+}
+
+// E independent aviaries of D consecutive rows (2 .. 256), neighbours inside the aviary only: no sort.  A workgroup holds
+// floor(256 / D) aviaries, their positions staged in LDS; a lane = a drone walks its own aviary's D entries (the lanes of an
+// aviary read the same address: a broadcast).  Row numbers in the keys and in nbr_idx are the drone's index INSIDE its aviary.
+template <int K>
+__global__ __launch_bounds__(kBlock) void nbr_env_kernel(const float4* __restrict__ pos4, const int D, const int G, const int E,
+                                                         const float r2, const NbOut O) {
+    __shared__ float4 sh[kBlock];
+    const int t = threadIdx.x;
+    const int g = t / D, d = t - g * D;
+    const int e = blockIdx.x * G + g;                      // aviary, counted from the first one asked for
+    const bool on = g < G && e < E;
+    const float nan = __int_as_float(0x7fc00000);
+    const float4* const mine = pos4 + O.qf + static_cast<size_t>(on ? e : 0) * D;
+    const float4 me = on ? mine[d] : make_float4(nan, nan, nan, 0.0f);
+    sh[t] = me;
+    __syncthreads();
+    if (!on) return;
+    const float4* const mates = sh + g * D;
+    unsigned long long best[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) best[i] = kNbNone;
+    int cnt = 0;
+    uint8_t* const adj = O.adj ? O.adj + (static_cast<size_t>(e) * D + d) * D : nullptr;
+    for (int j = 0; j < D; ++j) {
+        const float d2 = nb_dist2(mates[j], me);
+        const bool hit = d2 < r2 && j != d;
+        if (adj) adj[j] = (hit || j == d) ? 1 : 0;         // (the reference's matrix: np.identity + the pairs, :668-674)
+        if (hit) {
+            ++cnt;
+            const unsigned long long key = (static_cast<unsigned long long>(__float_as_uint(d2)) << 32) | static_cast<uint32_t>(j);
+            if (key < best[K - 1]) nb_insert<K>(best, key);
+        }
+    }
+    nb_store<K>(O, e * D + d, cnt, best, me, mine);
+}
+
 }  // namespace
 
 GPD_DBG_READER(gpd_detail_dbg_read_swarm)
@@ -1065,6 +1262,79 @@ int gpd_swarm_forces(const GpdParams* params, const GpdSwarm* w, int32_t build_l
 #undef GPD_FORCE_ARGS
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "gpd_swarm_forces launch");
+    return 0;
+}
+
+int gpd_neighbors(const float* pos4, int32_t n_rows, int32_t query_first, int32_t query_count, float radius, int32_t k,
+                  int32_t drones_per_env, float cell, float x0, float y0, float x1, float y1, const int32_t* visit_order,
+                  int32_t* cell_count, int32_t* cell_start, int32_t* order, float* sorted_xyzc, int32_t* nbr_count,
+                  int32_t* nbr_idx, float* nbr_rel, uint8_t* adjacency, void* stream) {
+    auto bad = [&](int code, const char* msg) { return fail(code, (std::string("gpd_neighbors: ") + msg).c_str()); };
+    if (!pos4 || !nbr_count) return bad(GPD_EINVAL, "NULL pos4 / nbr_count");
+    if (n_rows <= 0) return bad(GPD_EINVAL, "need n_rows > 0");
+    if (k < 1 || k > 32) return bad(GPD_ERANGE, "need 1 <= k <= 32");
+    if (!(radius > 0.0f) || !std::isfinite(radius)) return bad(GPD_EINVAL, "radius must be positive and finite");
+    if (query_first < 0 || query_count <= 0 || static_cast<int64_t>(query_first) + query_count > n_rows)
+        return bad(GPD_ERANGE, "the query range must lie inside the rows (0 <= query_first, 0 < query_count, query_first + query_count <= n_rows)");
+    if ((reinterpret_cast<uintptr_t>(pos4) & 15u) != 0) return bad(GPD_EINVAL, "pos4 must be 16-byte aligned (rows are read as float4)");
+    if (nbr_rel && (reinterpret_cast<uintptr_t>(nbr_rel) & 15u) != 0) return bad(GPD_EINVAL, "nbr_rel must be 16-byte aligned (entries are written as float4)");
+    const int D = drones_per_env;
+    if (D != 0 && (D < 2 || D > kBlock)) return bad(GPD_EINVAL, "drones_per_env must be 0 (one world) or 2 .. 256");
+    if (adjacency && D == 0) return bad(GPD_EINVAL, "adjacency needs drones_per_env >= 2 (one world has no dense matrix)");
+    const double rr = static_cast<double>(radius) * static_cast<double>(radius);
+    // (float64 product, rounded once; a radius whose square is beyond a float -- "everybody", the reference's default np.inf handed in
+    // as the largest finite float -- compares against the largest finite float)
+    const float r2 = rr > 3.4028234663852886e38 ? 3.4028234663852886e38f : static_cast<float>(rr);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const NbOut O{nbr_count, nbr_idx, reinterpret_cast<float4*>(nbr_rel), adjacency, query_first, query_count, k};
+    const float4* const p4 = reinterpret_cast<const float4*>(pos4);
+#define GPD_NB_K(LAUNCH) do { if (k <= 4) { LAUNCH(4); } else if (k <= 8) { LAUNCH(8); } else if (k <= 16) { LAUNCH(16); } else { LAUNCH(32); } } while (0)
+    if (D != 0) {
+        if (n_rows % D != 0 || query_first % D != 0 || query_count % D != 0)
+            return bad(GPD_EINVAL, "with drones_per_env = D the rows and the query range are whole aviaries (multiples of D)");
+        const int G = kBlock / D, E = query_count / D;
+        const dim3 grid(static_cast<unsigned>((E + G - 1) / G));
+#define GPD_NB_ENV(KK) hipLaunchKernelGGL(nbr_env_kernel<KK>, grid, dim3(kBlock), 0, st, p4, D, G, E, r2, O)
+        GPD_NB_K(GPD_NB_ENV);
+#undef GPD_NB_ENV
+    } else {
+        if (!cell_count || !cell_start || !order || !sorted_xyzc) return bad(GPD_EINVAL, "one world needs the sort's scratch: cell_count, cell_start, order, sorted_xyzc");
+        if (visit_order == order) return bad(GPD_EINVAL, "visit_order must not alias order (ping-pong two buffers)");
+        if ((reinterpret_cast<uintptr_t>(sorted_xyzc) & 15u) != 0) return bad(GPD_EINVAL, "sorted_xyzc must be 16-byte aligned");
+        if (!std::isfinite(x0) || !std::isfinite(y0) || !std::isfinite(x1) || !std::isfinite(y1) || x1 < x0 || y1 < y0)
+            return bad(GPD_EINVAL, "the box x0 <= x1, y0 <= y1 the grid is laid over must be finite");
+        if (!(cell >= 0.0f) || !std::isfinite(cell)) return bad(GPD_EINVAL, "cell must be 0 (the smallest that is exact) or a finite size in metres");
+        // cell >= radius + 1/64: two drones closer than `radius` then sit at most one cell apart whatever fp32 rounding does to
+        // their cell coordinates (an error of 2^-23 of the coordinate each: 1/128 cell at 65 536 cells from the corner)
+        double c = std::max(static_cast<double>(cell), static_cast<double>(radius) * (65.0 / 64.0));
+        auto cells_of = [](double extent, double c_) { const double m = std::ceil(extent / c_); return m < 3.0 ? 3 : m > 70000.0 ? 70000 : static_cast<int>(m); };
+        const double ex = static_cast<double>(x1) - x0, ey = static_cast<double>(y1) - y0;
+        int nx = cells_of(ex, c), ny = cells_of(ey, c);
+        while (static_cast<int64_t>(nx) * ny > 65536) { c *= 2.0; nx = cells_of(ex, c); ny = cells_of(ey, c); }     // coarser: less selective, still exact
+        const int keys = nx * ny;
+        const DwGrid G{static_cast<float>(1.0 / c), x0, y0, nx, ny, 0.0f, 0.0f, 1};
+        const dim3 grid(static_cast<unsigned>((n_rows + kBlock - 1) / kBlock));
+        const DwPos src{nullptr, 0, p4};
+        hipLaunchKernelGGL(dwg_count_kernel<false>, grid, dim3(kBlock), 0, st, src, n_rows, G, visit_order, cell_count, GpdState{}, nullptr, nullptr);
+        int32_t* const cursors = cell_count + keys + 1;
+        const DwBinOut B{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0.0f, 0};     // (own_cnt = 0: no force array)
+        float4* const srt = reinterpret_cast<float4*>(sorted_xyzc);
+        if (keys <= kDwScanMax) {
+            hipLaunchKernelGGL(dwg_scatter_kernel<true>, grid, dim3(kBlock), 0, st, src, n_rows, G, visit_order, cell_count, cursors,
+                               cell_start, order, srt, static_cast<float*>(nullptr), B);
+        } else {
+            hipLaunchKernelGGL(dwg_scan_kernel, dim3(1), dim3(1024), 0, st, cell_count, cell_start, keys);
+            hipLaunchKernelGGL(dwg_scatter_kernel<false>, grid, dim3(kBlock), 0, st, src, n_rows, G, visit_order, cell_count, cursors,
+                               cell_start, order, srt, static_cast<float*>(nullptr), B);
+        }
+        const dim3 sgrid(static_cast<unsigned>((n_rows + 63) / 64));
+#define GPD_NB_WORLD(KK) hipLaunchKernelGGL(nbr_world_kernel<KK>, sgrid, dim3(64), 0, st, p4, order, srt, cell_start, n_rows, nx, ny, r2, O, cell_count)
+        GPD_NB_K(GPD_NB_WORLD);
+#undef GPD_NB_WORLD
+    }
+#undef GPD_NB_K
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "gpd_neighbors launch");
     return 0;
 }
 

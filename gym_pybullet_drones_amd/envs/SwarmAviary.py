@@ -24,14 +24,15 @@ large-world counterpart, built on the `GpdSwarm` entries of t
 Interface: `CtrlAviary`-like.  `step(action)` takes raw RPMs `(n_own, 4)` clipped to `[0, MAX_RPM]`
 (`envs/CtrlAviary.py:140`) — or, with `act=ActionType.PID`, waypoints `(n_own, 3)` tracked by `DSLPIDControl`s
 (`examples/downwash.py:93-113`) — and returns the `(n_own, 20)` state vectors of this rank's drones.  Everything stays on the
-GPU.
+GPU.  `neighbors(radius, k)` / `collisions()` tell a drone who is near it (`gpd_neighbors`: the same counting sort on
+`radius`-sized cells, then a k-nearest search; the reference's `_getAdjacencyMatrix`, `envs/BaseAviary.py:658-675`, at swarm size).
 """
 import ctypes
 
 import numpy as np
 import torch
 
-from .. import _native, engine
+from .. import _native, engine, neighbors as _nb
 from ..control.DSLPIDControl import DSLPIDControlBatch
 from ..params import DroneParams
 from ..utils.enums import ACT_DIRECT_RPM, ACT_RAW_RPM, ActionType, DroneModel, PHYS_DW, Physics, warn_if_pyb
@@ -476,6 +477,13 @@ class SwarmAviary:
         self.step_counter = 0
         self._since_bin = 0                          # sub-steps since the last binning
         self._dw_version = -1                        # core.state_version the forces in dw_force were computed for
+        # neighbour queries (neighbors() / collisions()): which state this rank's rows of pos4 hold, and which state the other
+        # ranks' rows were last exchanged for
+        self._pos_version = self._xchg_version = -1
+        self._halo = bool(getattr(exchange, "halo", False))
+        self.COLLISION_R = P.COLLISION_R
+        self._searches = {}                          # (radius, k, rel) -> the scratch and outputs of that query
+        self._row_ids = None                         # row of pos4 -> the caller's drone index (shared worlds)
 
     # ---- the pieces of a sub-step (LocalSwarmGroup drives several ranks of one process through them) --------------------
     def _pack(self, vectors=None):
@@ -484,6 +492,7 @@ class SwarmAviary:
         with torch.cuda.device(self.device):
             rc = c.lib.gpd_swarm_pack(ctypes.byref(c._state), ctypes.byref(self._sw), _ptr(c.obs12), _ptr(vectors), c._stream())
         _native.check(rc, "gpd_swarm_pack")
+        self._pos_version = c.state_version
         self._since_bin = self.rebin_every           # (forces a binning)
         if getattr(self.exchange, "halo", False):    # ... and a new halo plan that holds nothing against the jump
             self.exchange.plan.forget()
@@ -509,6 +518,7 @@ class SwarmAviary:
             rc = c.lib.gpd_swarm_step(r[0], r[1], r[2], r[3], _ptr(rpm), r[4], _ptr(vectors), c._stream())
         if rc:
             _native.check(rc, "gpd_swarm_step")
+        self._pos_version = c.state_version          # (the kernel wrote the rank's new rows of pos4)
         self._since_bin += 1
 
     def _exchange(self):
@@ -517,6 +527,7 @@ class SwarmAviary:
                 self.exchange.exchange(self, replan=self._since_bin >= self.rebin_every)
             else:                                           # every position to every rank
                 self.exchange(self.pos4, self.RANK, self.slab)
+                self._xchg_version = self.core.state_version
 
     def all_positions(self) -> torch.Tensor:
         """(TOTAL_DRONES, 3) positions of the WHOLE world in the caller's drone order, on every rank -- a collective through
@@ -619,12 +630,66 @@ class SwarmAviary:
     def invalidate(self):
         """Tell the aviary that the state was changed without going through `reset()` / `core.set_state()` (e.g. by writing
         through the plane views `core.kin_P / kin_Q / kin_V / kin_W`, `core.positions()` ...; `core.kin` itself is a copy and rejects
-        writes): the next step re-packs, re-bins and recomputes the downwash forces first."""
+        writes): the next step re-packs, re-bins and recomputes the downwash forces first (and so does the next neighbour query)."""
         self._dw_version = -1
+        self._pos_version = self._xchg_version = -1
 
     def state_vectors(self) -> torch.Tensor:
         """(n, 20) `_getDroneStateVector` rows (envs/BaseAviary.py:559-561)."""
         return self.core.state_vectors()
+
+    # ---- neighbour queries (include/gpd.h gpd_neighbors; the reference: BaseAviary._getAdjacencyMatrix, envs/BaseAviary.py:658-675) --
+    def _check_neighbor_query(self, radius, k):
+        """argument errors of neighbors() / collisions(), before any device work"""
+        if self._halo:
+            raise ValueError("neighbour queries need every position on every rank: a halo-exchanging world holds only its neighbours' "
+                             "border drones (use exchange='allgather' / a slab exchange)")
+        return _nb.check_args(radius, k)
+
+    def _current_pos4(self):
+        """pos4 for the CURRENT state: re-packed when the state changed behind it (reset() without downwash, set_state(),
+        invalidate()), exchanged when the other ranks' rows are older than this rank's (a shared world stepped without downwash)"""
+        c = self.core
+        if self._pos_version != c.state_version:
+            self._pack()
+        if self.WORLD_SIZE > 1 and self._xchg_version != c.state_version:
+            self._exchange()
+        return self.pos4
+
+    def neighbors(self, radius: float, k: int = 8, rel: bool = True) -> "_nb.Neighbors":
+        """For each of this rank's drones: how many other drones of the WORLD are closer than `radius` (`count`, however many),
+        and the nearest `k` of them, nearest first (`idx` in the caller's drone numbering, -1 where there are fewer; `rel`:
+        (xj - xi, yj - yi, zj - zi, distance); `mask = idx >= 0`).  Ties in distance go to the lower ROW of the packed position
+        array (the order the drones were dealt in: the caller's own order on one rank).  Device tensors, no host
+        synchronisation; the tensors of one (radius, k, rel) are reused by the next call with the same arguments.  Collective
+        in a shared world only when the positions have to be exchanged first (see `_current_pos4`)."""
+        radius, k = self._check_neighbor_query(radius, k)
+        pos4 = self._current_pos4()
+        key = (radius, k, bool(rel))
+        q = self._searches.get(key)
+        if q is None:
+            box = (self.x0, self.y0, self.x0 + self.nx * self.cell, self.y0 + self.ny * self.cell)      # the downwash grid's box
+            q = self._searches[key] = _nb.WorldSearch(self.device, self.n_rows, self.RANK * self.slab, self.NUM_DRONES, radius, k,
+                                                      box, rel=bool(rel))
+        out = q(pos4, self.core._stream())
+        if self.WORLD_SIZE == 1:
+            return out                               # (rows are the caller's drones)
+        if self._row_ids is None:
+            ids = np.full(self.n_rows, -1, dtype=np.int64)
+            _, _, counts = swarm_partition(self.TOTAL_DRONES, self.WORLD_SIZE)
+            for r, cnt in enumerate(counts):
+                first = swarm_first_drone(self.TOTAL_DRONES, self.WORLD_SIZE, r)
+                ids[r * self.slab:r * self.slab + cnt] = self._deal_order[first:first + cnt]
+            self._row_ids = torch.as_tensor(ids, dtype=torch.int32, device=self.device)
+        idx = torch.where(out.idx >= 0, self._row_ids[out.idx.clamp_min(0).long()], out.idx)
+        return _nb.Neighbors(idx, out.count, out.rel)
+
+    def collisions(self, min_dist: float = None) -> torch.Tensor:
+        """(n,) bool: this rank's drones whose nearest other drone is closer than `min_dist` (default: two collision radii of the
+        airframe, `2 * COLLISION_R` -- the cylinders of the URDF touch)."""
+        if min_dist is None:
+            min_dist = 2.0 * self.COLLISION_R
+        return self.neighbors(min_dist, k=1, rel=False).count > 0
 
     # ---- checkpoint / resume (SURVEY.md section 5: absent upstream) ----------------------------------------------------------
     def get_state(self) -> dict:
@@ -685,6 +750,8 @@ class LocalSwarmGroup:
         dev = self.ranks[0].device
         self._ids = [torch.as_tensor(e.GLOBAL_IDS, dtype=torch.long, device=dev) for e in self.ranks]
         self._all_ids = torch.cat(self._ids)
+        for e in self.ranks:
+            e._halo = exchange == "halo"
 
     @staticmethod
     def _noop(pos4, rank, slab):
@@ -693,6 +760,8 @@ class LocalSwarmGroup:
     def _exchange(self):
         if self.plans is not None:
             return self._exchange_halo()
+        for e in self.ranks:
+            e._xchg_version = e.core.state_version
         for src in self.ranks:
             sl = slice(src.RANK * src.slab, (src.RANK + 1) * src.slab)
             for dst in self.ranks:
@@ -767,3 +836,14 @@ class LocalSwarmGroup:
 
     def forces(self):
         return self._global(torch.cat([e.dw_force[:e.NUM_DRONES] for e in self.ranks]))
+
+    def neighbors(self, radius: float, k: int = 8, rel: bool = True) -> list:
+        """`SwarmAviary.neighbors` of every rank (a list, rank by rank: each answers for its own drones, `idx` in the caller's
+        numbering), after re-packing and exchanging the positions if some rank's are stale."""
+        for e in self.ranks:
+            e._check_neighbor_query(radius, k)
+        if any(e._pos_version != e.core.state_version or e._xchg_version != e.core.state_version for e in self.ranks):
+            for e in self.ranks:
+                e._pack()
+            self._exchange()
+        return [e.neighbors(radius, k, rel) for e in self.ranks]

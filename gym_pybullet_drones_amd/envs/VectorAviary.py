@@ -17,7 +17,7 @@ import math
 import numpy as np
 import torch
 
-from .. import _native, engine
+from .. import _native, engine, neighbors as _nb
 from ..params import DroneParams
 from ..utils.enums import ACT_RAW_RPM, ActionType, DroneModel, ObservationType, Physics
 
@@ -48,6 +48,7 @@ class VectorAviary:
                  pyb_like: bool = None,
                  nan_guard: bool = False,
                  randomize: dict = None,
+                 neighbourhood_radius: float = np.inf,
                  device=None):
         """`randomize`: domain randomisation of the plant, {field: r} with a field of `_native.SCALE_FIELDS` (mass, ixx, iyy, izz,
         kf, km, drag_xy, drag_z, gnd_eff) and 0 <= r < 1 -- every drone's scale of that field is drawn from U(1 - r, 1 + r) at
@@ -57,6 +58,7 @@ class VectorAviary:
             raise NotImplementedError("only ObservationType.KIN is on the MI355X hot path")
         self.randomize = self._check_randomize(randomize)      # (before any device work)
         self.NUM_ENVS, self.NUM_DRONES = int(num_envs), int(num_drones)
+        self.NEIGHBOURHOOD_RADIUS = neighbourhood_radius         # (envs/BaseAviary.py:124; used by neighbors() / adjacency())
         self.DRONE_MODEL, self.PHYSICS = drone_model, physics
         self.PYB_FREQ, self.CTRL_FREQ = pyb_freq, ctrl_freq
         self.PYB_STEPS_PER_CTRL = pyb_freq // ctrl_freq
@@ -187,6 +189,28 @@ class VectorAviary:
     def state_vectors(self) -> torch.Tensor:
         """(E, D, 20) `_getDroneStateVector`-ordered states (needs `track_rpm=True` for the RPM columns)."""
         return self.core.state_vectors().view(self.NUM_ENVS, self.NUM_DRONES, 20)
+
+    # ---- neighbour queries inside every aviary (include/gpd.h gpd_neighbors; envs/BaseAviary.py:658-675) ------------------------
+    def _neighbor_query(self, radius, k, rel, want_adjacency):
+        if self.NUM_DRONES < 2:
+            raise ValueError("neighbour queries need aviaries of at least two drones (num_drones = 1 has nobody to see)")
+        radius, k = _nb.check_args(self.NEIGHBOURHOOD_RADIUS if radius is None else radius, k)
+        c = self.core
+        return _nb.aviary_query(c.kin_P, self.NUM_ENVS, self.NUM_DRONES, radius, k, c._stream(), rel=rel, want_adjacency=want_adjacency)
+
+    def neighbors(self, radius: float = None, k: int = None, rel: bool = True) -> "_nb.Neighbors":
+        """For every drone the other drones OF ITS AVIARY closer than `radius` (None: `NEIGHBOURHOOD_RADIUS`): `count` (E, D),
+        the nearest `k` (default: min(D - 1, 8)) as `idx` (E, D, k) -- the drone's index inside its aviary, nearest first, ties
+        to the lower index, -1 where there are fewer -- and `rel` (E, D, k, 4): relative position and distance.  One launch, no
+        host synchronisation."""
+        if k is None:
+            k = max(1, min(self.NUM_DRONES - 1, 8))
+        return self._neighbor_query(radius, k, rel, False)[0]
+
+    def adjacency(self, radius: float = None) -> torch.Tensor:
+        """(E, D, D) uint8: `BaseAviary._getAdjacencyMatrix()` (envs/BaseAviary.py:658-675) of every aviary -- 1 on the diagonal
+        and where two drones are closer than `radius` (None: `NEIGHBOURHOOD_RADIUS`)."""
+        return self._neighbor_query(radius, 1, False, True)[1]
 
     # ---- domain randomisation: the plant of every drone (include/gpd.h GPD_SCALE_*; SimCore.set_plant) ------------------------
     def set_physical_params(self, mask=None, **scales):

@@ -599,6 +599,48 @@ int gpd_swarm_bin(const GpdSwarm* swarm, void* stream);
 int gpd_swarm_forces(const GpdParams* params, const GpdSwarm* swarm, int32_t build_lists, void* stream);
 
 /*
+ * Neighbour queries: for every row of a query range, how many OTHER drones are closer than `radius`, and the nearest k of them.
+ * Replaces BaseAviary._getAdjacencyMatrix (envs/BaseAviary.py:658-675: an O(N^2) Python loop over every pair of ONE aviary on
+ * the host) for the batched aviaries, and gives the one-world swarm -- where a dense matrix is out of the question -- the
+ * k-nearest lists a decentralised policy or a flocking rule observes, and a collision test (radius = two collision radii, k = 1).
+ *
+ *   pos4            [n_rows][4] floats x, y, z, (ignored), 16-byte aligned: GpdSwarm.pos4, or plane P of GpdState.kin.  A row
+ *                   whose position is not finite takes no part, neither as query nor as neighbour (GpdSwarm's rows without a
+ *                   drone and its meta rows are such rows)
+ *   query_first, query_count   the rows that are answered (a rank of a shared world asks for its own slab); all rows can be neighbours
+ *   radius          > 0, finite.  Neighbour: 3-D Euclidean distance STRICTLY below it (:673) -- squared distances
+ *                   (dx*dx + dy*dy) + dz*dz in fp32 against radius^2 computed in float64 and rounded once
+ *   k               1 .. 32 entries per query
+ *   drones_per_env  0: ONE world.  The rows are sorted by the cell of a periodic x-y grid laid over the box x0 <= x <= x1,
+ *                   y0 <= y <= y1 (the counting sort of gpd_downwash_global) and a query searches the 3 x 3 cells around its
+ *                   own.  Cell size: max(cell, radius * 65/64) -- `cell` = 0 asks for the smallest -- doubled until nx * ny <= 65536;
+ *                   nx, ny >= 3.  Drones outside the box wrap around (still exact: every pair is distance-tested, and the 1/64
+ *                   covers the fp32 rounding of the cell coordinates up to 65 536 cells from the corner).  The cell size, the
+ *                   box and visit_order change the speed, never the result.
+ *                   D = 2 .. 256: n_rows / D independent aviaries of D consecutive rows, neighbours inside the aviary only; no
+ *                   grid, no scratch (cell .. sorted_xyzc ignored); n_rows, query_first and query_count are multiples of D.
+ *   visit_order, cell_count, cell_start, order, sorted_xyzc   (one world) the sort's scratch as for gpd_downwash_global, no
+ *                   allocation inside the library: visit_order [n_rows] or NULL; cell_count [2 * 65537] int32, ZERO before the
+ *                   first call and left zeroed by every call; cell_start [65537] int32; order [n_rows] int32 (out: the sorted
+ *                   order, a permutation of the rows -- next call's visit_order, ping-pong); sorted_xyzc [n_rows][4] float
+ *   nbr_count       [query_count] int32 out: neighbours of the row, however many (may exceed k) = the row sum of the
+ *                   reference's matrix minus its diagonal 1
+ *   nbr_idx         [query_count][k] int32 out or NULL: the min(k, count) nearest, ordered by (squared distance, row) ascending --
+ *                   ties go to the lower row, whatever order the sort left the candidates in; the rest -1.  One world: row
+ *                   numbers of pos4; drones_per_env = D: the drone's index inside its aviary
+ *   nbr_rel         [query_count][k][4] float out or NULL (16-byte aligned): (xj - xi, yj - yi, zj - zi, distance) of those
+ *                   entries; padding (0, 0, 0, +inf)
+ *   adjacency       [query_count / D][D][D] uint8 out or NULL, drones_per_env = D only: the reference's matrix, diagonal 1
+ * Everything is validated before the first device call: GPD_EINVAL (NULL pos4 / nbr_count / scratch, radius, alignment,
+ * drones_per_env, adjacency with one world, box, cell), GPD_ERANGE (k, the query range).  Asynchronous on `stream`; three or
+ * four launches for one world (count, [scan,] scatter, search), one for aviaries.
+ */
+int gpd_neighbors(const float* pos4, int32_t n_rows, int32_t query_first, int32_t query_count, float radius, int32_t k,
+                  int32_t drones_per_env, float cell, float x0, float y0, float x1, float y1, const int32_t* visit_order,
+                  int32_t* cell_count, int32_t* cell_start, int32_t* order, float* sorted_xyzc, int32_t* nbr_count,
+                  int32_t* nbr_idx, float* nbr_rel, uint8_t* adjacency, void* stream);
+
+/*
  * Masked reset.  Replaces BaseAviary.reset/_housekeeping (envs/BaseAviary.py:220-255, 451-477)
  * for the envs whose mask byte is non-zero (mask == NULL: all).  Sets pos/quat to init_pose,
  * vel, rpy_rates, last_rpm and step_counter to zero and writes the initial obs12 rows.  As in
