@@ -18,20 +18,21 @@ if not os.path.exists(os.path.join(INCLUDE, "gpd.h")):            # ... or the c
 LIB_PATH = os.path.join(CSRC, "libgpd.so")
 ABI_VERSION = 9
 
-# Four translation units over csrc/gpd_common.inc (the shared physics), one library:
+# Five translation units over csrc/gpd_common.inc (the shared physics), one library:
 #   step_rollout.hip  gpd_step / gpd_rollout*            -mllvm -amdgpu-sched-strategy=max-ilp: interleaves independent dependency chains, which
 #                     fills the one-wait-state hazard behind every packed-fp32 result with useful work instead of s_nops (13 of 287 issue
 #                     slots of a rollout step)
 #   policy.hip        gpd_rollout_policy                 the default scheduler: 10 % faster on its MFMA + activation mix (round-2 A/B)
 #   swarm.hip         the one-world kernels              max-ilp, as in rounds 2-4
 #   abi.hip           small kernels, RCCL, library-level entries
+#   mrac.hip          gpd_mrac / gpd_mrac_reset / gpd_rollout_mrac: the adaptive controller and the rollout that carries it (max-ilp)
 #   -mllvm -amdgpu-kernarg-preload-count=14: the first 14 argument dwords of a kernel arrive in SGPRs with the wave (gfx942+ command
 #   processor) instead of through a scalar load -- gpd_step_kernel's argument list starts with what its load section needs
 COMMON_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC"]
 MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 HIPCC_FLAGS = COMMON_FLAGS + MAX_ILP + ["-shared"]        # (kept under this name for the ISA tests)
-UNITS = (("step_rollout.hip", MAX_ILP + KERNARG_PRELOAD), ("policy.hip", []), ("swarm.hip", MAX_ILP + KERNARG_PRELOAD), ("abi.hip", MAX_ILP))
+UNITS = (("step_rollout.hip", MAX_ILP + KERNARG_PRELOAD), ("policy.hip", []), ("swarm.hip", MAX_ILP + KERNARG_PRELOAD), ("abi.hip", MAX_ILP), ("mrac.hip", MAX_ILP))
 HEADERS = ("gpd_common.inc", "policy_kernel.inc", "step_kernel_body.inc", "rollout_kernel_body.inc", "rollout1_kernel_body.inc")
 
 
@@ -77,11 +78,24 @@ class GpdSwarm(ctypes.Structure):
                 ("drift", ctypes.c_void_p), ("total_drones", ctypes.c_int32), ("list_adapt", ctypes.c_int32)]
 
 
+class GpdMrac(ctypes.Structure):
+    """mirror of `struct GpdMrac` (the MRAC design as fp32 constants, control/MRAC.py)"""
+    _fields_ = [("PB", ctypes.c_float * 48), ("Kr_ref_gain", ctypes.c_float * 48), ("Am_lo", ctypes.c_float * 48),
+                ("A_grav", ctypes.c_float * 4), ("B_diag", ctypes.c_float * 4), ("mixer", ctypes.c_float * 12),
+                ("gamma_x", ctypes.c_float), ("gamma_r", ctypes.c_float), ("inv_4kf", ctypes.c_float), ("max_torque", ctypes.c_float),
+                ("pwm2rpm_scale", ctypes.c_float), ("inv_pwm2rpm_scale", ctypes.c_float), ("pwm2rpm_const", ctypes.c_float),
+                ("min_pwm", ctypes.c_float), ("max_pwm", ctypes.c_float), ("pad_", ctypes.c_float * 3),
+                ("Kx0", ctypes.c_float * 48), ("Kr0", ctypes.c_float * 16)]
+
+
+#: floats of MRAC state per controller (GPD_MRAC_STATE): Kx [12][4] | Kr [4][4] | Xm [12]
+MRAC_STATE = 76
+
 DEBUG_LIB_PATH = os.path.join(CSRC, "libgpd_debug.so")
 
 
 def build(force: bool = False, verbose: bool = False, debug: bool = False) -> str:
-    """Compile the four units of csrc/ -> csrc/libgpd.so for gfx950 (side by side).  Returns the library path.
+    """Compile the five units of csrc/ -> csrc/libgpd.so for gfx950 (side by side).  Returns the library path.
     `debug=True`: the debug-bounds build (-DGPD_DEBUG_BOUNDS, include/gpd.h `gpd_debug_status`) -> csrc/libgpd_debug.so; use it by
     setting GPD_LIB to that path before the package is imported."""
     srcs = [os.path.join(CSRC, u) for u, _ in UNITS]
@@ -160,6 +174,13 @@ _SIGNATURES = {
                                _P, _P, _P, _P, ctypes.c_int32, _P]),
     "gpd_pid_sync": (ctypes.c_int, [ctypes.POINTER(GpdParams), _P, ctypes.c_int64, ctypes.c_float, _P, _P, _P, _P, _P, _P,
                                     _P, _P, _P, _P, ctypes.c_int32, _P]),
+    "gpd_sizeof_mrac": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int32)]),
+    "gpd_mrac": (ctypes.c_int, [ctypes.POINTER(GpdMrac), _P, _P, ctypes.c_int64, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                ctypes.c_int32, _P]),
+    "gpd_mrac_reset": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.POINTER(GpdMrac), _P, ctypes.c_int32, ctypes.c_int32, _P]),
+    "gpd_rollout_mrac": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdMrac), ctypes.POINTER(GpdState),
+                                        ctypes.POINTER(GpdStepCfg), _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64,
+                                        ctypes.c_int32, _P]),
     "gpd_state_vectors": (ctypes.c_int, [ctypes.POINTER(GpdState), _P, _P, ctypes.c_int32, _P]),
     "gpd_comm_unique_id": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8)]),
     "gpd_comm_init": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32,
@@ -217,6 +238,9 @@ def lib() -> ctypes.CDLL:
         raise GpdError(f"struct layout mismatch: library {tuple(sizes)} vs binding {want}")
     if L.gpd_sizeof_swarm() != ctypes.sizeof(GpdSwarm):
         raise GpdError(f"struct layout mismatch: GpdSwarm is {L.gpd_sizeof_swarm()} bytes in the library, {ctypes.sizeof(GpdSwarm)} in the binding")
+    mrac_size = ctypes.c_int32(0)
+    if L.gpd_sizeof_mrac(ctypes.byref(mrac_size)) != 0 or mrac_size.value != ctypes.sizeof(GpdMrac):
+        raise GpdError(f"struct layout mismatch: GpdMrac is {mrac_size.value} bytes in the library, {ctypes.sizeof(GpdMrac)} in the binding")
     _lib = L
     return L
 

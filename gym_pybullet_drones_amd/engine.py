@@ -257,6 +257,12 @@ class SimCore:
             rc = self.lib.gpd_reset(ctypes.byref(self._state), _ptr(self.init_pose), self.init_per_env, _ptr(mask),
                                     self.E, self.D, int(reset_pid), _ptr(self.obs12), self._stream())
         _native.check(rc, "gpd_reset")
+        if self.mrac_rpm is not None:     # (an MRAC rollout of a reset aviary starts from zero RPMs, as the reference's loop does)
+            with torch.cuda.stream(self._pinned) if self._pinned is not None else contextlib.nullcontext():
+                if mask is None:
+                    self.mrac_rpm.zero_()
+                else:
+                    self.mrac_rpm.view(self.E, self.D * 4).masked_fill_(mask.to(torch.bool).unsqueeze(1), 0.0)
         if self.host_visible:
             self.drain()
         if self.bad is not None:          # (the non-finite flags describe the state the last launch left: a reset pose is finite)
@@ -476,6 +482,55 @@ class SimCore:
         self.terminated.copy_(term[K - 1])
         self.truncated.copy_(trunc[K - 1])
         return obs, rew, term, trunc, acts
+
+    #: [N, 4] the RPMs an MRAC rollout carries from one launch to the next (None until the first `rollout_mrac`)
+    mrac_rpm = None
+
+    def rollout_mrac(self, ctrl, targets, num_steps: int, last_only: bool = False):
+        """K control steps in ONE launch with the adaptive controller IN the loop (`gpd_rollout_mrac`; the loop of the reference's
+        `examples/mrac.py:82-90`): step k is one env step with the carried RPMs as the action (zeros after a reset, as the
+        example starts), then one call of `ctrl` (a `control.VectorMRAC` with one controller per drone) on the new state.
+
+        `targets`: `[N, 12]` (target pos | rpy | vel | rpy rates, held for all K steps) or `[K, N, 12]`; rows of 3 floats are
+        positions (the rest zero, the reference's defaults).  Aviaries of one drone, no task, RPM actions (`VectorCtrlAviary`).
+        A plant table (`set_plant`) is honoured: the airframes differ, the controller's design stays nominal.  Returns
+        `obs12 [K, N, 12]` (a persistent buffer) or, with `last_only`, the latest rows `[N, 12]`.  Bitwise identical to K x
+        (`step(rpm)`, `rpm = ctrl.compute(...)`), and K1 then K2 steps to K1 + K2 in one launch."""
+        K = int(num_steps)
+        if K < 1:
+            raise ValueError("num_steps must be >= 1")
+        if self.host_visible:
+            raise ValueError("rollout_mrac: a host-visible core steps one aviary at a time (CtrlAviary.step + MRAC.computeControl)")
+        if getattr(self, "act_ring", None) is not None:
+            raise ValueError("rollout_mrac: this core keeps an action history, which the fused rollout would not advance "
+                             "(step() + VectorMRAC.compute() serve it)")
+        if getattr(ctrl, "n", None) != self.N or ctrl.device != self.device or getattr(ctrl, "host_visible", False):
+            raise ValueError(f"rollout_mrac needs a VectorMRAC of {self.N} controllers on {self.device}")
+        t = torch.as_tensor(targets, dtype=torch.float32, device=self.device)
+        if t.shape[-1] == 3:
+            t = torch.cat([t, torch.zeros(t.shape[:-1] + (9,), dtype=torch.float32, device=self.device)], dim=-1)
+        if tuple(t.shape) == (self.N, 12):
+            t_stride = 0
+        elif tuple(t.shape) == (K, self.N, 12):
+            t_stride = self.N * 12
+        else:
+            raise ValueError(f"targets must be [{self.N}, 12] or [{K}, {self.N}, 12] (or rows of 3: positions), got {tuple(t.shape)}")
+        t = t.contiguous()
+        if self.mrac_rpm is None:
+            self.mrac_rpm = torch.zeros((self.N, 4), dtype=torch.float32, device=self.device)
+        if last_only:
+            obs, o_stride = self.obs12, 0
+        else:
+            obs, o_stride = self._rollout_buffers(K)[0], self.N * 12
+        self.state_version += 1
+        with torch.cuda.device(self.device):
+            rc = self.lib.gpd_rollout_mrac(ctypes.byref(self._params), ctypes.byref(ctrl.struct()), ctypes.byref(self._state),
+                                           ctypes.byref(self._cfg), _ptr(ctrl.state), _ptr(ctrl.counter), ctrl.ld, _ptr(t), t_stride,
+                                           _ptr(self.mrac_rpm), _ptr(self.plant_rows), _ptr(obs), o_stride, K, self._stream())
+        _native.check(rc, "gpd_rollout_mrac")
+        if not last_only:
+            self.obs12.copy_(obs[K - 1])
+        return obs
 
     def _latest_terminal(self, tobs, term, trunc, K):
         """`term_obs12` after a K-step launch = what K single steps would have left: for every aviary the terminal observation
@@ -704,7 +759,7 @@ class SimCore:
     #: episode clocks, the latest observation rows and task outputs (a policy rollout starts from `obs12`), and -- with an action
     #: history -- the ring with its positions (the reference's never-reset `action_buffer`, envs/BaseRLAviary.py:65-67)
     _STATE_FIELDS = ("kin", "last_rpm", "pid", "step_counter", "obs12", "reward", "terminated", "truncated", "term_obs12",
-                     "act_ring", "ring_pos", "bad", "plant_scales")
+                     "act_ring", "ring_pos", "bad", "plant_scales", "mrac_rpm")
 
     def get_state(self) -> dict:
         """Snapshot (device clones) of the complete simulator state: `set_state(**get_state())` later -- on this core or on
@@ -731,6 +786,8 @@ class SimCore:
             if tuple(scales.shape) != (len(_native.SCALE_FIELDS), n):
                 raise ValueError(f"set_state: plant_scales has shape {tuple(scales.shape)}, expected ({len(_native.SCALE_FIELDS)}, {n})")
             self.set_plant(scales.view(-1, self.E, self.D))
+        if given.get("mrac_rpm") is not None and self.mrac_rpm is None:      # (allocated by the first rollout_mrac)
+            self.mrac_rpm = torch.zeros((self.N, 4), dtype=torch.float32, device=self.device)
         for name, v in given.items():
             t = getattr(self, name, None)
             if v is None or t is None:       # (a snapshot of a core with more optional parts than this one: the rest applies)

@@ -186,6 +186,15 @@ class VectorAviary:
         E, D = self.NUM_ENVS, self.NUM_DRONES
         return obs.view(-1, E, D, 12), reward, terminated, truncated, acts.view(-1, E, D, self.ACT_DIM)
 
+    def rollout_mrac(self, ctrl, targets, num_steps: int, last_only: bool = False):
+        """K control steps in ONE launch with the adaptive controller in the loop (`SimCore.rollout_mrac`; the loop of the
+        reference's `examples/mrac.py:82-90`).  `ctrl`: a `control.VectorMRAC` with one controller per drone; `targets`: (E, 12) /
+        (K, E, 12) rows target pos | rpy | vel | rpy rates (rows of 3: positions).  Single-drone aviaries without a task
+        (`VectorCtrlAviary`); a plant table (`randomize=` / `set_physical_params`) is honoured.  Returns obs (K, E, 1, 12), or
+        (E, 1, 12) with `last_only`."""
+        obs = self.core.rollout_mrac(ctrl, targets, num_steps, last_only=last_only)
+        return obs.view(-1, self.NUM_ENVS, self.NUM_DRONES, 12) if not last_only else obs.view(self.NUM_ENVS, self.NUM_DRONES, 12)
+
     def state_vectors(self) -> torch.Tensor:
         """(E, D, 20) `_getDroneStateVector`-ordered states (needs `track_rpm=True` for the RPM columns)."""
         return self.core.state_vectors().view(self.NUM_ENVS, self.NUM_DRONES, 20)

@@ -676,6 +676,99 @@ int gpd_pid_sync(const GpdParams* params, float* pid, int64_t ld, float ctrl_dt,
                  int32_t n, void* stream);
 
 /*
+ * MRAC: the reference's model-reference adaptive controller (control/MRAC.py:12-155, flown by examples/mrac.py), batched, and fused
+ * into the rollout.  State x = (pos, rpy, vel, body rates) of 12 floats, input u = (thrust, three torques).  The DESIGN
+ * (control/MRAC.py:56-104 -- pole placement, the Lyapunov equation) is the host's business, in float64; the device receives its
+ * products as fp32 constants, rounded once.  A HOST struct like GpdParams, passed by value in the kernel argument segment; the
+ * kernels keep it in LDS.  All matrices row-major.
+ */
+typedef struct GpdMrac {
+    float PB[48];           /* [12][4]  P Bm: the reference's  e^T P Bm  (:133-134) is  e^T PB */
+    float Kr_ref_gain[48];  /* [4][12]  pinv(B) (A - B K):  rt = -Kr_ref_gain r         (:93, :128) */
+    /* The reference model Am = A - B K, Bm = B (:95-96) in the form their structure allows (:69-85): B is zero above its last four
+     * rows, so rows 0..7 of Am are those of A -- rows 0..5 are [0 I] (d/dt of pos, rpy = vel, body rates: nothing to store), rows 6, 7
+     * hold gravity's four entries -- and only rows 8..11 are dense.  Evaluating the full 12 x 12 product adds exact zeros. */
+    float Am_lo[48];        /* [4][12]  rows 8..11 of Am */
+    float A_grav[4];        /* Am[6][3], Am[6][4], Am[7][3], Am[7][4] = g sin(psi), g cos(psi), -g cos(psi), g sin(psi) */
+    float B_diag[4];        /* Bm[8+k][k] = 1/m, 1/Ixx, 1/Iyy, 1/Izz */
+    float mixer[12];        /* [4][3]                                                   (:37-50) */
+    float gamma_x, gamma_r; /* Gamma_x = gamma_x I, Gamma_r = gamma_r I                 (:99-100) */
+    float inv_4kf;          /* 1/(4 KF), host-computed in float64                       (:144) */
+    float max_torque;       /* 3200                                                     (:142) */
+    float pwm2rpm_scale, inv_pwm2rpm_scale, pwm2rpm_const, min_pwm;                     /* (:30-33) */
+    float max_pwm, pad_[3];
+    /* read by gpd_mrac_reset only */
+    float Kx0[48];          /* [12][4]  initial gains Kx = -K^T                         (:102) */
+    float Kr0[16];          /* [4][4]   Kr = I                                          (:103) */
+} GpdMrac;
+
+/* Floats of controller state per controller: [GPD_MRAC_STATE][ld], controller n at mrac_state + r*ld + n (the state's SoA convention):
+ * rows 0..47 Kx [12][4] row-major | rows 48..63 Kr [4][4] | rows 64..75 Xm. */
+#define GPD_MRAC_STATE 76
+
+/* sizeof(GpdMrac) -> *size_out, for a binding to verify its mirror.  (gpd_sizeof_swarm RETURNS its size; this one writes it and
+ * returns 0, or GPD_EINVAL for NULL: like every entry with a pointer argument it answers NULL with a code.) */
+int gpd_sizeof_mrac(int32_t* size_out);
+
+/*
+ * Batched MRAC.computeControl (control/MRAC.py:109-155) for n independent controllers, shaped like gpd_pid: one lane per
+ * controller, asynchronous on `stream`, capturable.  In the reference's order: rpy of cur_quat; body rates = the intrinsic-XYZ
+ * rotation of rpy, inverted, applied to cur_ang_vel (:121, restated as the reference computes it); Xm <- X where counter == 0,
+ * counter += 1; rt = -Kr_ref_gain r; u = Kx^T X + Kr^T rt with the gains BEFORE this call's update; the adaptation
+ * Kx += -gamma_x X (e^T PB) dt, Kr += -gamma_r rt (e^T PB) dt with e = X - Xm; thrust / torque clips, mixer and PWM clip;
+ * Xm += (Am Xm + Bm rt) dt.
+ *   mrac         HOST pointer, like GpdParams
+ *   mrac_state   [GPD_MRAC_STATE][ld], updated in place;  counter [n] int32, updated in place
+ *   cur_pos, cur_vel, cur_ang_vel [n][3], cur_quat [n][4] (16-byte aligned), target_pos [n][3]
+ *   target_rpy, target_vel, target_rpy_rates   [n][3] or NULL (= zeros, the reference's defaults)
+ *   rpm [n][4] out (16-byte aligned); pos_e [n][3], rpy_e [n][3] out or NULL (rpy_e: three angles, :150)
+ * Validated before any device work.  GPD_EINVAL: a NULL pointer other than the optional ones, n <= 0 or ld < n, ctrl_dt <= 0,
+ * cur_quat or rpm not 16-byte aligned.  GPD_ERANGE: n > 2^26 (32-bit byte offsets).
+ */
+int gpd_mrac(const GpdMrac* mrac, float* mrac_state, int32_t* counter, int64_t ld, float ctrl_dt,
+             const float* cur_pos, const float* cur_quat, const float* cur_vel, const float* cur_ang_vel,
+             const float* target_pos, const float* target_rpy, const float* target_vel, const float* target_rpy_rates,
+             float* rpm, float* pos_e, float* rpy_e, int32_t n, void* stream);
+
+/*
+ * MRAC.reset (control/MRAC.py:106-107 -> BaseControl.reset) for the controllers whose mask byte is non-zero (mask == NULL: all):
+ * the counter goes to zero and NOTHING else -- the next call re-seeds Xm from the state it sees, the adapted gains survive.
+ * restore_gains != 0 (an extra the reference does not have) also puts Kx0 / Kr0 of `mrac` back (a second launch).
+ * GPD_EINVAL: NULL mrac_state / counter, NULL mrac with restore_gains, n <= 0 or ld < n.  GPD_ERANGE: n > 2^26.
+ */
+int gpd_mrac_reset(float* mrac_state, int32_t* counter, int64_t ld, const GpdMrac* mrac, const uint8_t* mask, int32_t n,
+                   int32_t restore_gains, void* stream);
+
+/*
+ * K control steps in ONE launch with the MRAC controller IN the loop: the loop of examples/mrac.py:82-90
+ * (`obs, ... = env.step(action); action = ctrl.computeControlFromState(state=obs[0], ...)`).  A drone's state and its 76
+ * controller floats are loaded once, stay in registers for all K steps and their sub-steps, and are stored once.  Step k: one env
+ * step with the carried RPMs as the action (the first call of a fresh aviary: zeros, as the example starts), then one controller
+ * call on the new state gives the next RPMs.  Bit for bit K x (gpd_step + gpd_mrac); K1 then K2 steps = K1 + K2 in one launch.
+ *   cfg            drones_per_env = 1, task GPD_TASK_NONE, no auto-reset, act_type GPD_ACT_RAW_RPM or GPD_ACT_DIRECT_RPM, any
+ *                  sub-step count; GPD_PHYS_GND / DRAG / GROUND / DAMP allowed, GPD_PHYS_DW (or state.dw_force): GPD_ENOTSUP (it
+ *                  needs mates; gpd_step + gpd_mrac serve every shape)
+ *   mrac_state, counter, mrac_ld   as in gpd_mrac, one controller per drone
+ *   targets        step t reads [N][12] rows (target pos | rpy | vel | rpy rates) at targets + t*target_step_stride (floats);
+ *                  stride 0 holds one block for all K steps.  16-byte aligned
+ *   rpm_carry      [N][4] in/out, 16-byte aligned: the action of the first step in, the controller's latest output out
+ *   plant_rows     NULL, or the per-drone plant table of gpd_plant_derive (pitch state.ld): the airframe is the drone's own while
+ *                  `mrac` stays the nominal design
+ *   obs12          step t writes [N][12] at obs12 + t*obs_step_stride; stride 0 keeps only the last step's rows.  16-byte aligned
+ * Validated before any device work.
+ *   GPD_EINVAL   a NULL pointer (plant_rows excepted), state.kin not 16-byte aligned or state.ld outside 1 .. 2^32 - 1, num_envs /
+ *                substeps / num_steps <= 0, an unknown physics flag, state.ld or mrac_ld < num_envs, GPD_PHYS_DRAG without
+ *                state.last_rpm, a negative step stride, a non-zero one below 12*num_envs or not a multiple of 4 floats, targets /
+ *                rpm_carry / obs12 / plant_rows not 16-byte aligned, pyb_dt or ctrl_dt <= 0
+ *   GPD_ENOTSUP  drones_per_env != 1, a task or auto_reset, an act_type other than the two RPM ones, GPD_PHYS_DW or state.dw_force
+ *   GPD_ERANGE   num_envs > 2^26 (32-bit byte offsets)
+ */
+int gpd_rollout_mrac(const GpdParams* params, const GpdMrac* mrac, const GpdState* state, const GpdStepCfg* cfg,
+                     float* mrac_state, int32_t* counter, int64_t mrac_ld, const float* targets, int64_t target_step_stride,
+                     float* rpm_carry, const float* plant_rows, float* obs12, int64_t obs_step_stride, int32_t num_steps,
+                     void* stream);
+
+/*
  * Gather the 20-float state vectors of BaseAviary._getDroneStateVector
  * (envs/BaseAviary.py:541-561): pos3 | quat4 | rpy3 | vel3 | ang_v3 | last_clipped_action4,
  * from the SoA state and the obs12 rows of the latest step.  state20 is [n][20].
