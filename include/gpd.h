@@ -354,8 +354,8 @@ enum {
  *
  * gpd_rollout_plant: gpd_rollout with the plant rows (pitch state.ld, like the state) -- one entry for step() (num_steps = 1: the
  * single-step kernel, as gpd_rollout routes a one-step rollout) and rollout().  Every other argument as in gpd_rollout; the action
- * ring of `state` is ignored (gpd_full_obs pushes after the call).  Served by generic kernels of their own (gpd_step_plant_kernel, gpd_rollout1_plant_kernel,
- * gpd_rollout_plant_kernel) for every shape gpd_rollout serves, except state.dw_force (one aviary of more than 256 drones,
+ * ring of `state` is ignored (gpd_full_obs pushes after the call).  Served by generic kernels of their own (the PLANT = true
+ * instantiations of gpd_step_kernel, gpd_rollout1_kernel and gpd_rollout_kernel) for every shape gpd_rollout serves, except state.dw_force (one aviary of more than 256 drones,
  * gpd_downwash_global): GPD_ENOTSUP.
  * Both entries validate before any device work: NULL pointers, ld < num_envs * drones_per_env, rows not 16-byte aligned.
  */

@@ -135,8 +135,8 @@ def test_derive_reproduces_the_nominal_struct_and_the_float64_reference(gpu_devi
 
 # (action, physics flags, drones per aviary, sub-steps, K, keep_terminal_obs): every action type, flags {0, 7, 8, 24, 31}, D {1, 2, 3, 8, 100},
 # S {1, 8}, K {1, 20}, with and without terminal observations, auto-reset on and episodes short enough to end inside the horizon.  Between
-# them: gpd_step_plant_kernel (K = 1, single and multi), gpd_rollout1_plant_kernel (K > 1, single and multi), gpd_rollout_plant_kernel
-# (terminal observations, D > 64; single and multi)
+# them, the PLANT = true instantiations of gpd_step_kernel (K = 1, single and multi), gpd_rollout1_kernel (K > 1, single and multi) and
+# gpd_rollout_kernel (terminal observations, D > 64; single and multi)
 NOMINAL_SHAPES = [("rpm", 0, 1, 1, 20, False), ("rpm", 0, 1, 1, 1, False), ("pid", 7, 2, 8, 20, False), ("vel", 8, 3, 1, 1, True),
                   ("one_d_rpm", 24, 8, 8, 20, True), ("one_d_pid", 31, 100, 1, 20, False), ("raw_rpm", 31, 1, 8, 20, True),
                   ("direct_rpm", 7, 100, 1, 1, False), ("one_d_pid", 24, 1, 8, 1, False), ("vel", 0, 2, 1, 20, False)]

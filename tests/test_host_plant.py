@@ -116,19 +116,33 @@ def test_vector_aviary_rejects_bad_randomisation_ranges(bad):
 
 
 def test_compiled_unit_holds_the_plant_kernels_without_scratch():
-    """The three plant kernels exist under names of their own (the existing kernels' mangled prefixes match only themselves) and
-    need no scratch memory; the derive kernel too."""
-    from test_kernel_isa import _kernel, _unit_asm
+    """The PLANT = true instantiations of the three kernel templates exist, 20 of each, built from the generic entries only (ACT from the
+    argument block, the sub-step loop), and need no scratch memory; the derive kernel too.  No lookup the ISA tests make for a uniform
+    kernel matches one of them."""
+    from test_kernel_isa import UNIFORM_LOOKUPS, _kernel, _unit_asm
     lines = _unit_asm(0)
     labels = [m.group(1) for m in (re.match(r"^(_Z\w+):", l) for l in lines) if m]
-    for name in ("gpd_step_plant_kernel", "gpd_rollout1_plant_kernel", "gpd_rollout_plant_kernel", "gpd_plant_derive_kernel"):
-        found = [l for l in labels if name in l]
-        assert found, name
-        for sym in found:
-            _, meta = _kernel(lines, sym[2:])          # (the helper matches `_Z\w*` + a name)
-            assert re.search(r"ScratchSize: 0\b", meta), sym
-    # the plant kernels are built from the generic entries only: ACT from the argument block, the sub-step loop
-    plant = [l for l in labels if "_plant_kernelI" in l]
-    assert len(plant) == 60, len(plant)         # 10 <PID, EXT, AW> x {step, rollout1, rollout} x {single, multi}
-    for prefix in ("gpd_step_kernelI", "gpd_rollout1_kernelI", "gpd_rollout_kernelI"):
-        assert not [l for l in labels if prefix in l and "plant" in l]
+
+    def targs(sym, template):         # the template arguments of an instantiation of `template`, or None
+        m = re.search(r"\d+" + template + r"I((?:L[bi]n?\d+E)+)E", sym)
+        return [int(a.replace("n", "-")) for a in re.findall(r"L[bi](n?\d+)E", m.group(1))] if m else None
+
+    # template -> (number of parameters, index of ACT, index of S1); PLANT is the last parameter of each
+    templates = {"gpd_step_kernel": (10, 4, 5), "gpd_rollout1_kernel": (12, 3, 4), "gpd_rollout_kernel": (7, 4, 5)}
+    plant = []
+    for template, (count, act, s1) in templates.items():
+        found = [(l, targs(l, template)) for l in labels if targs(l, template)]
+        assert found and all(len(a) == count for _, a in found), template
+        mine = [(l, a) for l, a in found if a[-1] == 1]
+        assert len(mine) == 20, (template, len(mine))         # 10 <PID, EXT, AW> x {single, multi}
+        for sym, a in mine:
+            assert a[act] == -1 and a[s1] == 0, sym
+        plant += [l for l, _ in mine]
+    assert len(plant) == 60, len(plant)
+    derive = [l for l in labels if "gpd_plant_derive_kernel" in l]
+    assert derive
+    for sym in plant + derive:
+        _, meta = _kernel(lines, sym[2:])          # (the helper matches `_Z\w*` + a name)
+        assert re.search(r"ScratchSize: 0\b", meta), sym
+    for name in UNIFORM_LOOKUPS:
+        assert not [l for l in plant if re.match(r"^_Z\w*" + name + r"\w*$", l)], name

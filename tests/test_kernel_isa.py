@@ -15,7 +15,13 @@ import pytest
 
 from conftest import REPO
 
-HEADLINE = "gpd_rollout1_kernelILb0ELb0ELi4ELi0ELb1ELb0ELb0ELb0ELi0ELin1ELb0EE"  # <PID=0, EXT=0, AW=4, ACT=RPM, S1=1, MULTI=0, NT_OBS=0, RING=0, DC=0, FL=-1, HI=0>
+# Mangled names of gpd_rollout1_kernel<PID, EXT, AW, ACT, S1, MULTI, NT_OBS, RING, DC, FL, HI, PLANT>, each spelled out to its last argument
+# and the closing `E`: `_kernel()` matches `\w*` behind a name, and a name cut short could pick another instantiation (a PLANT = 1 one)
+HEADLINE = "gpd_rollout1_kernelILb0ELb0ELi4ELi0ELb1ELb0ELb0ELb0ELi0ELin1ELb0ELb0EE"  # <PID=0, EXT=0, AW=4, ACT=RPM, S1=1, MULTI=0, NT_OBS=0, RING=0, DC=0, FL=-1, HI=0, PLANT=0>
+ROLL1_MULTI_GENERIC = "gpd_rollout1_kernelILb0ELb1ELi4ELi0ELb0ELb1ELb1ELb0ELi0ELin1ELb0ELb0EE"   # EXT, RPM, MULTI: any aviary size, any flags
+ROLL1_PAIRS_DW = "gpd_rollout1_kernelILb0ELb1ELi4ELi0ELb1ELb1ELb1ELb0ELi2ELi4ELb0ELb0EE"         # ... S1, DC=2, FL=4
+ROLL1_EIGHT_ALL = "gpd_rollout1_kernelILb0ELb1ELi4ELi0ELb1ELb1ELb1ELb0ELi8ELi7ELb0ELb0EE"        # ... S1, DC=8, FL=7
+UNIFORM_LOOKUPS = (HEADLINE, ROLL1_MULTI_GENERIC, ROLL1_PAIRS_DW, ROLL1_EIGHT_ALL)
 
 
 POLICY = "gpd_rollout_policy_kernelILb0ELi4ELi0ELi5ELb0E"  # <PID=0, AW=4, ACT=RPM, NK1=5 (72-float rows), tanh>
@@ -298,11 +304,11 @@ def test_history_rows_are_streamed_out_in_16_byte_pieces(abi_asm):
 def test_two_drone_aviaries_exchange_through_dpp(gpd_asm):
     """MULTI rollout kernel, RPM, all force terms (BASELINE config 5's kernel): the mate's position (3 values) and its reward /
     distance / out-of-bounds terms (3) arrive by `quad_perm:[1,0,3,2]` moves -- in each of the three copies of the step."""
-    body, _ = _kernel(gpd_asm, "gpd_rollout1_kernelILb0ELb1ELi4ELi0ELb0ELb1ELb1ELb0ELi0ELin1ELb0E")      # any aviary size, any flags
+    body, _ = _kernel(gpd_asm, ROLL1_MULTI_GENERIC)      # any aviary size, any flags
     assert sum("quad_perm:[1,0,3,2]" in l for l in body) == 18
     # compiled for pairs, PYB_DW's flags, one sub-step per step (what BASELINE config 5 at 240 Hz runs): the same moves, and nothing of the other sizes
     # is left -- no LDS exchange of positions (the only LDS traffic is the observation patch: 3 writes + 3 reads per step copy)
-    body, meta = _kernel(gpd_asm, "gpd_rollout1_kernelILb0ELb1ELi4ELi0ELb1ELb1ELb1ELb0ELi2ELi4ELb0E")
+    body, meta = _kernel(gpd_asm, ROLL1_PAIRS_DW)
     assert sum("quad_perm:[1,0,3,2]" in l for l in body) == 18 and re.search(r"ScratchSize: 0\b", meta)
     assert sum(op.startswith("ds_") for op, _ in _ops(body)) == 18
 
@@ -311,7 +317,7 @@ def test_stacks_of_eight_run_their_exchange_straight_line(gpd_asm):
     """gpd_rollout1_kernel compiled for aviaries of eight (BASELINE config 3 ii, RPM, all force terms, one sub-step per step): in each
     of the three step copies the six 16-byte reads of the mates' positions stand in ONE run (issued together: the second group's LDS
     latency passes under the first group's arithmetic); no scratch."""
-    body, meta = _kernel(gpd_asm, "gpd_rollout1_kernelILb0ELb1ELi4ELi0ELb1ELb1ELb1ELb0ELi8ELi7ELb0E")
+    body, meta = _kernel(gpd_asm, ROLL1_EIGHT_ALL)
     assert re.search(r"ScratchSize: 0\b", meta)
     ops = [op for op, _ in _ops(body) if op.startswith("ds_") or op.startswith(("s_cbranch", "s_branch"))]
     runs, cur = [], 0
