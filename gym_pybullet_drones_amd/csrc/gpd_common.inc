@@ -1,4 +1,4 @@
-// gpd_common.inc — the MI355X (gfx950 / CDNA4) hot path of the vectorised quadrotor simulator: what its four translation units share.
+// gpd_common.inc — the MI355X (gfx950 / CDNA4) hot path of the vectorised quadrotor simulator: what its five translation units share.
 //
 // One wavefront lane per drone.  A lane loads its 13 kinematic floats from the structure-of-arrays
 // state (four planes: three of float4 and one of float => a wave's load of a plane is one coalesced 1 KiB /
@@ -64,8 +64,12 @@ namespace {
 #endif
 constexpr int kBlock = GPD_BLOCK;   // 256 = 4 wavefronts; one workgroup per CU fills all 4 SIMDs
 
+// A run-time value as a template argument: a launch path hands Const<value>{} to a generic lambda, which names the kernel with
+// decltype(arg)::value -- every kernel is launched from ONE place, and only the combinations some call site passes are instantiated.
+template <auto V> using Const = std::integral_constant<decltype(V), V>;
+
 }  // namespace
-// The library is built from FOUR translation units over this header -- step_rollout.hip, policy.hip, swarm.hip, abi.hip -- because
+// The library is built from FIVE translation units over this header -- step_rollout.hip, policy.hip, swarm.hip, abi.hip, mrac.hip -- because
 // the kernels want different instruction schedulers (-amdgpu-sched-strategy: max-ilp fills the packed-fp32 hazards of the physics; the
 // default strategy is 10 % faster on the MFMA / activation mix of the policy kernel, A/B in round 2) and because one 3 800-line unit
 // took three minutes to compile.  The last-error string is shared (defined in abi.hip).

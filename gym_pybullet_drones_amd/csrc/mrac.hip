@@ -407,13 +407,13 @@ int gpd_rollout_mrac(const GpdParams* params, const GpdMrac* mrac, const GpdStat
     const bool ext = (C.physics_flags & 31u) != 0;
     const dim3 grid(static_cast<unsigned>((N + kBlock - 1) / kBlock));
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define GPD_MRAC_LAUNCH(EXT_, PLANT_)                                                                                              \
-    hipLaunchKernelGGL((gpd_rollout_mrac_kernel<EXT_, PLANT_>), grid, dim3(kBlock), 0, st, *params, *mrac, state->kin, state->last_rpm, \
-                       state->step_counter, state->bad, static_cast<uint32_t>(state->ld), C, mrac_state, counter, mrac_ld, targets,  \
-                       target_step_stride, rpm_carry, plant_rows, obs12, obs_step_stride, num_steps)
-    if (plant_rows) { if (ext) GPD_MRAC_LAUNCH(true, true); else GPD_MRAC_LAUNCH(false, true); }
-    else { if (ext) GPD_MRAC_LAUNCH(true, false); else GPD_MRAC_LAUNCH(false, false); }
-#undef GPD_MRAC_LAUNCH
+    auto launch = [&](auto ext_, auto plant_) {
+        hipLaunchKernelGGL((gpd_rollout_mrac_kernel<decltype(ext_)::value, decltype(plant_)::value>), grid, dim3(kBlock), 0, st, *params, *mrac,
+                           state->kin, state->last_rpm, state->step_counter, state->bad, static_cast<uint32_t>(state->ld), C, mrac_state, counter,
+                           mrac_ld, targets, target_step_stride, rpm_carry, plant_rows, obs12, obs_step_stride, num_steps);
+    };
+    if (plant_rows) { if (ext) launch(Const<true>{}, Const<true>{}); else launch(Const<false>{}, Const<true>{}); }
+    else { if (ext) launch(Const<true>{}, Const<false>{}); else launch(Const<false>{}, Const<false>{}); }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "gpd_rollout_mrac launch");
     return 0;

@@ -3,27 +3,7 @@
 #include "policy_kernel.inc"
 
 #ifdef GPD_PID_POLICY_IN_POLICY_TU
-void gpd_detail_launch_policy_pid(const GpdPolicyLaunch& a) {
-    const Span& T = *static_cast<const Span*>(a.span);
-    const dim3 grid(a.grid);
-    hipStream_t st = static_cast<hipStream_t>(a.stream);
-#define GPD_POL(AW_, ACT_, NK1_)                                                                                                   \
-    do {                                                                                                                            \
-        if (a.policy->activation == 1)                                                                                              \
-            hipLaunchKernelGGL((gpd_rollout_policy_kernel<true, AW_, ACT_, NK1_, true>), grid, dim3(kBlock), 0, st, *a.params, *a.state, *a.cfg, T, \
-                               *a.policy, a.obs12_in, a.target_pos, a.init_pose, a.actions_out, a.obs12, a.reward, a.terminated, a.truncated, a.term_obs12); \
-        else                                                                                                                        \
-            hipLaunchKernelGGL((gpd_rollout_policy_kernel<true, AW_, ACT_, NK1_, false>), grid, dim3(kBlock), 0, st, *a.params, *a.state, *a.cfg, T, \
-                               *a.policy, a.obs12_in, a.target_pos, a.init_pose, a.actions_out, a.obs12, a.reward, a.terminated, a.truncated, a.term_obs12); \
-    } while (0)
-    switch (a.cfg->act_type) {
-        case GPD_ACT_VEL: if (a.hist) GPD_POL(4, GPD_ACT_VEL, 5); else GPD_POL(4, GPD_ACT_VEL, 1); break;
-        case GPD_ACT_PID: if (a.hist) GPD_POL(3, GPD_ACT_PID, 4); else GPD_POL(3, GPD_ACT_PID, 1); break;
-        default: if (a.hist) GPD_POL(1, GPD_ACT_ONE_D_PID, 2); else GPD_POL(1, GPD_ACT_ONE_D_PID, 1); break;
-    }
-#undef GPD_POL
-#undef GPD_POLN
-}
+void gpd_detail_launch_policy_pid(const GpdPolicyLaunch& a) { launch_policy<true>(a); }
 #endif
 
 GPD_DBG_READER(gpd_detail_dbg_read_policy)
@@ -61,7 +41,7 @@ int gpd_rollout_policy(const GpdParams* params, const GpdState* state, const Gpd
     if (cfg->task != GPD_TASK_NONE && !target_pos) return bad(GPD_EINVAL, "task needs target_pos");
     if (cfg->auto_reset && !init_pose) return bad(GPD_EINVAL, "auto_reset needs init_pose");
     const int A = (cfg->act_type == GPD_ACT_RPM || cfg->act_type == GPD_ACT_VEL) ? 4 : (cfg->act_type == GPD_ACT_PID ? 3 : 1);
-    const int cap = A == 4 ? 68 : (A == 3 ? 52 : 20);                 // history features the kernel's registers hold (16*NK1 - 12)
+    const int cap = 16 * pol_nk1(A, true) - 12;                       // history features the kernel's registers hold
     const bool hist = policy->in_dim != 12;
     if (hist) {
         if (!state->act_ring || !state->ring_pos || state->hist_len <= 0) return bad(GPD_EINVAL, "in_dim > 12 needs the action ring of state");
@@ -73,46 +53,24 @@ int gpd_rollout_policy(const GpdParams* params, const GpdState* state, const Gpd
     GpdStepCfg c = *cfg;
     if (cfg->task == GPD_TASK_NONE) { target_pos = state->kin; c.target_per_env = 0; }
     const Span T{num_steps, 0, obs_step_stride, env_step_stride, 2};
-    const dim3 grid(static_cast<unsigned>((N + kBlock - 1) / kBlock));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define GPD_POL(PID_, AW_, ACT_, NK1_)                                                                                              \
-    do {                                                                                                                            \
-        if (policy->activation == 1)                                                                                                \
-            hipLaunchKernelGGL((gpd_rollout_policy_kernel<PID_, AW_, ACT_, NK1_, true>), grid, dim3(kBlock), 0, st, *params, *state, c, T, \
-                               *policy, obs12_in, target_pos, init_pose, actions_out, obs12, reward, terminated, truncated, term_obs12); \
-        else                                                                                                                        \
-            hipLaunchKernelGGL((gpd_rollout_policy_kernel<PID_, AW_, ACT_, NK1_, false>), grid, dim3(kBlock), 0, st, *params, *state, c, T, \
-                               *policy, obs12_in, target_pos, init_pose, actions_out, obs12, reward, terminated, truncated, term_obs12); \
-    } while (0)
-#define GPD_POLN(AW_, ACT_, NK1_)                                                                                                    \
-    do {                                                                                                                            \
-        const float4 sd = make_float4(action_std[0], AW_ > 1 ? action_std[1] : 0.0f, AW_ > 2 ? action_std[2] : 0.0f,                 \
-                                      AW_ > 3 ? action_std[3] : 0.0f);                                                               \
-        if (policy->activation == 1)                                                                                                \
-            hipLaunchKernelGGL((gpd_rollout_policy_noise_kernel<AW_, ACT_, NK1_, true>), grid, dim3(kBlock), 0, st, *params, *state, c, \
-                               T, *policy, obs12_in, target_pos, init_pose, actions_out, obs12, reward, terminated, truncated, noise, \
-                               mean_out, sd, term_obs12);                                                                           \
-        else                                                                                                                        \
-            hipLaunchKernelGGL((gpd_rollout_policy_noise_kernel<AW_, ACT_, NK1_, false>), grid, dim3(kBlock), 0, st, *params, *state, c, \
-                               T, *policy, obs12_in, target_pos, init_pose, actions_out, obs12, reward, terminated, truncated, noise, \
-                               mean_out, sd, term_obs12);                                                                           \
-    } while (0)
+    const unsigned grid = static_cast<unsigned>((N + kBlock - 1) / kBlock);
+    const GpdPolicyLaunch a{params, state, &c, &T, policy, obs12_in, target_pos, init_pose, actions_out, obs12, reward, terminated,
+                            truncated, stream, grid, hist ? 1 : 0, term_obs12};
     if (noise) {                 // sampling: the RPM action types (the ones examples/learn.py and the reference's learn.py train)
         if (pid) return bad(GPD_ENOTSUP, "sampling (noise) is implemented for ActionType.RPM and ONE_D_RPM");
-        if (cfg->act_type == GPD_ACT_RPM) { if (hist) GPD_POLN(4, GPD_ACT_RPM, 5); else GPD_POLN(4, GPD_ACT_RPM, 1); }
-        else { if (hist) GPD_POLN(1, GPD_ACT_ONE_D_RPM, 2); else GPD_POLN(1, GPD_ACT_ONE_D_RPM, 1); }
-    } else
-    if (pid) {                   // (instantiated in the main unit, see GpdPolicyLaunch)
-        const GpdPolicyLaunch a{params, state, &c, &T, policy, obs12_in, target_pos, init_pose, actions_out, obs12, reward, terminated,
-                                truncated, stream, grid.x, hist ? 1 : 0, term_obs12};
-        gpd_detail_launch_policy_pid(a);
-    } else if (cfg->act_type == GPD_ACT_RPM) {      // NK1 = K-steps of layer 1: 16*NK1 >= 12 + history features
-        if (hist) GPD_POL(false, 4, GPD_ACT_RPM, 5); else GPD_POL(false, 4, GPD_ACT_RPM, 1);
+        policy_variant<false>(cfg->act_type, hist, policy->activation == 1, [&](auto aw, auto act, auto nk1, auto relu) {
+            constexpr int AW = decltype(aw)::value;
+            const float4 sd = make_float4(action_std[0], AW > 1 ? action_std[1] : 0.0f, AW > 2 ? action_std[2] : 0.0f,
+                                          AW > 3 ? action_std[3] : 0.0f);
+            hipLaunchKernelGGL((gpd_rollout_policy_noise_kernel<AW, decltype(act)::value, decltype(nk1)::value, decltype(relu)::value>),
+                               dim3(grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream), *params, *state, c, T, *policy, obs12_in,
+                               target_pos, init_pose, actions_out, obs12, reward, terminated, truncated, noise, mean_out, sd, term_obs12);
+        });
+    } else if (pid) {
+        gpd_detail_launch_policy_pid(a);         // (instantiated in the main unit, see GpdPolicyLaunch)
     } else {
-        if (hist) GPD_POL(false, 1, GPD_ACT_ONE_D_RPM, 2); else GPD_POL(false, 1, GPD_ACT_ONE_D_RPM, 1);
+        launch_policy<false>(a);
     }
-#undef GPD_POL
-#undef GPD_POLN
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "gpd_rollout_policy launch");
     return 0;

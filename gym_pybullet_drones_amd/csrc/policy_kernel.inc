@@ -1,5 +1,5 @@
-// policy_kernel.inc -- the policy-in-the-loop rollout kernel (DESIGN.md section 3.7), a template: policy.hip instantiates the RPM variants
-// under the default scheduler, step_rollout.hip the DSLPID variants under max-ilp.  Included after gpd_common.inc.
+// policy_kernel.inc -- the policy-in-the-loop rollout kernel (DESIGN.md section 3.7), a template, and its launcher: policy.hip instantiates
+// the RPM variants under the default scheduler, step_rollout.hip the DSLPID variants under max-ilp.  Included after gpd_common.inc.
 #pragma once
 namespace {
 
@@ -362,6 +362,40 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_policy_noise_kernel(
     float* __restrict__ term_obs12) {
     rollout_policy_body<false, AW, ACT, NK1, RELU, true>(P, S, C, T, Pol, obs12_in, target_pos, init_pose, actions_out, obs12, reward,
                                                          terminated, truncated, noise, mean_out, sd.x, sd.y, sd.z, sd.w, term_obs12);
+}
+
+// Which instantiation serves a call: f(Const<AW>, Const<ACT>, Const<NK1>, Const<RELU>) with the row width and the action type from
+// `act_type` -- one of the three DSLPID types (PID) or of the two RPM types (!PID; the entry has checked it) -- RELU from the policy's
+// activation, and NK1 = K-steps of layer 1: 16*NK1 >= 12 + history features (the capacity gpd_rollout_policy checks a history against).
+// A unit instantiates the kernels of the PID it asks for, and no other.
+constexpr int pol_nk1(int aw, bool hist) { return !hist ? 1 : (aw == 4 ? 5 : (aw == 3 ? 4 : 2)); }
+
+template <bool PID, class F>
+void policy_variant(int act_type, bool hist, bool relu, F&& f) {
+    auto with = [&](auto aw, auto act) {
+        auto go = [&](auto nk1) { if (relu) f(aw, act, nk1, Const<true>{}); else f(aw, act, nk1, Const<false>{}); };
+        if (hist) go(Const<pol_nk1(decltype(aw)::value, true)>{}); else go(Const<pol_nk1(decltype(aw)::value, false)>{});
+    };
+    if constexpr (PID) {
+        switch (act_type) {
+            case GPD_ACT_VEL: with(Const<4>{}, Const<GPD_ACT_VEL>{}); break;
+            case GPD_ACT_PID: with(Const<3>{}, Const<GPD_ACT_PID>{}); break;
+            default: with(Const<1>{}, Const<GPD_ACT_ONE_D_PID>{}); break;
+        }
+    } else {
+        if (act_type == GPD_ACT_RPM) with(Const<4>{}, Const<GPD_ACT_RPM>{}); else with(Const<1>{}, Const<GPD_ACT_ONE_D_RPM>{});
+    }
+}
+
+// the deterministic kernels' launch (the caller reads hipGetLastError)
+template <bool PID>
+void launch_policy(const GpdPolicyLaunch& a) {
+    const Span& T = *static_cast<const Span*>(a.span);
+    policy_variant<PID>(a.cfg->act_type, a.hist != 0, a.policy->activation == 1, [&](auto aw, auto act, auto nk1, auto relu) {
+        hipLaunchKernelGGL((gpd_rollout_policy_kernel<PID, decltype(aw)::value, decltype(act)::value, decltype(nk1)::value, decltype(relu)::value>),
+                           dim3(a.grid), dim3(kBlock), 0, static_cast<hipStream_t>(a.stream), *a.params, *a.state, *a.cfg, T, *a.policy,
+                           a.obs12_in, a.target_pos, a.init_pose, a.actions_out, a.obs12, a.reward, a.terminated, a.truncated, a.term_obs12);
+    });
 }
 
 }  // namespace

@@ -745,8 +745,6 @@ inline bool sized_variants() {
     return on;
 }
 
-template <auto V> using Const = std::integral_constant<decltype(V), V>;
-
 // f(Const<i>{}) -- instantiated for the entries of LIST this <EXT, ACT, PLANT> compiles, and only for them
 template <const auto& LIST, bool EXT, int ACT, bool PLANT, class F, size_t... I>
 void launch_entry(size_t i, F& f, std::index_sequence<I...>) {
@@ -965,26 +963,7 @@ int rollout_impl(const char* who, bool keep_ring, More&& more, const GpdParams* 
 // The DSLPID variants of the policy kernel are instantiated HERE, under this unit's scheduler (gpd_common.inc says why);
 // GPD_PID_POLICY_IN_POLICY_TU (experiment / regression switch, tests/test_kernel_isa.py) moves them to policy.hip
 #ifndef GPD_PID_POLICY_IN_POLICY_TU
-void gpd_detail_launch_policy_pid(const GpdPolicyLaunch& a) {
-    const Span& T = *static_cast<const Span*>(a.span);
-    const dim3 grid(a.grid);
-    hipStream_t st = static_cast<hipStream_t>(a.stream);
-#define GPD_POL(AW_, ACT_, NK1_)                                                                                                   \
-    do {                                                                                                                            \
-        if (a.policy->activation == 1)                                                                                              \
-            hipLaunchKernelGGL((gpd_rollout_policy_kernel<true, AW_, ACT_, NK1_, true>), grid, dim3(kBlock), 0, st, *a.params, *a.state, *a.cfg, T, \
-                               *a.policy, a.obs12_in, a.target_pos, a.init_pose, a.actions_out, a.obs12, a.reward, a.terminated, a.truncated, a.term_obs12); \
-        else                                                                                                                        \
-            hipLaunchKernelGGL((gpd_rollout_policy_kernel<true, AW_, ACT_, NK1_, false>), grid, dim3(kBlock), 0, st, *a.params, *a.state, *a.cfg, T, \
-                               *a.policy, a.obs12_in, a.target_pos, a.init_pose, a.actions_out, a.obs12, a.reward, a.terminated, a.truncated, a.term_obs12); \
-    } while (0)
-    switch (a.cfg->act_type) {
-        case GPD_ACT_VEL: if (a.hist) GPD_POL(4, GPD_ACT_VEL, 5); else GPD_POL(4, GPD_ACT_VEL, 1); break;
-        case GPD_ACT_PID: if (a.hist) GPD_POL(3, GPD_ACT_PID, 4); else GPD_POL(3, GPD_ACT_PID, 1); break;
-        default: if (a.hist) GPD_POL(1, GPD_ACT_ONE_D_PID, 2); else GPD_POL(1, GPD_ACT_ONE_D_PID, 1); break;
-    }
-#undef GPD_POL
-}
+void gpd_detail_launch_policy_pid(const GpdPolicyLaunch& a) { launch_policy<true>(a); }
 #endif
 
 GPD_DBG_READER(gpd_detail_dbg_read_step)

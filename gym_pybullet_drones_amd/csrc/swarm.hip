@@ -1084,6 +1084,33 @@ __global__ __launch_bounds__(kBlock) void nbr_env_kernel(const float4* __restric
     nb_store<K>(O, e * D + d, cnt, best, me, mine);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Host side
+// ------------------------------------------------------------------------------------------------
+DwGrid grid_of(const GpdSwarm& w) {
+    return DwGrid{1.0f / w.cell, w.x0, w.y0, w.nx, w.ny, w.z0, w.nz > 1 ? 1.0f / w.zbin : 0.0f, w.nz};
+}
+
+// The counting sort of `n` positions by key: count, then the scatter, which up to kDwScanMax keys scans the counts itself and beyond
+// them follows a scan launch.  `count` holds 2 (keys + 1) integers, zeroed: the counts, and in its second half the scatter's per-key
+// cursors.  `vec_out`: the count pass also writes the state vectors of `vec_state` (dwg_count_kernel<true>).
+void dwg_sort(hipStream_t st, const DwPos& src, int n, const DwGrid& G, const int* visit, int* count, int* start, int* order,
+              float4* sorted, float* dw_out, const DwBinOut& B, const GpdState* vec_state = nullptr, const float* vec_obs12 = nullptr,
+              float* vec_out = nullptr) {
+    const dim3 grid(static_cast<unsigned>((n + kBlock - 1) / kBlock));
+    const int keys = G.nx * G.ny * G.nz;
+    int* const cursors = count + keys + 1;
+    if (vec_out) hipLaunchKernelGGL(dwg_count_kernel<true>, grid, dim3(kBlock), 0, st, src, n, G, visit, count, *vec_state, vec_obs12, vec_out);
+    else hipLaunchKernelGGL(dwg_count_kernel<false>, grid, dim3(kBlock), 0, st, src, n, G, visit, count, GpdState{}, nullptr, nullptr);
+    auto scatter = [&](auto fused) {
+        hipLaunchKernelGGL(dwg_scatter_kernel<decltype(fused)::value>, grid, dim3(kBlock), 0, st, src, n, G, visit, count, cursors, start,
+                           order, sorted, dw_out, B);
+    };
+    if (keys <= kDwScanMax) return scatter(Const<true>{});
+    hipLaunchKernelGGL(dwg_scan_kernel, dim3(1), dim3(1024), 0, st, count, start, keys);
+    scatter(Const<false>{});
+}
+
 }  // namespace
 
 GPD_DBG_READER(gpd_detail_dbg_read_swarm)
@@ -1106,35 +1133,19 @@ int gpd_downwash_global(const GpdParams* params, const float* kin, int64_t ld, i
     if (nx < 3 || ny < 3 || static_cast<int64_t>(nx) * ny * nz > 65536)
         return fail(GPD_ERANGE, "gpd_downwash_global: need nx, ny >= 3 (periodic 3x3 search) and nx*ny*nz <= 65536");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int cells = nx * ny, keys = cells * nz;
     const DwGrid G{1.0f / cell, x0, y0, nx, ny, z0, nz > 1 ? 1.0f / zbin : 0.0f, nz};
-    hipError_t e;
-    const dim3 grid(static_cast<unsigned>((n + kBlock - 1) / kBlock));
-    const DwPos src{kin, ld, nullptr};
     if (vec_out) {
         if (!vec_state || !vec_state->kin || !vec_obs12) return fail(GPD_EINVAL, "gpd_downwash_global: vec_out needs vec_state and vec_obs12");
         if (vec_state->ld < n) return fail(GPD_EINVAL, "gpd_downwash_global: vec_state.ld < n");
-        hipLaunchKernelGGL(dwg_count_kernel<true>, grid, dim3(kBlock), 0, st, src, n, G, visit_order, cell_count, *vec_state,
-                           vec_obs12, vec_out);
-    } else {
-        hipLaunchKernelGGL(dwg_count_kernel<false>, grid, dim3(kBlock), 0, st, src, n, G, visit_order, cell_count, GpdState{},
-                           nullptr, nullptr);
     }
-    int32_t* const cursors = cell_count + keys + 1;       // second half of cell_count: the scatter's per-key cursors
     const DwBinOut B{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, n, 0.0f, 0};
-    if (keys <= kDwScanMax) {
-        hipLaunchKernelGGL(dwg_scatter_kernel<true>, grid, dim3(kBlock), 0, st, src, n, G, visit_order, cell_count, cursors,
-                           cell_start, order, reinterpret_cast<float4*>(sorted_xyzc), dw_out, B);
-    } else {
-        hipLaunchKernelGGL(dwg_scan_kernel, dim3(1), dim3(1024), 0, st, cell_count, cell_start, keys);
-        hipLaunchKernelGGL(dwg_scatter_kernel<false>, grid, dim3(kBlock), 0, st, src, n, G, visit_order, cell_count, cursors,
-                           cell_start, order, reinterpret_cast<float4*>(sorted_xyzc), dw_out, B);
-    }
+    dwg_sort(st, DwPos{kin, ld, nullptr}, n, G, visit_order, cell_count, cell_start, order, reinterpret_cast<float4*>(sorted_xyzc), dw_out, B,
+             vec_state, vec_obs12, vec_out);
     const DwWorld Wd{nullptr, nullptr, nullptr, 0, n, 0, 0, 0, cell, nullptr, 0.0f, n};
     hipLaunchKernelGGL(dwg_force_kernel<0>, dim3(static_cast<unsigned>((n + 63) / 64)), dim3(kBlock), 0, st, static_cast<uint32_t*>(nullptr),
                        static_cast<unsigned short*>(nullptr), static_cast<int*>(nullptr), Wd.pos4, order,
                        reinterpret_cast<const float4*>(sorted_xyzc), 0, Wd.n_slots, *params, G, Wd, DwLists{}, cell_start, dw_out, cell_count);
-    e = hipGetLastError();
+    hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "gpd_downwash_global launch");
     return 0;
 }
@@ -1183,11 +1194,15 @@ int gpd_swarm_step(const GpdParams* params, const GpdState* state, const GpdStep
                      reinterpret_cast<float4*>(swarm->pos_sorted), swarm->drift, vec_out};
     const dim3 grid(static_cast<unsigned>((cfg->num_envs + kBlock - 1) / kBlock));
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define GPD_SWARM_HOT state->kin, action, state->last_rpm, state->dw_force, O.bin_pos_own, O.slot_of_own, static_cast<uint32_t>(state->ld), cfg->num_envs
+    auto launch = [&](auto act) {
+        hipLaunchKernelGGL(gpd_swarm_step_kernel<decltype(act)::value>, grid, dim3(kBlock), 0, st, state->kin, action, state->last_rpm,
+                           state->dw_force, O.bin_pos_own, O.slot_of_own, static_cast<uint32_t>(state->ld), cfg->num_envs, *params, *state,
+                           *cfg, obs12, O);
+    };
     switch (cfg->act_type) {
-        case GPD_ACT_RAW_RPM: hipLaunchKernelGGL(gpd_swarm_step_kernel<GPD_ACT_RAW_RPM>, grid, dim3(kBlock), 0, st, GPD_SWARM_HOT, *params, *state, *cfg, obs12, O); break;
-        case GPD_ACT_DIRECT_RPM: hipLaunchKernelGGL(gpd_swarm_step_kernel<GPD_ACT_DIRECT_RPM>, grid, dim3(kBlock), 0, st, GPD_SWARM_HOT, *params, *state, *cfg, obs12, O); break;
-        default: hipLaunchKernelGGL(gpd_swarm_step_kernel<GPD_ACT_RPM>, grid, dim3(kBlock), 0, st, GPD_SWARM_HOT, *params, *state, *cfg, obs12, O); break;
+        case GPD_ACT_RAW_RPM: launch(Const<GPD_ACT_RAW_RPM>{}); break;
+        case GPD_ACT_DIRECT_RPM: launch(Const<GPD_ACT_DIRECT_RPM>{}); break;
+        default: launch(Const<GPD_ACT_RPM>{}); break;
     }
     // (too many meta rows for every force workgroup to read: leave the rank's maximum in its first meta row)
     if (static_cast<int64_t>(swarm->world_size) * swarm->meta_rows > 1024)
@@ -1216,23 +1231,10 @@ int gpd_swarm_bin(const GpdSwarm* w, void* stream) {
     if (int rc = swarm_args("gpd_swarm_bin", w, true)) return rc;
     if (!w->dw_force) return fail(GPD_EINVAL, "gpd_swarm_bin: NULL dw_force (a drone without a finite position gets force 0 here)");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int n = w->n_rows, keys = w->nx * w->ny * w->nz;
-    const DwGrid G{1.0f / w->cell, w->x0, w->y0, w->nx, w->ny, w->z0, w->nz > 1 ? 1.0f / w->zbin : 0.0f, w->nz};
-    const dim3 grid(static_cast<unsigned>((n + kBlock - 1) / kBlock));
-    const DwPos src{nullptr, 0, reinterpret_cast<const float4*>(w->pos4)};
-    hipLaunchKernelGGL(dwg_count_kernel<false>, grid, dim3(kBlock), 0, st, src, n, G, w->visit, w->cell_count, GpdState{}, nullptr, nullptr);
-    int32_t* const cursors = w->cell_count + keys + 1;
     const DwBinOut B{w->slot_key, w->slot_of, w->visit_out, w->list_ok, reinterpret_cast<float4*>(w->bin_pos), w->pos4, w->drift, w->slab, w->world_size, w->meta_rows, w->rank * w->slab, w->own_count,
                      w->pair_list ? w->list_delta : 0.0f, w->list_adapt != 0};
-    float4* const srt = reinterpret_cast<float4*>(w->pos_sorted);
-    if (keys <= kDwScanMax) {
-        hipLaunchKernelGGL(dwg_scatter_kernel<true>, grid, dim3(kBlock), 0, st, src, n, G, w->visit, w->cell_count, cursors,
-                           w->cell_start, w->order, srt, w->dw_force, B);
-    } else {
-        hipLaunchKernelGGL(dwg_scan_kernel, dim3(1), dim3(1024), 0, st, w->cell_count, w->cell_start, keys);
-        hipLaunchKernelGGL(dwg_scatter_kernel<false>, grid, dim3(kBlock), 0, st, src, n, G, w->visit, w->cell_count, cursors,
-                           w->cell_start, w->order, srt, w->dw_force, B);
-    }
+    dwg_sort(st, DwPos{nullptr, 0, reinterpret_cast<const float4*>(w->pos4)}, w->n_rows, grid_of(*w), w->visit, w->cell_count, w->cell_start,
+             w->order, reinterpret_cast<float4*>(w->pos_sorted), w->dw_force, B);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "gpd_swarm_bin launch");
     return 0;
@@ -1247,7 +1249,7 @@ int gpd_swarm_forces(const GpdParams* params, const GpdSwarm* w, int32_t build_l
         return fail(GPD_EINVAL, "gpd_swarm_forces: pair_list needs pair_nb, list_ok, 4 <= list_cap <= 65535 and list_delta >= 0");
     // (an entry is lane << 26 | index and 0xffffffff marks an empty lane: index 2^26 - 1 of lane 63 must not exist)
     if (lists && w->n_rows >= (1 << 26)) return fail(GPD_ERANGE, "gpd_swarm_forces: wake lists address fewer than 2^26 rows");
-    const DwGrid G{1.0f / w->cell, w->x0, w->y0, w->nx, w->ny, w->z0, w->nz > 1 ? 1.0f / w->zbin : 0.0f, w->nz};
+    const DwGrid G = grid_of(*w);
     const float4* const p4 = reinterpret_cast<const float4*>(w->pos4);
     const DwWorld Wd{w->pos_sorted ? nullptr : p4, w->slot_key, p4, w->rank * w->slab, w->own_count, w->slab, w->world_size, w->meta_rows, w->cell,
                      w->drift, 1.0f / static_cast<float>(w->total_drones), w->n_rows};
@@ -1255,11 +1257,13 @@ int gpd_swarm_forces(const GpdParams* params, const GpdSwarm* w, int32_t build_l
     const dim3 grid(static_cast<unsigned>((w->n_rows + 63) / 64) + 1u);        // (+ the workgroup that computes the drift)
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float4* const srt = reinterpret_cast<const float4*>(w->pos_sorted);
-#define GPD_FORCE_ARGS Ls.list, Ls.nb, Ls.ok, Wd.pos4, w->order, srt, Ls.cap, Wd.n_slots, *params, G, Wd, Ls, w->cell_start, w->dw_force, w->cell_count
-    if (!lists) hipLaunchKernelGGL(dwg_force_kernel<0>, grid, dim3(kBlock), 0, st, GPD_FORCE_ARGS);
-    else if (build_lists) hipLaunchKernelGGL(dwg_force_kernel<1>, grid, dim3(kBlock), 0, st, GPD_FORCE_ARGS);
-    else hipLaunchKernelGGL(dwg_force_kernel<2>, grid, dim3(kBlock), 0, st, GPD_FORCE_ARGS);
-#undef GPD_FORCE_ARGS
+    auto launch = [&](auto mode) {      // 0: no wake lists, 1: the sweep that builds them, 2: their replay
+        hipLaunchKernelGGL(dwg_force_kernel<decltype(mode)::value>, grid, dim3(kBlock), 0, st, Ls.list, Ls.nb, Ls.ok, Wd.pos4, w->order, srt,
+                           Ls.cap, Wd.n_slots, *params, G, Wd, Ls, w->cell_start, w->dw_force, w->cell_count);
+    };
+    if (!lists) launch(Const<0>{});
+    else if (build_lists) launch(Const<1>{});
+    else launch(Const<2>{});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "gpd_swarm_forces launch");
     return 0;
@@ -1288,15 +1292,16 @@ int gpd_neighbors(const float* pos4, int32_t n_rows, int32_t query_first, int32_
     hipStream_t st = static_cast<hipStream_t>(stream);
     const NbOut O{nbr_count, nbr_idx, reinterpret_cast<float4*>(nbr_rel), adjacency, query_first, query_count, k};
     const float4* const p4 = reinterpret_cast<const float4*>(pos4);
-#define GPD_NB_K(LAUNCH) do { if (k <= 4) { LAUNCH(4); } else if (k <= 8) { LAUNCH(8); } else if (k <= 16) { LAUNCH(16); } else { LAUNCH(32); } } while (0)
+    // the kernels' list length: the request rounded up to 4, 8, 16 or 32
+    auto with_k = [&](auto&& launch) {
+        if (k <= 4) launch(Const<4>{}); else if (k <= 8) launch(Const<8>{}); else if (k <= 16) launch(Const<16>{}); else launch(Const<32>{});
+    };
     if (D != 0) {
         if (n_rows % D != 0 || query_first % D != 0 || query_count % D != 0)
             return bad(GPD_EINVAL, "with drones_per_env = D the rows and the query range are whole aviaries (multiples of D)");
         const int G = kBlock / D, E = query_count / D;
         const dim3 grid(static_cast<unsigned>((E + G - 1) / G));
-#define GPD_NB_ENV(KK) hipLaunchKernelGGL(nbr_env_kernel<KK>, grid, dim3(kBlock), 0, st, p4, D, G, E, r2, O)
-        GPD_NB_K(GPD_NB_ENV);
-#undef GPD_NB_ENV
+        with_k([&](auto kk) { hipLaunchKernelGGL(nbr_env_kernel<decltype(kk)::value>, grid, dim3(kBlock), 0, st, p4, D, G, E, r2, O); });
     } else {
         if (!cell_count || !cell_start || !order || !sorted_xyzc) return bad(GPD_EINVAL, "one world needs the sort's scratch: cell_count, cell_start, order, sorted_xyzc");
         if (visit_order == order) return bad(GPD_EINVAL, "visit_order must not alias order (ping-pong two buffers)");
@@ -1311,28 +1316,16 @@ int gpd_neighbors(const float* pos4, int32_t n_rows, int32_t query_first, int32_
         const double ex = static_cast<double>(x1) - x0, ey = static_cast<double>(y1) - y0;
         int nx = cells_of(ex, c), ny = cells_of(ey, c);
         while (static_cast<int64_t>(nx) * ny > 65536) { c *= 2.0; nx = cells_of(ex, c); ny = cells_of(ey, c); }     // coarser: less selective, still exact
-        const int keys = nx * ny;
         const DwGrid G{static_cast<float>(1.0 / c), x0, y0, nx, ny, 0.0f, 0.0f, 1};
-        const dim3 grid(static_cast<unsigned>((n_rows + kBlock - 1) / kBlock));
-        const DwPos src{nullptr, 0, p4};
-        hipLaunchKernelGGL(dwg_count_kernel<false>, grid, dim3(kBlock), 0, st, src, n_rows, G, visit_order, cell_count, GpdState{}, nullptr, nullptr);
-        int32_t* const cursors = cell_count + keys + 1;
         const DwBinOut B{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0.0f, 0};     // (own_cnt = 0: no force array)
         float4* const srt = reinterpret_cast<float4*>(sorted_xyzc);
-        if (keys <= kDwScanMax) {
-            hipLaunchKernelGGL(dwg_scatter_kernel<true>, grid, dim3(kBlock), 0, st, src, n_rows, G, visit_order, cell_count, cursors,
-                               cell_start, order, srt, static_cast<float*>(nullptr), B);
-        } else {
-            hipLaunchKernelGGL(dwg_scan_kernel, dim3(1), dim3(1024), 0, st, cell_count, cell_start, keys);
-            hipLaunchKernelGGL(dwg_scatter_kernel<false>, grid, dim3(kBlock), 0, st, src, n_rows, G, visit_order, cell_count, cursors,
-                               cell_start, order, srt, static_cast<float*>(nullptr), B);
-        }
+        dwg_sort(st, DwPos{nullptr, 0, p4}, n_rows, G, visit_order, cell_count, cell_start, order, srt, nullptr, B);
         const dim3 sgrid(static_cast<unsigned>((n_rows + 63) / 64));
-#define GPD_NB_WORLD(KK) hipLaunchKernelGGL(nbr_world_kernel<KK>, sgrid, dim3(64), 0, st, p4, order, srt, cell_start, n_rows, nx, ny, r2, O, cell_count)
-        GPD_NB_K(GPD_NB_WORLD);
-#undef GPD_NB_WORLD
+        with_k([&](auto kk) {
+            hipLaunchKernelGGL(nbr_world_kernel<decltype(kk)::value>, sgrid, dim3(64), 0, st, p4, order, srt, cell_start, n_rows, nx, ny, r2, O,
+                               cell_count);
+        });
     }
-#undef GPD_NB_K
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "gpd_neighbors launch");
     return 0;

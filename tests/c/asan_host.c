@@ -1,8 +1,9 @@
 /*
  * Drives the HOST side of every C-ABI entry (include/gpd.h) under AddressSanitizer + UndefinedBehaviorSanitizer, on a machine without
- * a GPU: libgpd's four units compiled host-only with the sanitizers, the HIP runtime replaced by tests/stubs/hip_stub.c (launches are
- * counted, nothing runs).  What is exercised: argument validation and error codes, the per-thread last-error string, struct plumbing,
- * and the launch arithmetic (grid / block / dynamic LDS sizes at the largest supported shapes -- where a 32-bit product overflows first).
+ * a GPU: libgpd's five units (step_rollout.hip, policy.hip, swarm.hip, abi.hip, mrac.hip) compiled host-only with the sanitizers, the HIP
+ * runtime replaced by tests/stubs/hip_stub.c (launches are counted and named, nothing runs).  What is exercised: argument validation and
+ * error codes, the per-thread last-error string, struct plumbing, the launch arithmetic (grid / block / dynamic LDS sizes at the largest
+ * supported shapes -- where a 32-bit product overflows first), and which kernel a call is routed to (KERNEL: a piece of its symbol).
  * Device pointers are fake non-null addresses: host code must never dereference them (ASan would say so).  SURVEY.md section 5's
  * "-fsanitize=address host build"; run by tests/test_host_sanitizers.py.  Prints one line per check; exit code = failed checks.
  */
@@ -14,6 +15,8 @@
 
 int hipstub_launches(void);
 void hipstub_last(unsigned out[7]);
+const char* hipstub_last_kernel(void);
+#define KERNEL(piece) (strstr(hipstub_last_kernel(), piece) != NULL)
 
 static int failed;
 #define CHECK(cond, what) do { if (!(cond)) { ++failed; printf("FAIL %s (line %d): %s\n", what, __LINE__, gpd_last_error()); } else printf("ok   %s\n", what); } while (0)
@@ -84,16 +87,25 @@ int main(void) {
             CHECK(STEP(DEV(3), DEV(4)) == 0, what);
         }
     C.act_type = GPD_ACT_RPM; C.physics_flags = 0;
+    int rc = gpd_rollout(&P, &S, &C, 1, DEV(3), 4096 * 4, DEV(4), DEV(5), DEV(6), 4096 * 12, DEV(7), DEV(8), DEV(9), 4096, NULL, NULL);
+    CHECK(rc == 0 && KERNEL("gpd_step_kernel"), "a rollout of one step -> gpd_step_kernel");
     /* rollouts: the store-wave kernel (terminal observations) asks for dynamic LDS, the single-drone kernel for none */
-    int rc = gpd_rollout(&P, &S, &C, 64, DEV(3), 4096 * 4, DEV(4), DEV(5), DEV(6), 4096 * 12, DEV(7), DEV(8), DEV(9), 4096, NULL, NULL);
+    rc = gpd_rollout(&P, &S, &C, 64, DEV(3), 4096 * 4, DEV(4), DEV(5), DEV(6), 4096 * 12, DEV(7), DEV(8), DEV(9), 4096, NULL, NULL);
     hipstub_last(last);
     CHECK(rc == 0 && last[0] == 16 && last[3] == 256 && last[6] == 0, "gpd_rollout, 4096 aviaries: 16 workgroups, no dynamic LDS");
+    CHECK(KERNEL("gpd_rollout1_kernel"), "a rollout without terminal observations -> gpd_rollout1_kernel");
     rc = gpd_rollout(&P, &S, &C, 64, DEV(3), 4096 * 4, DEV(4), DEV(5), DEV(6), 4096 * 12, DEV(7), DEV(8), DEV(9), 4096, DEV(12), NULL);
     hipstub_last(last);
     CHECK(rc == 0 && last[3] == 320 && last[6] == 4 * (256 * 48 + 256 * 4 + 512), "gpd_rollout with terminal observations: 320 threads, four LDS slots");
+    CHECK(KERNEL("gpd_rollout_kernel"), "a rollout with terminal observations -> gpd_rollout_kernel");
+    C.drones_per_env = 100; C.num_envs = 40; C.task = GPD_TASK_MULTIHOVER;
+    rc = gpd_rollout(&P, &S, &C, 64, DEV(3), 4000 * 4, DEV(4), DEV(5), DEV(6), 4000 * 12, DEV(7), DEV(8), DEV(9), 40, NULL, NULL);
+    CHECK(rc == 0 && KERNEL("gpd_rollout_kernel"), "a rollout of 100-drone aviaries -> gpd_rollout_kernel");
+    C.drones_per_env = 1; C.num_envs = 4096; C.task = GPD_TASK_HOVER;
     CHECK(gpd_rollout(&P, &S, &C, 0, DEV(3), 0, DEV(4), DEV(5), DEV(6), 0, DEV(7), DEV(8), DEV(9), 0, NULL, NULL) != 0, "gpd_rollout with K = 0 is refused");
     S.act_ring = DEV(13); S.ring_pos = DEV(14); S.hist_len = 15;
     CHECK(gpd_rollout_history(&P, &S, &C, 20, DEV(3), 4096 * 4, DEV(4), DEV(5), DEV(6), 4096 * 12, DEV(7), DEV(8), DEV(9), 4096, NULL) == 0, "gpd_rollout_history");
+    CHECK(KERNEL("gpd_rollout1_kernel"), "gpd_rollout_history -> gpd_rollout1_kernel");
     CHECK(gpd_hist_rows(&S, 4096, 1, 4, DEV(6), DEV(15), NULL) == 0, "gpd_hist_rows");
     CHECK(gpd_full_obs(&S, 20, 4096, 1, 4, DEV(6), 4096 * 12, DEV(3), 4096 * 4, DEV(15), 4096 * 72, NULL) == 0, "gpd_full_obs");
     CHECK(gpd_hist_rows(&S, 4096, 1, 5, DEV(6), DEV(15), NULL) != 0, "gpd_hist_rows with act_dim 5 is refused");
@@ -103,6 +115,15 @@ int main(void) {
     pol.in_dim = 12 + 15 * 4;
     CHECK(gpd_rollout_policy(&P, &S, &C, &pol, 8, DEV(6), DEV(4), DEV(5), DEV(22), DEV(6), 4096 * 12, DEV(7), DEV(8), DEV(9), 4096, NULL, NULL, NULL, NULL, NULL) == 0,
           "gpd_rollout_policy, 72-float rows");
+#define POLICY(noise_, std_) gpd_rollout_policy(&P, &S, &C, &pol, 8, DEV(6), DEV(4), DEV(5), DEV(22), DEV(6), 4096 * 12, DEV(7), DEV(8), DEV(9), 4096, noise_, std_, NULL, NULL, NULL)
+    CHECK(KERNEL("gpd_rollout_policy_kernelILb0ELi4ELi0ELi5E"), "RPM actions with a history -> <PID 0, AW 4, ACT 0, NK1 5>");
+    const float action_std[4] = {0.1f, 0.1f, 0.1f, 0.1f};        /* (read by the host: a real array) */
+    CHECK(POLICY(DEV(29), action_std) == 0 && KERNEL("gpd_rollout_policy_noise_kernel"), "with noise -> gpd_rollout_policy_noise_kernel");
+    pol.in_dim = 12;
+    CHECK(POLICY(NULL, NULL) == 0 && KERNEL("gpd_rollout_policy_kernelILb0ELi4ELi0ELi1E"), "RPM actions, in_dim 12 -> NK1 1");
+    C.act_type = GPD_ACT_VEL;
+    CHECK(POLICY(NULL, NULL) == 0 && KERNEL("gpd_rollout_policy_kernelILb1E"), "a PID action type -> a <PID 1> kernel");
+    C.act_type = GPD_ACT_RPM;
     pol.in_dim = 13;
     CHECK(gpd_rollout_policy(&P, &S, &C, &pol, 8, DEV(6), DEV(4), DEV(5), DEV(22), DEV(6), 4096 * 12, DEV(7), DEV(8), DEV(9), 4096, NULL, NULL, NULL, NULL, NULL) == GPD_ENOTSUP,
           "gpd_rollout_policy refuses in_dim 13");
@@ -134,11 +155,31 @@ int main(void) {
     CHECK(gpd_swarm_forces(&P, &W, 1, NULL) == 0 && hipstub_launches() == n0 + 1, "gpd_swarm_forces (build)");
     hipstub_last(last);
     CHECK(last[0] == 65792 / 64 + 1 && last[3] == 256, "one workgroup per 64 sorted drones + the drift workgroup");
-    CHECK(gpd_swarm_forces(&P, &W, 0, NULL) == 0, "gpd_swarm_forces (replay)");
+    CHECK(KERNEL("dwg_force_kernelILi1E"), "building the wake lists -> dwg_force_kernel<1>");
+    CHECK(gpd_swarm_forces(&P, &W, 0, NULL) == 0 && KERNEL("dwg_force_kernelILi2E"), "gpd_swarm_forces (replay) -> dwg_force_kernel<2>");
+    W.pair_list = NULL;
+    CHECK(gpd_swarm_forces(&P, &W, 0, NULL) == 0 && KERNEL("dwg_force_kernelILi0E"), "gpd_swarm_forces without lists -> dwg_force_kernel<0>");
+    W.pair_list = DEV(50);
     CHECK(gpd_swarm_step(&P, &S, &C, &W, DEV(3), DEV(6), DEV(23), NULL) == 0, "gpd_swarm_step");
     W.list_cap = 2; CHECK(gpd_swarm_forces(&P, &W, 0, NULL) == GPD_EINVAL, "list_cap 2 is refused"); W.list_cap = 48;
     W.n_rows = 1 << 26; CHECK(gpd_swarm_forces(&P, &W, 0, NULL) != 0, "wake lists refuse 2^26 rows"); W.n_rows = 65792;
     W.cell = 5.0f; CHECK(gpd_swarm_bin(&W, NULL) != 0, "a 5 m grid is refused"); W.cell = 10.5f;
+    /* ---- neighbour queries: the list length rounded up, one world or aviaries ---- */
+#define NEIGHBORS(k_, D_) gpd_neighbors(DEV(40), 65536, 0, 65536, 2.0f, k_, D_, 0.0f, -170.0f, -170.0f, 170.0f, 170.0f, NULL, DEV(42), DEV(43), DEV(44), DEV(49), DEV(54), DEV(55), DEV(56), NULL, NULL)
+    CHECK(NEIGHBORS(5, 0) == 0 && KERNEL("nbr_world_kernelILi8E"), "gpd_neighbors k = 5, one world -> nbr_world_kernel<8>");
+    CHECK(NEIGHBORS(17, 8) == 0 && KERNEL("nbr_env_kernelILi32E"), "gpd_neighbors k = 17, aviaries of 8 -> nbr_env_kernel<32>");
+    /* ---- the adaptive controller's rollout: <EXT, PLANT> ---- */
+    static GpdMrac M;
+    S.dw_force = NULL; C.num_envs = 4096; S.ld = 4096;
+#define MRAC(plant_) gpd_rollout_mrac(&P, &M, &S, &C, DEV(57), DEV(58), 4096, DEV(59), 0, DEV(60), plant_, DEV(6), 0, 8, NULL)
+    C.physics_flags = 0;
+    CHECK(MRAC(NULL) == 0 && KERNEL("gpd_rollout_mrac_kernelILb0ELb0E"), "gpd_rollout_mrac, plain -> <EXT 0, PLANT 0>");
+    CHECK(MRAC(DEV(61)) == 0 && KERNEL("gpd_rollout_mrac_kernelILb0ELb1E"), "gpd_rollout_mrac with a plant table -> <EXT 0, PLANT 1>");
+    C.physics_flags = 7;
+    CHECK(MRAC(NULL) == GPD_ENOTSUP, "gpd_rollout_mrac refuses downwash (flags 7)");
+    C.physics_flags = 3;         /* (every add-on model the entry accepts) */
+    CHECK(MRAC(NULL) == 0 && KERNEL("gpd_rollout_mrac_kernelILb1ELb0E"), "gpd_rollout_mrac with add-on models -> <EXT 1, PLANT 0>");
+    CHECK(MRAC(DEV(61)) == 0 && KERNEL("gpd_rollout_mrac_kernelILb1ELb1E"), "gpd_rollout_mrac, add-on models and a plant table -> <EXT 1, PLANT 1>");
     uint32_t dbg[4];
     CHECK(gpd_debug_status(dbg, 0, NULL) == GPD_ENOTSUP, "gpd_debug_status in a release build");
     printf("%d launches recorded, %d checks failed\n", hipstub_launches(), failed);

@@ -1,7 +1,9 @@
 """"-fsanitize=address host build".  The HOST side of libgpd -- argument checks, error strings, struct plumbing,
-launch arithmetic -- compiled from the four product units with AddressSanitizer + UndefinedBehaviorSanitizer (`hipcc --cuda-host-only`:
-no device code, seconds), linked against a HIP runtime that launches nothing (tests/stubs/hip_stub.c) and driven through every entry of
-include/gpd.h by a plain C program (tests/c/asan_host.c).  No GPU needed."""
+launch arithmetic, the choice of the kernel -- compiled from the five product units (step_rollout.hip, policy.hip, swarm.hip, abi.hip,
+mrac.hip) with AddressSanitizer + UndefinedBehaviorSanitizer (`hipcc --cuda-host-only`: no device code, seconds), linked against a HIP
+runtime that launches nothing and names what it was asked to launch (tests/stubs/hip_stub.c), and driven through every entry of
+include/gpd.h by a plain C program (tests/c/asan_host.c); tests/c/launch_trace.c then lists which kernel serves which call over the
+shapes at which a launch path decides something.  No GPU needed."""
 import os
 import re
 import subprocess
@@ -37,13 +39,34 @@ def test_host_side_of_the_c_abi_under_asan_and_ubsan(tmp_path):
     link = [clang + "++", "-shared", "-fPIC"] + san + objs + ["-x", "c", stub_c, os.path.join(REPO, "tests", "stubs", "hip_stub.c"), "-o", lib, "-ldl"]
     res = subprocess.run(link, capture_output=True, text=True)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
-    exe = str(tmp_path / "asan_host")
-    res = subprocess.run([clang] + san + ["-std=c11", "-I", _native.INCLUDE, os.path.join(REPO, "tests", "c", "asan_host.c"), lib, f"-Wl,-rpath,{tmp_path}", "-o", exe],
-                         capture_output=True, text=True)
-    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+    exes = {}
+    for name in ("asan_host", "launch_trace"):
+        exes[name] = str(tmp_path / name)
+        res = subprocess.run([clang] + san + ["-std=c11", "-I", _native.INCLUDE, os.path.join(REPO, "tests", "c", name + ".c"), lib, f"-Wl,-rpath,{tmp_path}", "-o", exes[name]],
+                             capture_output=True, text=True)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    env.pop("GPD_ROLLOUT_SIZED", None)
+    run = subprocess.run([exes["asan_host"]], capture_output=True, text=True, env=env, timeout=120)
     print(run.stdout[-3000:])
     assert "AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-4000:]
     assert run.returncode == 0 and " 0 checks failed" in run.stdout, run.stdout[-3000:] + run.stderr[-2000:]
-    assert run.stdout.count("\nok ") + run.stdout.startswith("ok ") >= 50
+    assert run.stdout.count("\nok ") + run.stdout.startswith("ok ") >= 86
+
+    # which kernel serves which call, with the sized variants and under the hook that leaves the generic kernels only
+    traces = []
+    for hook in ({}, {"GPD_ROLLOUT_SIZED": "0"}):
+        run = subprocess.run([exes["launch_trace"]], capture_output=True, text=True, env=dict(env, **hook), timeout=120)
+        assert "AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-4000:]
+        assert run.returncode == 0, run.stderr[-2000:]
+        lines = run.stdout.splitlines()
+        assert len(lines) > 10000
+        assert not [l for l in lines if l.endswith("-> nothing")][:5]                 # every accepted call launched
+        assert not [l for l in lines if l.split(" -> ")[1].startswith("?")][:5]       # ... kernels the stub can name
+        traces.append(lines)
+    sized, generic = traces
+    assert len(sized) == len(generic)
+    rollout_kernels = ("gpd_step_kernel", "gpd_rollout_kernel", "gpd_rollout1_kernel")
+    changed = [(a, b) for a, b in zip(sized, generic) if a != b]
+    assert changed                                                                     # (the hook does something)
+    assert not [(a, b) for a, b in changed if not (any(k in a for k in rollout_kernels) and any(k in b for k in rollout_kernels))][:5]
