@@ -4,9 +4,15 @@ There is NO fallback: if the library is missing or does not match the header, im
 product path raises.  `build()` compiles it in-tree with hipcc for gfx950 (cross-compiles on a
 machine without a GPU).
 """
+import contextlib
 import ctypes
 import os
 import subprocess
+
+try:        # PyTorch's HIP runtime first: libgpd.so then binds to the copy torch mapped (one runtime per process; loaded the other way
+    import torch  # round, a kernel launch fails with "no ROCm-capable device is detected": round 5)
+except ImportError:     # (setup.py compiles the library through build() where torch need not be installed)
+    torch = None
 
 from .params import GpdParams
 
@@ -209,10 +215,6 @@ def lib() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
         return _lib
-    try:        # PyTorch's HIP runtime first: libgpd.so then binds to the copy torch mapped (one runtime per process; loaded the other way
-        import torch  # noqa: F401 -- round a kernel launch fails with "no ROCm-capable device is detected", gpurun_out/smoke3.log, round 5)
-    except ImportError:
-        pass
     path = os.environ.get("GPD_LIB", LIB_PATH)     # GPD_LIB: A/B-test another build of the same ABI
     if not os.path.exists(path):
         raise GpdError(f"{path} not found: the HIP extension has not been built "
@@ -253,3 +255,59 @@ def check(rc: int, what: str):
 
 def exported_symbols():
     return list(_SIGNATURES)
+
+
+# ---- the one way in: every launch off the hot paths is one `call(...)` line; the hot paths pre-build their tuples with `as_c` ----
+#: `stream` of `call` for the entries that take none (gpd_comm_*, gpd_sizeof_mrac ...)
+NO_STREAM = object()
+_get_raw_stream = getattr(getattr(torch, "_C", None), "_cuda_getCurrentRawStream", None)
+
+
+def raw_stream(device) -> int:
+    """hipStream_t of torch's current stream on `device` (the accessor torch's own compiled kernels use: no Stream object per call)"""
+    if _get_raw_stream is not None and device.index is not None:
+        return _get_raw_stream(device.index)
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+_NO_GUARD = contextlib.nullcontext()
+_Tensor = getattr(torch, "Tensor", None)
+#: what `as_c` has nothing to do for: NULL, numbers, and the two kinds of object it returns itself (a pre-built tuple passes through)
+_AS_IS = frozenset((type(None), int, float, bool, ctypes.c_void_p, type(ctypes.byref(ctypes.c_int()))))
+
+
+def device_guard(device):
+    """the device guard, or nothing when `device` (None: whichever) is the current one already"""
+    if device is None or device.index is None or device.index == torch.cuda.current_device():
+        return _NO_GUARD
+    return torch.cuda.device(device)
+
+
+def as_c(x):
+    """One argument as ctypes takes it: a tensor -> its address, a struct -> a reference to it (explicitly: an entry that takes a
+    struct through a plain `void *`, like gpd_rollout_policy's policy, gets no automatic by-reference passing from ctypes);
+    None (NULL), numbers and ready-made ctypes objects as they are."""
+    kind = type(x)          # (exact types first: `isinstance(3, torch.Tensor)` costs more than the whole function does this way)
+    if kind is _Tensor:
+        return ctypes.c_void_p(x.data_ptr())
+    if kind in _AS_IS:
+        return x
+    if isinstance(x, ctypes.Structure):
+        return ctypes.byref(x)
+    if isinstance(x, _Tensor):      # (a subclass: a Parameter, engine.KinRows)
+        return ctypes.c_void_p(x.data_ptr())
+    return x
+
+
+def call(name: str, device, stream, *args, allow=(), what: str = None) -> int:
+    """`lib().<name>(*args, stream)` with `device` current (None: whatever is), the arguments converted by `as_c`; raises GpdError
+    (naming `what`, by default the entry) unless the entry returns 0 or a code in `allow`, which is returned."""
+    fn = getattr(lib(), name)
+    argv = [a if type(a) in _AS_IS else as_c(a) for a in args]
+    if stream is not NO_STREAM:
+        argv.append(stream)
+    with device_guard(device):
+        rc = fn(*argv)
+    if rc and rc not in allow:
+        check(rc, what or name)
+    return rc

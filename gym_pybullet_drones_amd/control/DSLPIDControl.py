@@ -8,26 +8,14 @@ lives in a [9][ld] float32 block: in HBM for the batch class, in page-locked hos
 device addresses directly for the single-drone class, whose call is then ONE library call (`gpd_pid_sync`:
 the launch and the wait for it; inputs written and outputs read by the host in place; no copies).
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _native
+from ..engine import as_f32, resolve_device, zeros
 from ..params import MIXER, PIDGains
 from ..utils.enums import ActionType, DroneModel
 from .BaseControl import BaseControl
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _f32(x, n, k, device):
-    if x is None:
-        return None
-    t = torch.as_tensor(np.asarray(x, dtype=np.float32) if not torch.is_tensor(x) else x, dtype=torch.float32, device=device)
-    return t.reshape(n, k).contiguous()
 
 
 class DSLPIDControlBatch(BaseControl):
@@ -38,11 +26,7 @@ class DSLPIDControlBatch(BaseControl):
         if drone_model not in (DroneModel.CF2X, DroneModel.CF2P):
             raise ValueError("[ERROR] in DSLPIDControl.__init__(), DSLPIDControl requires DroneModel.CF2X or DroneModel.CF2P")
         self.lib = _native.lib()
-        if device is None:
-            if not torch.cuda.is_available():
-                raise _native.GpdError("DSLPIDControl runs on an MI355X only: no CUDA/HIP device available")
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
+        self.device = resolve_device(device, "DSLPIDControl")
         self.n = int(num_controllers)
         self.ld = (self.n + 63) // 64 * 64
         gains = PIDGains()
@@ -51,11 +35,7 @@ class DSLPIDControlBatch(BaseControl):
         self.PWM2RPM_SCALE, self.PWM2RPM_CONST = gains.PWM2RPM_SCALE, gains.PWM2RPM_CONST
         self.MIN_PWM, self.MAX_PWM = gains.MIN_PWM, gains.MAX_PWM
         self.MIXER_MATRIX = MIXER[drone_model].copy()
-        if host_visible:
-            with torch.cuda.device(self.device):
-                self._state = torch.zeros((9, self.ld), dtype=torch.float32).pin_memory()
-        else:
-            self._state = torch.zeros((9, self.ld), dtype=torch.float32, device=self.device)
+        self._state = zeros((9, self.ld), torch.float32, self.device, host_visible)
         super().__init__(drone_model=drone_model, g=g)
         self._coefficients_changed()
 
@@ -87,18 +67,14 @@ class DSLPIDControlBatch(BaseControl):
         """Batched control step -> (rpm [n,4], pos_e [n,3], yaw_e [n]) float32 device tensors."""
         n, dev = self.n, self.device
         self.control_counter += 1
-        pos, quat, vel = _f32(cur_pos, n, 3, dev), _f32(cur_quat, n, 4, dev), _f32(cur_vel, n, 3, dev)
-        tpos, trpy = _f32(target_pos, n, 3, dev), _f32(target_rpy, n, 3, dev)
-        tvel, trates = _f32(target_vel, n, 3, dev), _f32(target_rpy_rates, n, 3, dev)
+        pos, quat, vel = as_f32(cur_pos, n, 3, dev), as_f32(cur_quat, n, 4, dev), as_f32(cur_vel, n, 3, dev)
+        tpos, trpy = as_f32(target_pos, n, 3, dev), as_f32(target_rpy, n, 3, dev)
+        tvel, trates = as_f32(target_vel, n, 3, dev), as_f32(target_rpy_rates, n, 3, dev)
         rpm = torch.empty((n, 4), dtype=torch.float32, device=dev)
         pos_e = torch.empty((n, 3), dtype=torch.float32, device=dev)
         yaw_e = torch.empty((n,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = self.lib.gpd_pid(ctypes.byref(self._params), _ptr(self._state), self.ld, float(control_timestep),
-                                  _ptr(pos), _ptr(quat), _ptr(vel), _ptr(tpos), _ptr(trpy), _ptr(tvel), _ptr(trates),
-                                  _ptr(rpm), _ptr(pos_e), _ptr(yaw_e), n,
-                                  ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _native.check(rc, "gpd_pid")
+        _native.call("gpd_pid", dev, _native.raw_stream(dev), self._params, self._state, self.ld, float(control_timestep), pos, quat, vel,
+                     tpos, trpy, tvel, trates, rpm, pos_e, yaw_e, n)
         return rpm, pos_e, yaw_e
 
 
@@ -110,12 +86,10 @@ class DSLPIDControl(DSLPIDControlBatch):
 
     def __init__(self, drone_model: DroneModel, g: float = 9.8, device=None):
         super().__init__(1, drone_model=drone_model, g=g, device=device, host_visible=True)
-        with torch.cuda.device(self.device):
-            self._io_t = torch.zeros((self._IO_FLOATS,), dtype=torch.float32).pin_memory()
+        self._io_t = zeros((self._IO_FLOATS,), torch.float32, self.device, host_visible=True)
         self._io = self._io_t.numpy()
-        base = self._io_t.data_ptr()
-        at = lambda off: ctypes.c_void_p(base + 4 * off)      # noqa: E731
-        self._pid_args = (_ptr(self._state), self.ld, at(self._POS), at(self._QUAT), at(self._VEL), at(self._TPOS), at(self._TRPY),
+        at = lambda off: _native.as_c(self._io_t[off:])      # noqa: E731
+        self._pid_args = (_native.as_c(self._state), self.ld, at(self._POS), at(self._QUAT), at(self._VEL), at(self._TPOS), at(self._TRPY),
                           at(self._TVEL), at(self._TRATES), at(self._RPM), at(self._POS_E), at(self._YAW_E))
 
     def _member(self, row):
@@ -138,10 +112,11 @@ class DSLPIDControl(DSLPIDControlBatch):
         io[self._TRPY:self._TRPY + 3] = target_rpy
         io[self._TVEL:self._TVEL + 3] = target_vel
         io[self._TRATES:self._TRATES + 3] = target_rpy_rates
-        with torch.cuda.device(self.device):        # ONE library call: the launch and the wait for it (include/gpd.h: gpd_pid_sync)
-            rc = self.lib.gpd_pid_sync(ctypes.byref(self._params), a[0], a[1], float(control_timestep), a[2], a[3], a[4], a[5], a[6], a[7], a[8],
-                                       a[9], a[10], a[11], 1, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _native.check(rc, "gpd_pid_sync")
+        with _native.device_guard(self.device):     # ONE library call: the launch and the wait for it (include/gpd.h: gpd_pid_sync)
+            rc = self.lib.gpd_pid_sync(_native.as_c(self._params), a[0], a[1], float(control_timestep), a[2], a[3], a[4], a[5], a[6], a[7], a[8],
+                                       a[9], a[10], a[11], 1, _native.raw_stream(self.device))
+        if rc:
+            _native.check(rc, "gpd_pid_sync")
         out = io.astype(np.float64)
         return out[self._RPM:self._RPM + 4], out[self._POS_E:self._POS_E + 3], float(out[self._YAW_E])
 
@@ -180,10 +155,7 @@ def pid_rpm_for_action(env, action, act_type=None):
         elif act_type == ActionType.ONE_D_PID:
             tpos[k] = pos[k] + 0.1 * np.array([0, 0, a[0]])
     rpm = torch.empty((n, 4), dtype=torch.float32, device=dev)
-    args = [_f32(x, n, k, dev) for x, k in ((pos, 3), (quat, 4), (vel, 3), (tpos, 3), (trpy, 3), (tvel, 3))]
-    with torch.cuda.device(dev):
-        rc = core.lib.gpd_pid(ctypes.byref(core._params), _ptr(core.pid), core.ld, float(env.CTRL_TIMESTEP),
-                              *[_ptr(a) for a in args], _ptr(None), _ptr(rpm), _ptr(None), _ptr(None), n,
-                              ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    _native.check(rc, "gpd_pid")
+    args = [as_f32(x, n, k, dev) for x, k in ((pos, 3), (quat, 4), (vel, 3), (tpos, 3), (trpy, 3), (tvel, 3))]
+    _native.call("gpd_pid", dev, _native.raw_stream(dev), core._params, core.pid, core.ld, float(env.CTRL_TIMESTEP), *args, None, rpm,
+                 None, None, n)
     return rpm.cpu().numpy().astype(np.float64)

@@ -10,12 +10,11 @@ imported lazily, here only: the rest of the package imports without it.
 
 Controller state per controller: 76 floats `[76][ld]` -- Kx (12 x 4) | Kr (4 x 4) | Xm (12) -- and an int32 call counter.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _native
+from ..engine import as_f32, resolve_device, zeros
 from ..params import MIXER
 from ..utils.enums import DroneModel
 from .BaseControl import BaseControl
@@ -23,10 +22,6 @@ from .BaseControl import BaseControl
 #: the reference's constants (`:30-33`, `:142`)
 PWM2RPM_SCALE, PWM2RPM_CONST, MIN_PWM, MAX_PWM, MAX_TORQUE = 0.2685, 4070.3, 20000, 65535, 3200.0
 _MODELS = (DroneModel.CF2X, DroneModel.CF2P, DroneModel.RACE)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
 def mixer_matrix(drone_model: DroneModel) -> np.ndarray:
@@ -99,18 +94,14 @@ class VectorMRAC(BaseControl):
         if drone_model not in _MODELS:
             raise ValueError("[ERROR] MRAC requires DroneModel.CF2X or DroneModel.CF2P or DroneModel.RACE")
         self.lib = _native.lib()
-        if device is None:
-            if not torch.cuda.is_available():
-                raise _native.GpdError("MRAC runs on an MI355X only: no CUDA/HIP device available")
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
+        self.device = resolve_device(device, "MRAC")
         self.n = int(num)
         if self.n < 1:
             raise ValueError("VectorMRAC: num must be >= 1")
         self.ld = (self.n + 63) // 64 * 64
         self.host_visible = bool(host_visible)
-        self.state = self._buf((_native.MRAC_STATE, self.ld), torch.float32)
-        self.counter = self._buf((self.ld,), torch.int32)
+        self.state = zeros((_native.MRAC_STATE, self.ld), torch.float32, self.device, self.host_visible)
+        self.counter = zeros((self.ld,), torch.int32, self.device, self.host_visible)
         super().__init__(drone_model=drone_model, g=g)
         self.Ixx, self.Iyy, self.Izz = (self._getURDFParameter(k) for k in ("ixx", "iyy", "izz"))
         self.J = np.diag([self.Ixx, self.Iyy, self.Izz])
@@ -123,12 +114,6 @@ class VectorMRAC(BaseControl):
         self._gamma = [float(gamma), float(gamma)]
         self._struct = None
         self.reset(gains=True)
-
-    def _buf(self, shape, dtype):
-        if self.host_visible:
-            with torch.cuda.device(self.device):
-                return torch.zeros(shape, dtype=dtype).pin_memory()
-        return torch.zeros(shape, dtype=dtype, device=self.device)
 
     # ---- the design's constants ---------------------------------------------------------------------------------------------
     def struct(self) -> "_native.GpdMrac":
@@ -147,9 +132,6 @@ class VectorMRAC(BaseControl):
     def Gamma_r(self, value):
         self._gamma[1], self._struct = _scalar_of_identity(value, 4, "Gamma_r"), None
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     # ---- BaseControl surface ------------------------------------------------------------------------------------------------
     def reset(self, mask=None, gains: bool = False):
         """The reference's `reset()` (`:106-107`): the call counters (of the controllers in the bool/uint8 `mask` [n]; None: all) go
@@ -161,10 +143,8 @@ class VectorMRAC(BaseControl):
             mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.uint8).contiguous()
             if mask.numel() != self.n:
                 raise ValueError(f"VectorMRAC.reset: mask has {mask.numel()} elements, expected {self.n}")
-        with torch.cuda.device(self.device):
-            rc = self.lib.gpd_mrac_reset(_ptr(self.state), _ptr(self.counter), self.ld, ctypes.byref(self.struct()), _ptr(mask), self.n,
-                                         int(bool(gains)), self._stream())
-        _native.check(rc, "gpd_mrac_reset")
+        _native.call("gpd_mrac_reset", self.device, _native.raw_stream(self.device), self.state, self.counter, self.ld, self.struct(), mask,
+                     self.n, int(bool(gains)))
 
     @property
     def control_counter(self):
@@ -195,26 +175,18 @@ class VectorMRAC(BaseControl):
                     raise ValueError(f"VectorMRAC.set_state: shape {tuple(src.shape)}, expected {tuple(dst.shape)}")
                 dst.copy_(src.to(dst.dtype))
 
-    def _f32(self, x, k):
-        if x is None:
-            return None
-        t = torch.as_tensor(np.asarray(x, dtype=np.float32) if not torch.is_tensor(x) else x, dtype=torch.float32, device=self.device)
-        return t.reshape(self.n, k).contiguous()
-
     def compute(self, control_timestep, cur_pos, cur_quat, cur_vel, cur_ang_vel, target_pos, target_rpy=None, target_vel=None,
                 target_rpy_rates=None):
         """Batched `computeControl` -> `(rpm [n, 4], pos_e [n, 3], rpy_e [n, 3])` float32 device tensors; asynchronous on the
         current stream, capturable in a hipGraph when every input is a contiguous float32 device tensor already."""
         n, dev = self.n, self.device
-        a = [self._f32(x, k) for x, k in ((cur_pos, 3), (cur_quat, 4), (cur_vel, 3), (cur_ang_vel, 3), (target_pos, 3), (target_rpy, 3),
+        a = [as_f32(x, n, k, dev) for x, k in ((cur_pos, 3), (cur_quat, 4), (cur_vel, 3), (cur_ang_vel, 3), (target_pos, 3), (target_rpy, 3),
                                           (target_vel, 3), (target_rpy_rates, 3))]
         rpm = torch.empty((n, 4), dtype=torch.float32, device=dev)
         pos_e = torch.empty((n, 3), dtype=torch.float32, device=dev)
         rpy_e = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = self.lib.gpd_mrac(ctypes.byref(self.struct()), _ptr(self.state), _ptr(self.counter), self.ld, float(control_timestep),
-                                   *[_ptr(t) for t in a], _ptr(rpm), _ptr(pos_e), _ptr(rpy_e), n, self._stream())
-        _native.check(rc, "gpd_mrac")
+        _native.call("gpd_mrac", dev, _native.raw_stream(dev), self.struct(), self.state, self.counter, self.ld, float(control_timestep), *a,
+                     rpm, pos_e, rpy_e, n)
         return rpm, pos_e, rpy_e
 
     computeControl = compute
@@ -233,11 +205,10 @@ class MRAC(VectorMRAC):
             print("[ERROR] MRAC requires DroneModel.CF2X or DroneModel.CF2P or DroneModel.RACE")
             exit()
         super().__init__(1, drone_model=drone_model, device=device, g=g, host_visible=True)
-        with torch.cuda.device(self.device):
-            self._io_t = torch.zeros((self._IO_FLOATS,), dtype=torch.float32).pin_memory()
+        self._io_t = zeros((self._IO_FLOATS,), torch.float32, self.device, host_visible=True)
         self._io = self._io_t.numpy()
-        at = lambda off: ctypes.c_void_p(self._io_t.data_ptr() + 4 * off)      # noqa: E731
-        self._args = [at(o) for o in (self._POS, self._QUAT, self._VEL, self._ANGV, self._TPOS, self._TRPY, self._TVEL, self._TRATES,
+        at = lambda off: _native.as_c(self._io_t[off:])      # noqa: E731
+        self._args = [_native.as_c(self.state), _native.as_c(self.counter)] + [at(o) for o in (self._POS, self._QUAT, self._VEL, self._ANGV, self._TPOS, self._TRPY, self._TVEL, self._TRATES,
                                       self._RPM, self._POS_E, self._RPY_E)]
 
     def _wait(self):
@@ -283,10 +254,11 @@ class MRAC(VectorMRAC):
                           (self._TRATES, target_rpy_rates, 3)):
             io[off:off + k] = v
         a = self._args
-        with torch.cuda.device(self.device):
-            rc = self.lib.gpd_mrac(ctypes.byref(self.struct()), _ptr(self.state), _ptr(self.counter), self.ld, float(control_timestep),
-                                   a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], 1, self._stream())
-        _native.check(rc, "gpd_mrac")
+        with _native.device_guard(self.device):
+            rc = self.lib.gpd_mrac(_native.as_c(self.struct()), a[0], a[1], self.ld, float(control_timestep),
+                                   a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12], 1, _native.raw_stream(self.device))
+        if rc:
+            _native.check(rc, "gpd_mrac")
         self._wait()
         out = io.astype(np.float64)
         return out[self._RPM:self._RPM + 4], out[self._POS_E:self._POS_E + 3], out[self._RPY_E:self._RPY_E + 3]

@@ -20,6 +20,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import _native
+
 
 def env_shard(total_envs: int, rank: int, world_size: int):
     """Contiguous block [start, stop) of envs owned by `rank` (sizes differ by at most one; hand
@@ -119,8 +121,6 @@ class NativeComm:
     _shared = None
 
     def __init__(self, device=None, group=None):
-        from . import _native
-        self._native = _native
         self.lib = _native.lib()
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -129,13 +129,13 @@ class NativeComm:
         blob = [None]
         self.comm = None
         self.group = group
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device):        # (held over the broadcast too)
             if self.rank == 0:
                 # a failure here (no RCCL on this box) must still reach the other ranks, which sit in the broadcast below:
                 # rank 0 broadcasts the error text instead of the id and EVERY rank raises (callers then agree on a
                 # fallback with all_ranks_ok instead of dead-locking between a broadcast and an all-reduce)
                 try:
-                    _native.check(self.lib.gpd_comm_unique_id(ident), "gpd_comm_unique_id")
+                    _native.call("gpd_comm_unique_id", None, _native.NO_STREAM, ident)
                     blob[0] = bytes(ident)
                 except Exception as e:      # noqa: BLE001
                     blob[0] = f"rank 0: {type(e).__name__}: {e}"
@@ -145,10 +145,10 @@ class NativeComm:
                 raise _native.GpdError(blob[0])
             ident = (ctypes.c_uint8 * _native.COMM_ID_BYTES).from_buffer_copy(blob[0])
             comm = ctypes.c_void_p()
-            _native.check(self.lib.gpd_comm_init(ctypes.byref(comm), ident, self.rank, self.world), "gpd_comm_init")
+            _native.call("gpd_comm_init", None, _native.NO_STREAM, ctypes.byref(comm), ident, self.rank, self.world)
             self.comm = comm
         n = ctypes.c_int32(0)
-        _native.check(self.lib.gpd_comm_count(self.comm, ctypes.byref(n)), "gpd_comm_count")
+        _native.call("gpd_comm_count", None, _native.NO_STREAM, self.comm, n)
         self.ranks_seen = int(n.value)              # what RCCL itself says the communicator spans (ncclCommCount)
 
     @classmethod
@@ -184,7 +184,7 @@ class NativeObsAllGather:
 
     def __init__(self, shard_rows: int, cols: int = 12, device=None, group=None, comm: "NativeComm" = None):
         self.nc = comm if comm is not None else NativeComm.shared(device=device, group=group)
-        self._native, self.lib = self.nc._native, self.nc.lib
+        self.lib = self.nc.lib
         self.world, self.rank, self.device = self.nc.world, self.nc.rank, self.nc.device
         self.cols = cols
         self.count = int(shard_rows) * cols
@@ -203,10 +203,7 @@ class NativeObsAllGather:
     def __call__(self, shard: torch.Tensor):
         if shard.numel() != self.count or shard.dtype != torch.float32 or not shard.is_contiguous():
             raise ValueError(f"shard must be a contiguous float32 tensor of {self.count} elements")
-        with torch.cuda.device(self.device):
-            rc = self.lib.gpd_allgather_obs(self.nc.comm, ctypes.c_void_p(shard.data_ptr()), ctypes.c_void_p(self.full.data_ptr()),
-                                            self.count, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        self._native.check(rc, "gpd_allgather_obs")
+        _native.call("gpd_allgather_obs", self.device, _native.raw_stream(self.device), self.nc.comm, shard, self.full, self.count)
         return self.full
 
     def close(self):

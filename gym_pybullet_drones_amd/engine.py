@@ -34,18 +34,34 @@ def action_needs_fix(a, device):
     return a.device != device or a.dtype != torch.float32 or not a.is_contiguous()
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+def resolve_device(device, who: str, strict: bool = False) -> torch.device:
+    """`device`, or torch's current HIP device for None; GpdError (in `who`'s name) when there is none.  `strict` (SimCore): anything
+    but a HIP device is refused as well, and a bare "cuda" becomes the current index."""
+    if device is None and torch.cuda.is_available():
+        device = torch.device("cuda", torch.cuda.current_device())
+    if device is None or (strict and torch.device(device).type != "cuda"):
+        raise _native.GpdError(f"{who} runs on an MI355X only: no CUDA/HIP device available" + (" (there is no CPU fallback)" if strict else ""))
+    device = torch.device(device)
+    if strict and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
 
 
-_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+def zeros(shape, dtype, device, host_visible: bool = False) -> torch.Tensor:
+    """a zeroed buffer the kernels read and write: HBM, or (host_visible) page-locked host memory mapped into the device's
+    address space (hipHostMalloc through torch's pinned allocator: the host pointer IS the device pointer)"""
+    if host_visible:
+        with torch.cuda.device(device):
+            return torch.zeros(shape, dtype=dtype).pin_memory()
+    return torch.zeros(shape, dtype=dtype, device=device)
 
 
-def _raw_stream(device) -> int:
-    """hipStream_t of torch's current stream on `device` (the accessor torch's own compiled kernels use: no Stream object per call)"""
-    if _get_raw_stream is not None and device.index is not None:
-        return _get_raw_stream(device.index)
-    return torch.cuda.current_stream(device).cuda_stream
+def as_f32(x, n: int, k: int, device):
+    """a controller's operand as a contiguous float32 `[n, k]` tensor on `device` (None stays None)"""
+    if x is None:
+        return None
+    t = torch.as_tensor(np.asarray(x, dtype=np.float32) if not torch.is_tensor(x) else x, dtype=torch.float32, device=device)
+    return t.reshape(n, k).contiguous()
 
 
 #: MI355X: 256 CUs x 4 SIMDs
@@ -118,14 +134,7 @@ class SimCore:
         if pyb_freq % ctrl_freq != 0:
             raise ValueError("[ERROR] pyb_freq is not divisible by ctrl_freq.")
         self.lib = _native.lib()                      # raises if the HIP extension is missing
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
-        if device is None or torch.device(device).type != "cuda":
-            raise _native.GpdError("the simulator's hot path runs on an MI355X only: no CUDA/HIP device available "
-                                   "(there is no CPU fallback)")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = resolve_device(device, "the simulator's hot path", strict=True)
         self._dev_index = self.device.index
         self.E, self.D = int(num_envs), int(drones_per_env)
         self.N = self.E * self.D
@@ -150,13 +159,10 @@ class SimCore:
         dev, f32 = self.device, torch.float32
         self.host_visible = bool(host_visible)
 
+        self._rollout_cache, self._rollout_buf, self._policy_actions = {}, None, {}
+
         def buf(shape, dtype=f32):
-            """a zeroed buffer the kernels read and write: HBM, or (host_visible) page-locked host memory mapped into the device's
-            address space (hipHostMalloc through torch's pinned allocator: the host pointer IS the device pointer)"""
-            if self.host_visible:
-                with torch.cuda.device(dev):
-                    return torch.zeros(shape, dtype=dtype).pin_memory()
-            return torch.zeros(shape, dtype=dtype, device=dev)
+            return zeros(shape, dtype, dev, self.host_visible)
 
         self.kin_store = buf((13 * self.ld,))
         ld = self.ld
@@ -229,12 +235,15 @@ class SimCore:
     def _stream(self):
         if self._own_stream is not None:
             return self._own_stream
-        return ctypes.c_void_p(_raw_stream(self.device))
+        return ctypes.c_void_p(_native.raw_stream(self.device))
 
+    #: optional parts (None / 0 until `enable_history()`)
+    act_ring = ring_pos = obs_full = _full_buf = None
+    H = 0
     _own_stream = None
     _pinned = None
     _host_args = None
-    _step_args = None       # the arguments of gpd_step that never change between two calls, as ctypes objects (built on first use)
+    _step_args = None       # `_fixed_args()`, built on first use
 
     def use_stream(self, stream: "torch.cuda.Stream" = None):
         """Pin every launch of this core to `stream` (None: back to torch's current stream).  For independent batches that
@@ -253,10 +262,8 @@ class SimCore:
         self.state_version += 1
         if mask is not None:
             mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
-            rc = self.lib.gpd_reset(ctypes.byref(self._state), _ptr(self.init_pose), self.init_per_env, _ptr(mask),
-                                    self.E, self.D, int(reset_pid), _ptr(self.obs12), self._stream())
-        _native.check(rc, "gpd_reset")
+        _native.call("gpd_reset", self.device, self._stream(), self._state, self.init_pose, self.init_per_env, mask, self.E, self.D,
+                     int(reset_pid), self.obs12)
         if self.mrac_rpm is not None:     # (an MRAC rollout of a reset aviary starts from zero RPMs, as the reference's loop does)
             with torch.cuda.stream(self._pinned) if self._pinned is not None else contextlib.nullcontext():
                 if mask is None:
@@ -289,14 +296,14 @@ class SimCore:
         if a is None:
             if not self.host_visible:
                 raise ValueError("step_host() needs a core built with host_visible=True")
-            a = self._host_args = (ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg), _ptr(self.action_host),
-                                   _ptr(self.target), _ptr(self.init_pose), _ptr(self.obs12), _ptr(self.reward), _ptr(self.terminated),
-                                   _ptr(self.truncated), _ptr(self.term_obs12), self.lib.gpd_step_sync)
-        if self._own_stream is not None or _get_raw_stream is None or torch.cuda.current_device() != self._dev_index:
+            a = self._host_args = tuple(_native.as_c(x) for x in (self._params, self._state, self._cfg, self.action_host, self.target,
+                                                                  self.init_pose, self.obs12, self.reward, self.terminated,
+                                                                  self.truncated, self.term_obs12)) + (self.lib.gpd_step_sync,)
+        if self._own_stream is not None or _native._get_raw_stream is None or torch.cuda.current_device() != self._dev_index:
             self.step(self.action_host)
             return
         self.state_version += 1
-        rc = a[11](a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], _get_raw_stream(self._dev_index))
+        rc = a[11](a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], _native._get_raw_stream(self._dev_index))
         if rc:
             _native.check(rc, "gpd_step_sync")
 
@@ -341,11 +348,7 @@ class SimCore:
         if self.plant_rows is not None:
             self._plant_step(action)
             return self.obs12, self.reward, self.terminated, self.truncated
-        a = self._step_args
-        if a is None:
-            a = self._step_args = (ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg),
-                                   _ptr(self.target), _ptr(self.init_pose), _ptr(self.obs12), _ptr(self.reward),
-                                   _ptr(self.terminated), _ptr(self.truncated), _ptr(self.term_obs12))
+        a = self._step_args or self._fixed_args()
         if torch.cuda.current_device() == self._dev_index:
             rc = self.lib.gpd_step(a[0], a[1], a[2], ctypes.c_void_p(action.data_ptr()), a[3], a[4], a[5], a[6], a[7], a[8], a[9],
                                    self._stream())
@@ -397,35 +400,43 @@ class SimCore:
             o_stride, e_stride = self.N * 12, self.E
         self.pushed_history = False
         self.state_version += 1
-        with torch.cuda.device(self.device):
-            if self.plant_rows is not None:       # (the per-drone plant: gpd_rollout_plant; a history is pushed by full_obs())
-                rc = self.lib.gpd_rollout_plant(ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg),
-                                                K, _ptr(actions), a_stride, _ptr(self.target), _ptr(self.init_pose),
-                                                _ptr(obs), o_stride, _ptr(rew), _ptr(term), _ptr(trunc), e_stride,
-                                                _ptr(tobs), _ptr(self.plant_rows), self._stream())
-                _native.check(rc, "gpd_rollout_plant")
-            elif push_history and getattr(self, "act_ring", None) is not None and tobs is None:
-                # the kernel pushes every step's action into the ring itself (`gpd_rollout_history`)
-                rc = self.lib.gpd_rollout_history(ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg),
-                                                  K, _ptr(actions), a_stride, _ptr(self.target), _ptr(self.init_pose),
-                                                  _ptr(obs), o_stride, _ptr(rew), _ptr(term), _ptr(trunc), e_stride, self._stream())
-                if rc != _native.GPD_ENOTSUP:     # only "no fused variant for this shape" falls through (nothing was launched);
-                    _native.check(rc, "gpd_rollout_history")     # a real failure must not be retried on an already advanced state
-                    self.pushed_history = True
-            if not self.pushed_history and self.plant_rows is None:   # (no fused variant: the caller updates the ring with full_obs())
-                rc = self.lib.gpd_rollout(ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg),
-                                          K, _ptr(actions), a_stride, _ptr(self.target), _ptr(self.init_pose),
-                                          _ptr(obs), o_stride, _ptr(rew), _ptr(term), _ptr(trunc), e_stride,
-                                          _ptr(tobs), self._stream())
-                _native.check(rc, "gpd_rollout")
+        launch = (K, actions, a_stride, obs, o_stride, rew, term, trunc, e_stride, tobs)
+        if self.plant_rows is not None:           # (the per-drone plant: gpd_rollout_plant; a history is pushed by full_obs())
+            self._launch_rollout("gpd_rollout_plant", *launch, extra=(self.plant_rows,))
+        else:
+            if push_history and self.act_ring is not None and tobs is None:
+                # the kernel pushes every step's action into the ring itself (`gpd_rollout_history`).  Only "no fused variant for
+                # this shape" falls through (nothing was launched); a real failure must not be retried on an already advanced state
+                self.pushed_history = self._launch_rollout("gpd_rollout_history", *launch, allow=(_native.GPD_ENOTSUP,)) == 0
+            if not self.pushed_history:           # (no fused variant: the caller updates the ring with full_obs())
+                self._launch_rollout("gpd_rollout", *launch)
         if not last_only and update_latest:
-            self.obs12.copy_(obs[K - 1])
-            self.reward.copy_(rew[K - 1])
-            self.terminated.copy_(term[K - 1])
-            self.truncated.copy_(trunc[K - 1])
+            self._publish_latest(obs, rew, term, trunc, K)
             if tobs is not None and self.auto_reset:      # term_obs12 = what K single steps would have left
                 self._latest_terminal(tobs, term, trunc, K)
         return obs, rew, term, trunc
+
+    def _fixed_args(self):
+        """the arguments of gpd_step / gpd_rollout* that never change between two calls, as ctypes objects (set_target() drops them)"""
+        self._step_args = tuple(_native.as_c(x) for x in (self._params, self._state, self._cfg, self.target, self.init_pose, self.obs12,
+                                                          self.reward, self.terminated, self.truncated, self.term_obs12))
+        return self._step_args
+
+    def _launch_rollout(self, entry, K, actions, a_stride, obs, o_stride, rew, term, trunc, e_stride, tobs, extra=(), allow=()):
+        """One launch of a `gpd_rollout*` entry: the argument list they share, then `extra` (gpd_rollout_history has no
+        terminal-observation output: `tobs` is None there and is not passed).  The structs and the two fixed tables come pre-built,
+        as in step(): an eager loop of 20-step rollouts has this call next to its critical path (scratch/host_overhead.py)."""
+        a = self._step_args or self._fixed_args()
+        tail = () if entry == "gpd_rollout_history" else (tobs,)
+        return _native.call(entry, self.device, self._stream(), a[0], a[1], a[2], K, actions, a_stride, a[3], a[4], obs, o_stride, rew,
+                            term, trunc, e_stride, *tail, *extra, allow=allow)
+
+    def _publish_latest(self, obs, rew, term, trunc, K):
+        """the last step of a K-step block into the latest-step tensors (on torch's current stream)"""
+        self.obs12.copy_(obs[K - 1])
+        self.reward.copy_(rew[K - 1])
+        self.terminated.copy_(term[K - 1])
+        self.truncated.copy_(trunc[K - 1])
 
     def rollout_policy(self, policy, num_steps: int, want_actions: bool = True, noise: torch.Tensor = None, action_std=None,
                        mean_out: torch.Tensor = None):
@@ -460,7 +471,7 @@ class SimCore:
                                          or mean_out.numel() != K * self.N * self.A):
                 raise ValueError("mean_out must be a contiguous float32 tensor like noise")
         obs, rew, term, trunc, tobs = self._rollout_buffers(K)
-        cache = self.__dict__.setdefault("_policy_actions", {})
+        cache = self._policy_actions
         acts = None
         if want_actions:
             acts = cache.get(K)
@@ -469,18 +480,11 @@ class SimCore:
                 acts = cache[K] = torch.zeros((K, self.N, self.A), dtype=torch.float32, device=self.device)
         ps = policy.struct()
         self.state_version += 1
-        with torch.cuda.device(self.device):
-            rc = self.lib.gpd_rollout_policy(ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg),
-                                             ctypes.byref(ps), K, _ptr(self.obs12), _ptr(self.target), _ptr(self.init_pose),
-                                             _ptr(acts), _ptr(obs), self.N * 12, _ptr(rew), _ptr(term), _ptr(trunc), self.E,
-                                             _ptr(noise), std, _ptr(mean_out), _ptr(tobs), self._stream())
-        _native.check(rc, "gpd_rollout_policy")
+        _native.call("gpd_rollout_policy", self.device, self._stream(), self._params, self._state, self._cfg, ps, K, self.obs12,
+                     self.target, self.init_pose, acts, obs, self.N * 12, rew, term, trunc, self.E, noise, std, mean_out, tobs)
         if tobs is not None and self.auto_reset:       # (the kernel writes terminal rows only when it resets: K single steps of an
             self._latest_terminal(tobs, term, trunc, K)   # aviary without auto-reset leave term_obs12 untouched, and so does this)
-        self.obs12.copy_(obs[K - 1])
-        self.reward.copy_(rew[K - 1])
-        self.terminated.copy_(term[K - 1])
-        self.truncated.copy_(trunc[K - 1])
+        self._publish_latest(obs, rew, term, trunc, K)
         return obs, rew, term, trunc, acts
 
     #: [N, 4] the RPMs an MRAC rollout carries from one launch to the next (None until the first `rollout_mrac`)
@@ -501,7 +505,7 @@ class SimCore:
             raise ValueError("num_steps must be >= 1")
         if self.host_visible:
             raise ValueError("rollout_mrac: a host-visible core steps one aviary at a time (CtrlAviary.step + MRAC.computeControl)")
-        if getattr(self, "act_ring", None) is not None:
+        if self.act_ring is not None:
             raise ValueError("rollout_mrac: this core keeps an action history, which the fused rollout would not advance "
                              "(step() + VectorMRAC.compute() serve it)")
         if getattr(ctrl, "n", None) != self.N or ctrl.device != self.device or getattr(ctrl, "host_visible", False):
@@ -523,11 +527,8 @@ class SimCore:
         else:
             obs, o_stride = self._rollout_buffers(K)[0], self.N * 12
         self.state_version += 1
-        with torch.cuda.device(self.device):
-            rc = self.lib.gpd_rollout_mrac(ctypes.byref(self._params), ctypes.byref(ctrl.struct()), ctypes.byref(self._state),
-                                           ctypes.byref(self._cfg), _ptr(ctrl.state), _ptr(ctrl.counter), ctrl.ld, _ptr(t), t_stride,
-                                           _ptr(self.mrac_rpm), _ptr(self.plant_rows), _ptr(obs), o_stride, K, self._stream())
-        _native.check(rc, "gpd_rollout_mrac")
+        _native.call("gpd_rollout_mrac", self.device, self._stream(), self._params, ctrl.struct(), self._state, self._cfg, ctrl.state,
+                     ctrl.counter, ctrl.ld, t, t_stride, self.mrac_rpm, self.plant_rows, obs, o_stride, K)
         if not last_only:
             self.obs12.copy_(obs[K - 1])
         return obs
@@ -546,7 +547,7 @@ class SimCore:
     def terminal_observations(self, K: int) -> torch.Tensor:
         """`[K, N, 12]` terminal-observation block of the latest K-step `rollout()` / `rollout_policy()` (needs
         `keep_terminal_obs`): row (t, n) is meaningful where aviary n ended at step t."""
-        buf = self.__dict__.get("_rollout_cache", {}).get(int(K))
+        buf = self._rollout_cache.get(int(K))
         if buf is None or buf[4] is None:
             raise ValueError("no terminal observations: build with keep_terminal_obs=True and run a K-step rollout first")
         return buf[4]
@@ -559,8 +560,7 @@ class SimCore:
         self.H = int(hist_len)
         self.act_ring = torch.zeros((2 * self.H, self.N, self.A), dtype=torch.float32, device=self.device)
         self.ring_pos = torch.zeros((self.E,), dtype=torch.int32, device=self.device)
-        self.obs_full = None            # materialised rows, allocated on first request
-        self._full_buf = None
+        self.obs_full = self._full_buf = None       # materialised rows, allocated on first request
         self._state.act_ring = self.act_ring.data_ptr()
         self._state.ring_pos = self.ring_pos.data_ptr()
         self._state.hist_len = self.H
@@ -576,10 +576,8 @@ class SimCore:
         """Materialise the current full rows `[N, 12 + H*A]` (`gpd_hist_rows`: one gather kernel, no host sync)."""
         if self.obs_full is None:
             self.obs_full = torch.zeros((self.N, 12 + self.H * self.A), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gpd_hist_rows(ctypes.byref(self._state), self.N, self.D, self.A,
-                                        _ptr(self.obs12 if obs12 is None else obs12), _ptr(self.obs_full), self._stream())
-        _native.check(rc, "gpd_hist_rows")
+        _native.call("gpd_hist_rows", self.device, self._stream(), self._state, self.N, self.D, self.A,
+                     self.obs12 if obs12 is None else obs12, self.obs_full)
         return self.obs_full
 
     def full_obs(self, actions: torch.Tensor, obs12: torch.Tensor = None, num_steps: int = 1, want_rows: bool = True):
@@ -601,16 +599,13 @@ class SimCore:
             out = self._full_buf
             if obs12 is None:
                 obs12 = self._rollout_buf[0]
-        with torch.cuda.device(self.device):
-            rc = self.lib.gpd_full_obs(ctypes.byref(self._state), K, self.N, self.D, self.A,
-                                       _ptr(obs12) if want_rows else _ptr(None), self.N * 12, _ptr(actions), a_stride,
-                                       _ptr(out), self.N * W, self._stream())
-        _native.check(rc, "gpd_full_obs")
+        _native.call("gpd_full_obs", self.device, self._stream(), self._state, K, self.N, self.D, self.A, obs12 if want_rows else None,
+                     self.N * 12, actions, a_stride, out, self.N * W)
         return out
 
     def _rollout_buffers(self, K: int):
         """Persistent output buffers of a K-step rollout (kept per K: the four most recent lengths stay allocated)."""
-        cache = self.__dict__.setdefault("_rollout_cache", {})
+        cache = self._rollout_cache
         buf = cache.get(K)
         if buf is None:
             dev = self.device
@@ -656,10 +651,7 @@ class SimCore:
     def state_vectors(self) -> torch.Tensor:
         """[N,20] state vectors in `_getDroneStateVector` order (BaseAviary.py:559-561)."""
         out = torch.empty((self.N, 20), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gpd_state_vectors(ctypes.byref(self._state), _ptr(self.obs12), _ptr(out), self.N,
-                                            self._stream())
-        _native.check(rc, "gpd_state_vectors")
+        _native.call("gpd_state_vectors", self.device, self._stream(), self._state, self.obs12, out, self.N)
         return out
 
     def bad_envs(self) -> torch.Tensor:
@@ -736,23 +728,16 @@ class SimCore:
             torch.where(mask.view(1, self.E, 1).bool(), full, view, out=view)
         else:
             view.copy_(full)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gpd_plant_derive(ctypes.byref(self._params), _ptr(self.plant_scales), _ptr(None if first else mask), self.E,
-                                           self.D, self.ld, _ptr(self.plant_rows), self._stream())
-        _native.check(rc, "gpd_plant_derive")
+        _native.call("gpd_plant_derive", self.device, self._stream(), self._params, self.plant_scales, None if first else mask, self.E,
+                     self.D, self.ld, self.plant_rows)
 
     def _plant_step(self, action):
         """step() with a plant table: a one-step gpd_rollout_plant (the single-step kernel), then the action into the ring"""
-        with torch.cuda.device(self.device):
-            rc = self.lib.gpd_rollout_plant(ctypes.byref(self._params), ctypes.byref(self._state), ctypes.byref(self._cfg), 1,
-                                            _ptr(action), 0, _ptr(self.target), _ptr(self.init_pose), _ptr(self.obs12), 0,
-                                            _ptr(self.reward), _ptr(self.terminated), _ptr(self.truncated), 0, _ptr(self.term_obs12),
-                                            _ptr(self.plant_rows), self._stream())
-            _native.check(rc, "gpd_rollout_plant")
-            if getattr(self, "act_ring", None) is not None:       # (gpd_step pushes inside its kernel; the plant path after it)
-                rc = self.lib.gpd_full_obs(ctypes.byref(self._state), 1, self.N, self.D, self.A, _ptr(None), self.N * 12,
-                                           _ptr(action), 0, _ptr(None), 0, self._stream())
-                _native.check(rc, "gpd_full_obs")
+        self._launch_rollout("gpd_rollout_plant", 1, action, 0, self.obs12, 0, self.reward, self.terminated, self.truncated, 0,
+                             self.term_obs12, extra=(self.plant_rows,))
+        if self.act_ring is not None:             # (gpd_step pushes inside its kernel; the plant path after it)
+            _native.call("gpd_full_obs", self.device, self._stream(), self._state, 1, self.N, self.D, self.A, None, self.N * 12, action, 0,
+                         None, 0)
 
     # ---- checkpoint / resume (host <-> device copies, off the hot path) ------------------------------
     #: everything a later step can depend on: the integrator state, the controllers' members, the last applied RPMs (drag), the
@@ -817,7 +802,7 @@ class SimCore:
         if self.last_rpm is not None:
             per_drone += 4 * 4
         per_env = 4 + 2 + 2 * 4                                   # reward + 2 flags + counter r/w
-        if getattr(self, "act_ring", None) is not None:           # action pushed into both halves of the double ring
+        if self.act_ring is not None:                             # action pushed into both halves of the double ring
             per_drone += 2 * self.A * 4
             per_env += 2 * 4                                      # ring position r/w
         if self.plant_rows is not None:

@@ -27,8 +27,6 @@ Interface: `CtrlAviary`-like.  `step(action)` takes raw RPMs `(n_own, 4)` clippe
 GPU.  `neighbors(radius, k)` / `collisions()` tell a drone who is near it (`gpd_neighbors`: the same counting sort on
 `radius`-sized cells, then a k-nearest search; the reference's `_getAdjacencyMatrix`, `envs/BaseAviary.py:658-675`, at swarm size).
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -36,10 +34,6 @@ from .. import _native, engine, neighbors as _nb
 from ..control.DSLPIDControl import DSLPIDControlBatch
 from ..params import DroneParams
 from ..utils.enums import ACT_DIRECT_RPM, ACT_RAW_RPM, ActionType, DroneModel, PHYS_DW, Physics, warn_if_pyb
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
 def swarm_partition(num_drones: int, world_size: int):
@@ -71,10 +65,6 @@ def swarm_spatial_order(xyz, cell: float) -> np.ndarray:
     return np.lexsort((np.arange(len(xyz)), cxy[:, 0], cxy[:, 1]))
 
 
-import contextlib
-_NO_GUARD = contextlib.nullcontext()
-
-
 class TorchSlabExchange:
     """The all-gather of the ranks' position slabs through `torch.distributed` (RCCL with the "nccl" backend; with gloo the
     slabs are staged through host memory: CPU tests and the single-device test hook)."""
@@ -103,10 +93,7 @@ class NativeSlabExchange:
         self.nc = comm if comm is not None else NativeComm.shared(device=device)
 
     def __call__(self, pos4: torch.Tensor, rank: int, slab: int):
-        with torch.cuda.device(pos4.device):
-            rc = self.nc.lib.gpd_allgather_obs(self.nc.comm, ctypes.c_void_p(pos4.data_ptr() + rank * slab * 16), _ptr(pos4), slab * 4,
-                                               ctypes.c_void_p(torch.cuda.current_stream(pos4.device).cuda_stream))
-        _native.check(rc, "gpd_allgather_obs")
+        _native.call("gpd_allgather_obs", pos4.device, _native.raw_stream(pos4.device), self.nc.comm, pos4[rank * slab:], pos4, slab * 4)
 
 
 # ---- halo exchange: a rank's neighbours' border drones instead of every position -------------------------------------------
@@ -315,10 +302,8 @@ class NativeHaloExchange(_HaloExchange):
     def _allgather_small(self, t):
         out = torch.empty((self.nc.world, t.numel()), dtype=torch.float32, device=t.device)
         src = t.to(torch.float32).contiguous()
-        with torch.cuda.device(t.device):
-            rc = self.nc.lib.gpd_allgather_obs(self.nc.comm, _ptr(src), _ptr(out), src.numel(),
-                                               ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream))
-        _native.check(rc, "gpd_allgather_obs (halo plan)")
+        _native.call("gpd_allgather_obs", t.device, _native.raw_stream(t.device), self.nc.comm, src, out, src.numel(),
+                     what="gpd_allgather_obs (halo plan)")
         return out
 
     def _plan_changed(self, env):
@@ -328,10 +313,7 @@ class NativeHaloExchange(_HaloExchange):
 
     def _move(self, env):
         P = self.plan
-        with torch.cuda.device(env.device):
-            rc = self.nc.lib.gpd_p2p_group(self.nc.comm, self._S, len(P.sends), self._R, len(P.recvs),
-                                           ctypes.c_void_p(torch.cuda.current_stream(env.device).cuda_stream))
-        _native.check(rc, "gpd_p2p_group")
+        _native.call("gpd_p2p_group", env.device, _native.raw_stream(env.device), self.nc.comm, self._S, len(P.sends), self._R, len(P.recvs))
 
 
 class SwarmAviary:
@@ -489,33 +471,29 @@ class SwarmAviary:
     def _pack(self, vectors=None):
         """pos4 rows of this rank from the state block (after a reset / an outside change); the sort is stale afterwards"""
         c = self.core
-        with torch.cuda.device(self.device):
-            rc = c.lib.gpd_swarm_pack(ctypes.byref(c._state), ctypes.byref(self._sw), _ptr(c.obs12), _ptr(vectors), c._stream())
-        _native.check(rc, "gpd_swarm_pack")
+        _native.call("gpd_swarm_pack", self.device, c._stream(), c._state, self._sw, c.obs12, vectors)
         self._pos_version = c.state_version
         self._since_bin = self.rebin_every           # (forces a binning)
         if getattr(self.exchange, "halo", False):    # ... and a new halo plan that holds nothing against the jump
             self.exchange.plan.forget()
 
     def _refs(self):
-        """ctypes references of the four structs and the address of the observation block: built once (an eager sub-step is three
+        """references of the four structs and the address of the observation block: built once (an eager sub-step is three
         C calls; the host side of each is what an eager loop waits for)"""
-        r = self.__dict__.get("_ref_cache")
+        r = self._ref_cache
         if r is None:
             c = self.core
-            r = self._ref_cache = (ctypes.byref(c._params), ctypes.byref(c._state), ctypes.byref(c._cfg), ctypes.byref(self._sw), _ptr(c.obs12))
+            r = self._ref_cache = tuple(_native.as_c(x) for x in (c._params, c._state, c._cfg, self._sw, c.obs12))
         return r
 
-    def _guard(self):
-        """the device guard, or nothing when this world's device is the current one already"""
-        return _NO_GUARD if torch.cuda.current_device() == self.device.index else torch.cuda.device(self.device)
+    _ref_cache = None
 
     def _substep(self, rpm, vectors=None):
         c = self.core
         c.state_version += 1
         r = self._refs()
-        with self._guard():
-            rc = c.lib.gpd_swarm_step(r[0], r[1], r[2], r[3], _ptr(rpm), r[4], _ptr(vectors), c._stream())
+        with _native.device_guard(self.device):
+            rc = c.lib.gpd_swarm_step(r[0], r[1], r[2], r[3], _native.as_c(rpm), r[4], _native.as_c(vectors), c._stream())
         if rc:
             _native.check(rc, "gpd_swarm_step")
         self._pos_version = c.state_version          # (the kernel wrote the rank's new rows of pos4)
@@ -553,7 +531,7 @@ class SwarmAviary:
         c = self.core
         binned = False
         r = self._refs()
-        with self._guard():
+        with _native.device_guard(self.device):
             stream = c._stream()
             if self._since_bin >= self.rebin_every:
                 binned = True
@@ -722,11 +700,8 @@ class SwarmAviary:
         i32 = dict(dtype=torch.int32, device=self.device)
         count, start, order = torch.zeros(2 * (keys + 1), **i32), torch.zeros(keys + 1, **i32), torch.zeros(n, **i32)
         srt, out = torch.zeros((n, 4), dtype=torch.float32, device=self.device), torch.zeros(n, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = c.lib.gpd_downwash_global(ctypes.byref(c._params), _ptr(c.kin_store), c.ld, n, self.cell, self.x0, self.y0, self.nx, self.ny,
-                                           self.z0, self.zbin, self.nz, None, _ptr(count), _ptr(start), _ptr(order), _ptr(srt), _ptr(out),
-                                           None, None, None, c._stream())
-        _native.check(rc, "gpd_downwash_global")
+        _native.call("gpd_downwash_global", self.device, c._stream(), c._params, c.kin_store, c.ld, n, self.cell, self.x0, self.y0, self.nx,
+                     self.ny, self.z0, self.zbin, self.nz, None, count, start, order, srt, out, None, None, None)
         return out
 
     def close(self):

@@ -5,7 +5,6 @@ The reference has `BaseAviary._getAdjacencyMatrix()` (`envs/BaseAviary.py:658-67
 aviary on the host.  Here a drone gets the NUMBER of other drones closer than `radius` and the nearest `k` of them, ordered by
 (squared distance, row) -- ties go to the lower row, whatever the sort did -- as device tensors, with no host synchronisation.
 """
-import ctypes
 import math
 
 import torch
@@ -16,10 +15,6 @@ MAX_K = 32
 #: entries of the sort's scratch arrays (include/gpd.h: the grid has at most 65 536 cells, whatever the entry chooses)
 _KEYS = 65536
 _FLT_MAX = 3.4028234663852886e38
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
 def check_args(radius, k) -> tuple:
@@ -70,11 +65,8 @@ class WorldSearch:
     def __call__(self, pos4: torch.Tensor, stream) -> Neighbors:
         self._order, self._visit = self._visit, self._order
         o = self.out
-        with torch.cuda.device(self.device):
-            rc = _native.lib().gpd_neighbors(_ptr(pos4), self.n_rows, self.qf, self.qc, self.radius, self.k, 0, self.cell, *self.box,
-                                             _ptr(self._visit), _ptr(self._count), _ptr(self._start), _ptr(self._order),
-                                             _ptr(self._sorted), _ptr(o.count), _ptr(o.idx), _ptr(o.rel), None, stream)
-        _native.check(rc, "gpd_neighbors")
+        _native.call("gpd_neighbors", self.device, stream, pos4, self.n_rows, self.qf, self.qc, self.radius, self.k, 0, self.cell, *self.box,
+                     self._visit, self._count, self._start, self._order, self._sorted, o.count, o.idx, o.rel, None)
         return o
 
 
@@ -91,8 +83,6 @@ def aviary_query(pos4: torch.Tensor, num_envs: int, drones_per_env: int, radius,
     count = torch.empty((E, D), dtype=torch.int32, device=dev)
     relt = torch.empty((E, D, k, 4), dtype=torch.float32, device=dev) if rel else None
     adj = torch.empty((E, D, D), dtype=torch.uint8, device=dev) if want_adjacency else None
-    with torch.cuda.device(dev):
-        rc = _native.lib().gpd_neighbors(_ptr(pos4), E * D, 0, E * D, radius, k, D, 0.0, 0.0, 0.0, 0.0, 0.0, None, None, None, None, None,
-                                         _ptr(count), _ptr(idx), _ptr(relt), _ptr(adj), stream)
-    _native.check(rc, "gpd_neighbors")
+    _native.call("gpd_neighbors", dev, stream, pos4, E * D, 0, E * D, radius, k, D, 0.0, 0.0, 0.0, 0.0, 0.0, None, None, None, None, None,
+                 count, idx, relt, adj)
     return Neighbors(idx, count, relt), adj

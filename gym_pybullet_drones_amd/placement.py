@@ -70,8 +70,7 @@ class RolloutArena:
         rew = self._view(tail_off + p["rew"], "rew", torch.float32, (K, c.E))
         term = self._view(tail_off + p["term"], "term", torch.bool, (K, c.E))
         trunc = self._view(tail_off + p["trunc"], "trunc", torch.bool, (K, c.E))
-        cache = c.__dict__.setdefault("_rollout_cache", {})
-        cache[K] = (obs, rew, term, trunc, tobs)
+        c._rollout_cache[K] = (obs, rew, term, trunc, tobs)
         self.layout = (head_off, tail_off)
         return obs, rew, term, trunc
 

@@ -15,7 +15,7 @@ import torch
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, R)
 from gym_pybullet_drones_amd import _native  # noqa: E402
-from gym_pybullet_drones_amd.engine import _ptr  # noqa: E402
+from gym_pybullet_drones_amd._native import as_c as _ptr  # noqa: E402
 from gym_pybullet_drones_amd.envs import VectorAviary  # noqa: E402
 from gym_pybullet_drones_amd.utils.enums import ActionType  # noqa: E402
 

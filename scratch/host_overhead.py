@@ -34,3 +34,37 @@ t1 = time.perf_counter()
 torch.cuda.synchronize()
 t2 = time.perf_counter()
 print("SwarmAviary(65536): host time per eager step() %.2f us (incl. GPU drain %.2f us)" % ((t1 - t0) / n * 1e6, (t2 - t0) / n * 1e6))
+# the bindings off the eager step: one K = 20 rollout launch (the benchmark's eager loop; the host runs ahead of the GPU, so the
+# queue is drained between batches, outside the timed part), the host-visible drop-in step, the two single-drone controllers
+import numpy as np
+from gym_pybullet_drones_amd.control import DSLPIDControl, MRAC
+from gym_pybullet_drones_amd.envs import HoverAviary
+from gym_pybullet_drones_amd.utils.enums import DroneModel
+acts = torch.zeros((20, 4096, 1, 4), device="cuda:0")
+core.rollout(acts, update_latest=False)
+torch.cuda.synchronize()
+host = 0.0
+for _ in range(25):
+    t0 = time.perf_counter()
+    for _ in range(200): core.rollout(acts, update_latest=False)
+    host += time.perf_counter() - t0
+    torch.cuda.synchronize()
+print("host time per core.rollout(K=20, update_latest=False) %.2f us" % (host / 5000 * 1e6))
+
+
+def per_call(fn, n=5000, warm=200):
+    for _ in range(warm): fn()
+    t0 = time.perf_counter()
+    for _ in range(n): fn()
+    return (time.perf_counter() - t0) / n * 1e6
+
+
+hover = HoverAviary()
+hover.reset()
+a1 = np.zeros((1, 4), dtype=np.float32)
+print("HoverAviary().step() (host-visible, launch + wait) %.2f us" % per_call(lambda: hover.step(a1)))
+z3, q = np.zeros(3), np.array([0.0, 0.0, 0.0, 1.0])
+pid = DSLPIDControl(DroneModel.CF2X)
+print("DSLPIDControl.computeControl (single drone, launch + wait) %.2f us" % per_call(lambda: pid.computeControl(1 / 240, z3, q, z3, z3, z3)))
+mrac = MRAC(DroneModel.CF2X)
+print("MRAC.computeControl (single drone, launch + wait) %.2f us" % per_call(lambda: mrac.computeControl(1 / 240, z3, q, z3, z3, z3)))
