@@ -39,7 +39,7 @@ MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 HIPCC_FLAGS = COMMON_FLAGS + MAX_ILP + ["-shared"]        # (kept under this name for the ISA tests)
 UNITS = (("step_rollout.hip", MAX_ILP + KERNARG_PRELOAD), ("policy.hip", []), ("swarm.hip", MAX_ILP + KERNARG_PRELOAD), ("abi.hip", MAX_ILP), ("mrac.hip", MAX_ILP))
-HEADERS = ("gpd_common.inc", "policy_kernel.inc")
+HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc")
 
 
 class GpdError(RuntimeError):
@@ -197,6 +197,12 @@ _SIGNATURES = {
     "gpd_p2p_group": (ctypes.c_int, [_P, ctypes.POINTER(GpdP2P), ctypes.c_int32, ctypes.POINTER(GpdP2P), ctypes.c_int32, _P]),
     "gpd_debug_status": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int32, _P]),
     "gpd_clock_probe": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _P]),
+    # the differentiable rollout (diff.py): the taped forward, its reverse sweep, the tape's size
+    "gpd_rollout_tape_floats": (ctypes.c_int, [ctypes.POINTER(GpdStepCfg), ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "gpd_rollout_tape": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg), ctypes.c_int32, _P,
+                                        ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, _P]),
+    "gpd_rollout_vjp": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdStepCfg), ctypes.c_int64, ctypes.c_int32, _P,
+                                       ctypes.c_int64, _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P]),
 }
 COMM_ID_BYTES = 128
 GPD_EINVAL, GPD_ERANGE, GPD_ENOTSUP = -1, -2, -3

@@ -600,3 +600,6 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
 
 }  // extern "C"
 
+// the differentiable rollout: gpd_rollout_tape_floats / gpd_rollout_tape / gpd_rollout_vjp and their kernels
+#include "diff_kernels.inc"
+

@@ -1,0 +1,465 @@
+// diff_kernels.inc -- the differentiable rollout (pulled into abi.hip; DESIGN.md section 3.12):
+//   gpd_rollout_tape_kernel   gpd_rollout / gpd_rollout_plant for single-drone aviaries -- the same load_carry / map_action / env_step /
+//                             substep / store_carry code, so the same bits -- that also records, per env step, the 13 kinematic floats
+//                             the step started from (the plane layout of GpdState.kin, 52 B per drone-step) and, once, the rpm sum the
+//                             drag term of the call's first sub-step saw;
+//   gpd_rollout_vjp_kernel    the hand-written reverse sweep: one lane per drone, steps K-1 .. 0.  Per step it reads the taped state, the
+//                             action row and the cotangent rows, re-runs the forward sub-steps from the taped state for each sub-step in
+//                             reverse (S(S+1)/2 recomputations, no scratch memory, no per-sub-step tape), pushes the adjoint through them
+//                             and writes the action gradient of the step.  No atomics: every output word has one writer.
+// The adjoint is that of the function AS EXECUTED: a select differentiates the branch taken (the `turn` test of the quaternion update,
+// the gimbal fix-up of quat_to_rpy, the clip of GPD_ACT_RAW_RPM, max(0, .) of the reward).  The cos / sinc polynomials of the quaternion
+// exponential are differentiated as the polynomials they are (the exact path beyond |t| = 1 rad as cos / sinc).
+namespace {
+
+__device__ __forceinline__ float norm_thrust_of(const GpdParams& P) { return P.hover_thrust; }
+__device__ __forceinline__ float norm_thrust_of(const PlantParams& P) { return P.norm_thrust; }
+
+// one drone's 13 floats from / to a block in the plane layout (GpdState.kin, a tape step, the cotangent block)
+__device__ __forceinline__ Kin planes_load(const float* __restrict__ base, int64_t ld, uint32_t n) {
+    const uint32_t off16 = n * 16u;
+    const f4v p = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(base) + off16);
+    const f4v q = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(base + 4 * ld) + off16);
+    const f4v v = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(base + 8 * ld) + off16);
+    Kin k;
+    k.px = p.x; k.py = p.y; k.pz = p.z; k.wx = p.w;
+    k.qx = q.x; k.qy = q.y; k.qz = q.z; k.qw = q.w;
+    k.vx = v.x; k.vy = v.y; k.vz = v.z; k.wy = v.w;
+    k.wz = ld_row(base, ld, 12, n * 4u);
+    return k;
+}
+__device__ __forceinline__ void planes_store(float* __restrict__ base, int64_t ld, uint32_t n, const Kin& k) {
+    const uint32_t off16 = n * 16u;
+    // (opaque copies, as in store_carry: the field reads must not be combined into vector loads of the struct)
+    float e0 = k.px, e1 = k.py, e2 = k.pz, e3 = k.wx, e4 = k.qx, e5 = k.qy, e6 = k.qz, e7 = k.qw, e8 = k.vx, e9 = k.vy, e10 = k.vz, e11 = k.wy;
+    asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3), "+v"(e4), "+v"(e5), "+v"(e6), "+v"(e7), "+v"(e8), "+v"(e9), "+v"(e10), "+v"(e11));
+    const f4v p = {e0, e1, e2, e3}, q = {e4, e5, e6, e7}, v = {e8, e9, e10, e11};
+    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(base) + off16) = p;
+    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(base + 4 * ld) + off16) = q;
+    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(base + 8 * ld) + off16) = v;
+    st_row(base, ld, 12, n * 4u, k.wz);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the taped forward: K env steps per launch, one lane per drone, state in registers
+// ------------------------------------------------------------------------------------------------
+template <bool EXT, int AW, bool PLANT>
+__global__ __launch_bounds__(kBlock) void gpd_rollout_tape_kernel(const GpdParams P, const GpdState S, const GpdStepCfg C, const int K, const int64_t a_stride,
+                                                                  const int64_t o_stride, const int64_t e_stride,
+                                                                  const float* __restrict__ actions, const float* __restrict__ target_pos,
+                                                                  float* __restrict__ obs12, float* __restrict__ reward,
+                                                                  uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated,
+                                                                  const float* __restrict__ plant, float* __restrict__ tape) {
+    const uint32_t N = static_cast<uint32_t>(C.num_envs);
+    const uint32_t n_raw = blockIdx.x * kBlock + threadIdx.x;
+    Lane L;
+    L.tid = threadIdx.x;
+    L.active = n_raw < N;
+    L.n = L.active ? n_raw : 0u;          // (a lane without a drone computes on drone 0 and stores nothing)
+    L.env = L.n; L.le = L.tid; L.d = 0; L.base = L.tid; L.shfl = false;
+    const uint32_t flags = EXT ? C.physics_flags : 0u;
+    const int64_t ld = S.ld;
+    Carry c;
+    float tgx, tgy, tgz;
+    load_carry<false, EXT, false>(S, C, flags, L, target_pos, nullptr, c, tgx, tgy, tgz, nullptr);
+    c.roll = c.pitch = c.yaw = 0.0f;
+    plant_t<PLANT> Q = plant_of<PLANT>(P, plant, ld, L.n * 4u);
+    // the rpm sum the drag term of the call's first sub-step sees: a constant of the reverse sweep (the same expression as env_step's)
+    if (L.active) tape[static_cast<int64_t>(K) * 13 * ld + L.n] = ((c.l0 + c.l1) + c.l2) + c.l3;
+    for (int t = 0; t < K; ++t, actions += a_stride, obs12 += o_stride, reward += e_stride, terminated += e_stride, truncated += e_stride,
+                            tape += 13 * ld) {
+        const float4 act = load_action<AW>(actions, L.n);
+        if (L.active) planes_store(tape, ld, L.n, c.k);
+        StepOut out;
+        env_step<false, EXT, false, AW>(Q, C, flags, 1, L, act, tgx, tgy, tgz, false, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f,
+                                        nullptr, nullptr, c, out);
+        if (L.active) {
+            store_obs12(obs12, L.n, out.o[0], out.o[1], out.o[2], out.o[3], out.o[4], out.o[5], out.o[6], out.o[7],
+                        out.o[8], out.o[9], out.o[10], out.o[11]);
+            reward[L.env] = out.rew;
+            terminated[L.env] = static_cast<uint8_t>(out.term ? 1 : 0);
+            truncated[L.env] = static_cast<uint8_t>(out.trunc ? 1 : 0);
+        }
+    }
+    if (L.active) store_carry<false>(S, L, c);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the reverse sweep
+// ------------------------------------------------------------------------------------------------
+// Adjoint of quat_to_rpy at (x, y, z, w): (gr, gp, gy) are the cotangents of roll / pitch / yaw, (ax, ay, az, aw) receive the quaternion's.
+// Both branches are evaluated and selected (a lane on the branch not taken may compute inf / NaN there, which the select discards):
+// a branch that writes through the references makes the caller's cotangent struct an indexed array in scratch memory.
+__device__ __forceinline__ void rpy_vjp(float x, float y, float z, float w, float gr, float gp, float gy,
+                                        float& ax, float& ay, float& az, float& aw) {
+    const float sarg = -2.0f * fmaf(x, z, -(w * y));             // (the expression quat_to_rpy tests)
+    const bool gimbal = fabsf(sarg) >= 0.99999f;
+    // gimbal branch: roll = 0, pitch = +-pi/2, yaw = 2 atan2(+-x, -+y): d yaw = 2 (x dy - y dx) / (x^2 + y^2) on both signs
+    const float inv = 2.0f * gy / fmaf(x, x, y * y);
+    const float a_s = 2.0f * gp * fast_rsq((1.0f - sarg) * (1.0f + sarg));      // pitch = asin(sarg), sarg = 2 (w y - x z)
+    const float ra = 2.0f * fmaf(y, z, w * x), rb = fmaf(w, w, z * z) - fmaf(x, x, y * y);     // roll = atan2(ra, rb)
+    const float ri = gr / fmaf(ra, ra, rb * rb);
+    const float a_ra = 2.0f * ri * rb, a_rb = -2.0f * ri * ra;
+    const float ya = 2.0f * fmaf(x, y, w * z), yb = fmaf(w, w, -(y * y)) + fmaf(x, x, -(z * z));   // yaw = atan2(ya, yb)
+    const float yi = gy / fmaf(ya, ya, yb * yb);
+    const float a_ya = 2.0f * yi * yb, a_yb = -2.0f * yi * ya;
+    const float rx = (a_ra * w - a_rb * x) + (a_ya * y + a_yb * x) - a_s * z;
+    const float ry = (a_ra * z - a_rb * y) + (a_ya * x - a_yb * y) + a_s * w;
+    const float rz = (a_ra * y + a_rb * z) + (a_ya * w - a_yb * z) - a_s * x;
+    const float rw = (a_ra * x + a_rb * w) + (a_ya * z + a_yb * w) + a_s * y;
+    ax = gimbal ? -(inv * y) : rx;
+    ay = gimbal ? inv * x : ry;
+    az = gimbal ? 0.0f : rz;
+    aw = gimbal ? 0.0f : rw;
+}
+
+// Adjoint of one physics sub-step (substep<> of gpd_common.inc, the terms this entry supports: thrust, torques, Euler's equation, drag,
+// semi-implicit Euler, the exponential quaternion update, the observed world angular velocity).
+//   k        the state the sub-step STARTED from (recomputed by the caller)
+//   a        in: cotangent of the state it left; out: cotangent of the state it started from
+//   b*       AV: cotangent of the observed world angular velocity (pre-update rotation, post-update rates)
+//   ag[4]    += cotangent of the rotor thrust deviations;   a_drag  += cotangent of the rpm sum the drag term saw
+template <bool EXT, bool AV>
+__device__ __forceinline__ void substep_vjp(const GpdParams& P, const float h, const uint32_t flags, const float g[4], const float drag_sum,
+                                            const Kin& k, Kin& a, const float bx, const float by, const float bz, float ag[4],
+                                            float& a_drag) {
+    const bool drag = EXT && (flags & GPD_PHYS_DRAG);
+    // ---- forward: what the reverse pass needs of it
+    const Mat3 R = quat_to_mat(k.qx, k.qy, k.qz, k.qw);
+    const float dev = ((g[0] + g[1]) + g[2]) + g[3];
+    const float T = P.GRAVITY + dev;
+    const float wsum = drag ? drag_sum * (6.28318530717958647692f / 60.0f) : 0.0f;
+    const float kz = (P.drone_model == GPD_MODEL_RACE) ? -P.km_over_kf : P.km_over_kf;
+    const float tz = kz * (((-g[0] + g[1]) - g[2]) + g[3]);
+    const float arm = P.L * 0.70710678118654752440f;
+    const float arm_x = (P.drone_model == GPD_MODEL_CF2X) ? -arm : arm;
+    const bool plus = P.drone_model == GPD_MODEL_CF2P;
+    const float tx = plus ? (g[1] - g[3]) * P.L : (((g[0] + g[1]) - g[2]) - g[3]) * arm_x;
+    const float ty = plus ? (-g[0] + g[2]) * P.L : (((-g[0] + g[1]) + g[2]) - g[3]) * arm;
+    const float jwx = P.J[0] * k.wx, jwy = P.J[1] * k.wy, jwz = P.J[2] * k.wz;
+    const float tqx = tx - fmaf(k.wy, jwz, -(k.wz * jwy));
+    const float tqy = ty - fmaf(k.wz, jwx, -(k.wx * jwz));
+    const float tqz = tz - fmaf(k.wx, jwy, -(k.wy * jwx));
+    const float wx = fmaf(h, P.J_INV[0] * tqx, k.wx), wy = fmaf(h, P.J_INV[1] * tqy, k.wy), wz = fmaf(h, P.J_INV[2] * tqz, k.wz);   // new rates
+    const float n2 = fmaf(wz, wz, fmaf(wy, wy, wx * wx));
+    const float u = n2 * (0.25f * h * h);
+    // cos t and sin t / t as substep<>'s polynomials in u = t^2, and their derivatives in u
+    float cs = fmaf(fmaf(fmaf(fmaf(2.412107309e-05f, u, -1.388295778e-03f), u, 4.166645522e-02f), u, -4.999999736e-01f), u, 9.999999995e-01f);
+    float sp = fmaf(fmaf(fmaf(fmaf(2.693749890e-06f, u, -1.983586443e-04f), u, 8.333314057e-03f), u, -1.666666643e-01f), u, 1.0f);
+    float dcs = fmaf(fmaf(fmaf(4.0f * 2.412107309e-05f, u, 3.0f * -1.388295778e-03f), u, 2.0f * 4.166645522e-02f), u, -4.999999736e-01f);
+    float dsp = fmaf(fmaf(fmaf(4.0f * 2.693749890e-06f, u, 3.0f * -1.983586443e-04f), u, 2.0f * 8.333314057e-03f), u, -1.666666643e-01f);
+    if (!(u <= 1.0f)) {                    // tumbling: substep<>'s exact path, d cos(sqrt u) / du = -sinc / 2, d sinc / du = (cos - sinc) / 2u
+        const float n = sqrtf(n2);
+        float sn;
+        sincosf(n * h * 0.5f, &sn, &cs);
+        sp = sn / (n * h * 0.5f);
+        dcs = -0.5f * sp;
+        dsp = 0.5f * (cs - sp) / u;
+    }
+    const float sc = sp * (0.5f * h);
+    const bool turn = n2 > 1e-16f;
+
+    // ---- reverse
+    float awx = a.wx, awy = a.wy, awz = a.wz;                  // cotangent of the NEW rates
+    if (AV) {                                                  // av = R w'
+        awx += fmaf(R.r00, bx, fmaf(R.r10, by, R.r20 * bz));
+        awy += fmaf(R.r01, bx, fmaf(R.r11, by, R.r21 * bz));
+        awz += fmaf(R.r02, bx, fmaf(R.r12, by, R.r22 * bz));
+    }
+    float aqx = a.qx, aqy = a.qy, aqz = a.qz, aqw = a.qw;      // becomes the cotangent of the OLD quaternion
+    if (turn) {                                                // q' = cs q + sc (q (x) [w', 0])
+        const float lx = fmaf(wx, k.qw, fmaf(wz, k.qy, -(wy * k.qz)));
+        const float ly = fmaf(wy, k.qw, fmaf(wx, k.qz, -(wz * k.qx)));
+        const float lz = fmaf(wz, k.qw, fmaf(wy, k.qx, -(wx * k.qy)));
+        const float lw = -fmaf(wz, k.qz, fmaf(wy, k.qy, wx * k.qx));
+        const float a_cs = fmaf(a.qx, k.qx, fmaf(a.qy, k.qy, fmaf(a.qz, k.qz, a.qw * k.qw)));
+        const float a_sc = fmaf(a.qx, lx, fmaf(a.qy, ly, fmaf(a.qz, lz, a.qw * lw)));
+        const float alx = sc * a.qx, aly = sc * a.qy, alz = sc * a.qz, alw = sc * a.qw;
+        aqx = fmaf(cs, a.qx, (alz * wy - aly * wz) - alw * wx);
+        aqy = fmaf(cs, a.qy, (alx * wz - alz * wx) - alw * wy);
+        aqz = fmaf(cs, a.qz, (aly * wx - alx * wy) - alw * wz);
+        aqw = fmaf(cs, a.qw, fmaf(alx, wx, fmaf(aly, wy, alz * wz)));
+        const float a_n2 = fmaf(a_cs, dcs, a_sc * (0.5f * h) * dsp) * (0.25f * h * h);
+        awx += ((alx * k.qw + aly * k.qz) - alz * k.qy) - alw * k.qx + 2.0f * wx * a_n2;
+        awy += ((aly * k.qw - alx * k.qz) + alz * k.qx) - alw * k.qy + 2.0f * wy * a_n2;
+        awz += ((alx * k.qy - aly * k.qx) + alz * k.qw) - alw * k.qz + 2.0f * wz * a_n2;
+    }
+    // p' = p + h v': the position's cotangent passes through
+    const float avx = fmaf(h, a.px, a.vx), avy = fmaf(h, a.py, a.vy), avz = fmaf(h, a.pz, a.vz);    // cotangent of the NEW velocity
+    // w' = w + h J^-1 (t - w x J w)
+    const float atx = h * P.J_INV[0] * awx, aty = h * P.J_INV[1] * awy, atz = h * P.J_INV[2] * awz;
+    const float j21 = P.J[2] - P.J[1], j02 = P.J[0] - P.J[2], j10 = P.J[1] - P.J[0];
+    a.wx = awx - fmaf(aty, k.wz * j02, atz * (k.wy * j10));
+    a.wy = awy - fmaf(atx, k.wz * j21, atz * (k.wx * j10));
+    a.wz = awz - fmaf(atx, k.wy * j21, aty * (k.wx * j02));
+    const float kzt = kz * atz;
+    ag[0] -= kzt; ag[1] += kzt; ag[2] -= kzt; ag[3] += kzt;
+    if (plus) {
+        ag[1] += P.L * atx; ag[3] -= P.L * atx; ag[0] -= P.L * aty; ag[2] += P.L * aty;
+    } else {
+        const float px_ = arm_x * atx, py_ = arm * aty;
+        ag[0] += px_ - py_; ag[1] += px_ + py_; ag[2] += py_ - px_; ag[3] -= px_ + py_;
+    }
+    // v' = v + h F / M
+    const float afx = h * P.inv_M * avx, afy = h * P.inv_M * avy, afz = h * P.inv_M * avz;
+    a.vx = avx; a.vy = avy; a.vz = avz;
+    if (drag) {                                                // F -= drag_coeff * v * wsum
+        a.vx = fmaf(-(P.drag_coeff[0] * wsum), afx, a.vx);
+        a.vy = fmaf(-(P.drag_coeff[1] * wsum), afy, a.vy);
+        a.vz = fmaf(-(P.drag_coeff[2] * wsum), afz, a.vz);
+        const float a_wsum = -fmaf(P.drag_coeff[0] * k.vx, afx, fmaf(P.drag_coeff[1] * k.vy, afy, (P.drag_coeff[2] * k.vz) * afz));
+        a_drag += a_wsum * (6.28318530717958647692f / 60.0f);
+    }
+    // F = R[:, 2] T - (0, 0, GRAVITY)
+    const float a_T = fmaf(afx, R.r02, fmaf(afy, R.r12, afz * R.r22));
+    ag[0] += a_T; ag[1] += a_T; ag[2] += a_T; ag[3] += a_T;
+    // cotangent of the rotation matrix: the force column, and (AV) the observed angular velocity
+    const float r02 = fmaf(afx, T, AV ? bx * wz : 0.0f), r12 = fmaf(afy, T, AV ? by * wz : 0.0f), r22 = fmaf(afz, T, AV ? bz * wz : 0.0f);
+    const float r00 = AV ? bx * wx : 0.0f, r01 = AV ? bx * wy : 0.0f, r10 = AV ? by * wx : 0.0f, r11 = AV ? by * wy : 0.0f;
+    const float r20 = AV ? bz * wx : 0.0f, r21 = AV ? bz * wy : 0.0f;
+    // R = I + s B(q), s = 2 / |q|^2 (quat_to_mat)
+    const float x = k.qx, y = k.qy, z = k.qz, w = k.qw;
+    const float d = fmaf(x, x, fmaf(y, y, fmaf(z, z, w * w)));
+    const float s = 2.0f / d;
+    const float a_s = -(r00 * fmaf(y, y, z * z) + r11 * fmaf(x, x, z * z) + r22 * fmaf(x, x, y * y))
+                      + r01 * fmaf(x, y, -(w * z)) + r02 * fmaf(x, z, w * y) + r10 * fmaf(x, y, w * z)
+                      + r12 * fmaf(y, z, -(w * x)) + r20 * fmaf(x, z, -(w * y)) + r21 * fmaf(y, z, w * x);
+    const float a_d2 = -2.0f * (s / d) * a_s;                   // d s / d q_i = -(s / d) 2 q_i
+    const float b00 = s * r00, b01 = s * r01, b02 = s * r02, b10 = s * r10, b11 = s * r11, b12 = s * r12, b20 = s * r20, b21 = s * r21, b22 = s * r22;
+    a.qx = aqx + fmaf(a_d2, x, (b01 + b10) * y + (b02 + b20) * z + (b21 - b12) * w - 2.0f * (b11 + b22) * x);
+    a.qy = aqy + fmaf(a_d2, y, (b01 + b10) * x + (b12 + b21) * z + (b02 - b20) * w - 2.0f * (b00 + b22) * y);
+    a.qz = aqz + fmaf(a_d2, z, (b02 + b20) * x + (b12 + b21) * y + (b10 - b01) * w - 2.0f * (b00 + b11) * z);
+    a.qw = aqw + fmaf(a_d2, w, (b10 - b01) * z + (b02 - b20) * y + (b21 - b12) * x);
+}
+
+// Adjoint of map_action<false, AW> (the four RPM action types): out[AW] = cotangent of the raw action row
+//   ag[4]  cotangent of the thrust deviations;  a_sum  cotangent of the step's rpm sum (what the drag terms saw of it)
+template <int AW, class PP>
+__device__ __forceinline__ void action_vjp(const PP& P, const GpdStepCfg& C, const float4 act, const float rpm[4], const float ag[4],
+                                           const float a_sum, float out[4]) {
+    const float nt = norm_thrust_of(P);
+    if (AW == 1) {                        // one value drives the four rotors
+        const float e = 0.05f * act.x;
+        out[0] = 0.05f * fmaf(((ag[0] + ag[1]) + ag[2]) + ag[3], nt * (2.0f + 2.0f * e), 4.0f * a_sum * P.hover_rpm);
+        out[1] = out[2] = out[3] = 0.0f;
+    } else if (C.act_type == GPD_ACT_RPM) {
+        const float av[4] = {act.x, act.y, act.z, act.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) out[i] = 0.05f * fmaf(ag[i], nt * (2.0f + 2.0f * (0.05f * av[i])), a_sum * P.hover_rpm);
+    } else {                              // RAW_RPM: zero outside the clip; DIRECT_RPM: as is
+        const bool clip = C.act_type == GPD_ACT_RAW_RPM;
+        const float av[4] = {act.x, act.y, act.z, act.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const bool inside = !clip || (av[i] >= 0.0f && av[i] <= P.max_rpm);
+            out[i] = inside ? fmaf(ag[i], 2.0f * P.KF * rpm[i], a_sum) : 0.0f;
+        }
+    }
+}
+
+template <bool EXT, int AW, bool PLANT>
+__global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_kernel(const GpdParams P, const GpdStepCfg C, const int64_t ld, const int K,
+                                                                 const float* __restrict__ actions, const int64_t a_stride,
+                                                                 const float* __restrict__ target_pos, const float* __restrict__ plant,
+                                                                 const float* __restrict__ tape, const float* __restrict__ g_obs12,
+                                                                 const int64_t o_stride, const float* __restrict__ g_reward,
+                                                                 const int64_t e_stride, float* __restrict__ g_kin,
+                                                                 float* __restrict__ g_actions) {
+    const uint32_t N = static_cast<uint32_t>(C.num_envs);
+    const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t flags = EXT ? C.physics_flags : 0u;
+    const bool drag = EXT && (flags & GPD_PHYS_DRAG);
+    plant_t<PLANT> Q = plant_of<PLANT>(P, plant, ld, n * 4u);
+    const bool has_task = C.task != GPD_TASK_NONE;
+    const float* tp = target_pos + (C.target_per_env ? static_cast<size_t>(n) * 3 : 0);      // (task NONE: a readable dummy)
+    const float tgx = tp[0], tgy = tp[1], tgz = tp[2];
+    const float h = C.pyb_dt;
+    const int S = C.substeps;
+    Kin A = planes_load(g_kin, ld, n);                         // cotangent of the state after the step in hand
+    float a_next = 0.0f;                                       // cotangent of this step's rpm sum from the NEXT step's first drag term
+    const float first_sum = drag ? tape[static_cast<int64_t>(K) * 13 * ld + n] : 0.0f;
+    for (int t = K - 1; t >= 0; --t) {
+        const Kin k0 = planes_load(tape + static_cast<int64_t>(t) * 13 * ld, ld, n);
+        const float4 act = load_action<AW>(actions + t * a_stride, n);
+        Carry c{};
+        c.k = k0;
+        float rpm[4], g[4];
+        map_action<false, AW, -1>(Q, C, act, c, rpm, g);
+        const float cur_sum = ((rpm[0] + rpm[1]) + rpm[2]) + rpm[3];
+        float prev_sum = cur_sum;
+        if (drag) {                                            // the first sub-step sees the previous step's RPMs
+            prev_sum = first_sum;
+            if (t > 0) {
+                float rp[4], gp_[4];
+                map_action<false, AW, -1>(Q, C, load_action<AW>(actions + (t - 1) * a_stride, n), c, rp, gp_);
+                prev_sum = ((rp[0] + rp[1]) + rp[2]) + rp[3];
+            }
+        }
+        float go[12];
+        if (g_obs12) {
+            const f4u* row = reinterpret_cast<const f4u*>(g_obs12 + t * o_stride + static_cast<size_t>(n) * 12);
+            const f4u r0 = row[0], r1 = row[1], r2 = row[2];
+            go[0] = r0.x; go[1] = r0.y; go[2] = r0.z; go[3] = r0.w; go[4] = r1.x; go[5] = r1.y; go[6] = r1.z; go[7] = r1.w;
+            go[8] = r2.x; go[9] = r2.y; go[10] = r2.z; go[11] = r2.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 12; ++i) go[i] = 0.0f;
+        }
+        const float grew = (g_reward && has_task) ? g_reward[t * e_stride + n] : 0.0f;
+        float ag[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        float a_cur = a_next, a_prev = 0.0f;
+        float d0, d1, d2;
+        for (int j = S - 1; j >= 0; --j) {
+            Kin k = k0;                                        // the state sub-step j started from: j forward sub-steps from the tape
+            for (int i = 0; i < j; ++i) substep<EXT, false>(Q, h, flags, g, i == 0 ? prev_sum : cur_sum, 0.0f, k, d0, d1, d2);
+            const float ds = j == 0 ? prev_sum : cur_sum;
+            float a_drag = 0.0f;
+            if (j == S - 1) {
+                // the step's outputs are functions of the state its LAST sub-step leaves: obs12 = pos | rpy | vel | ang_v, the reward
+                Kin kp = k;
+                substep<EXT, false>(Q, h, flags, g, ds, 0.0f, kp, d0, d1, d2);
+                A.px += go[0]; A.py += go[1]; A.pz += go[2];
+                A.vx += go[6]; A.vy += go[7]; A.vz += go[8];
+                float rqx, rqy, rqz, rqw;
+                rpy_vjp(kp.qx, kp.qy, kp.qz, kp.qw, go[3], go[4], go[5], rqx, rqy, rqz, rqw);
+                A.qx += rqx; A.qy += rqy; A.qz += rqz; A.qw += rqw;
+                {   // reward = max(0, 2 - |target - p|^4), task_single's expressions
+                    const float ex = tgx - kp.px, ey = tgy - kp.py, ez = tgz - kp.pz;
+                    const float dist = fast_sqrt(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
+                    const float dd = dist * dist;
+                    const float gr = fmaf(-dd, dd, 2.0f) > 0.0f ? 4.0f * dd * grew : 0.0f;
+                    A.px = fmaf(gr, ex, A.px); A.py = fmaf(gr, ey, A.py); A.pz = fmaf(gr, ez, A.pz);
+                }
+                substep_vjp<EXT, true>(Q, h, flags, g, ds, k, A, go[9], go[10], go[11], ag, a_drag);
+            } else {
+                substep_vjp<EXT, false>(Q, h, flags, g, ds, k, A, 0.0f, 0.0f, 0.0f, ag, a_drag);
+            }
+            a_prev += j == 0 ? a_drag : 0.0f;                  // (selects: a branch here makes the two sums an indexed array in scratch)
+            a_cur += j == 0 ? 0.0f : a_drag;
+        }
+        float ga[4];
+        action_vjp<AW>(Q, C, act, rpm, ag, a_cur, ga);
+        float* dst = g_actions + (static_cast<size_t>(t) * N + n) * AW;
+        if (AW == 4) *reinterpret_cast<f4v*>(dst) = f4v{ga[0], ga[1], ga[2], ga[3]};
+        else dst[0] = ga[0];
+        a_next = a_prev;
+    }
+    planes_store(g_kin, ld, n, A);
+}
+
+// what the two entries refuse, before any device work: `who` and the reason in the message
+int diff_unsupported(const char* who, const GpdStepCfg* cfg) {
+    auto no = [&](const char* why) { return fail(GPD_ENOTSUP, (std::string(who) + ": " + why).c_str()); };
+    if (cfg->drones_per_env != 1) return no("aviaries of more than one drone are not differentiable (drones_per_env must be 1)");
+    if (cfg->task != GPD_TASK_NONE && cfg->task != GPD_TASK_HOVER) return no("task must be GPD_TASK_NONE or GPD_TASK_HOVER");
+    if (cfg->act_type != GPD_ACT_RPM && cfg->act_type != GPD_ACT_ONE_D_RPM && cfg->act_type != GPD_ACT_RAW_RPM && cfg->act_type != GPD_ACT_DIRECT_RPM)
+        return no("the DSLPID action types are not differentiable (RPM, ONE_D_RPM, RAW_RPM and DIRECT_RPM are)");
+    if (cfg->physics_flags & ~static_cast<uint32_t>(GPD_PHYS_DRAG))
+        return no("physics_flags other than GPD_PHYS_DRAG are not differentiable (ground effect, downwash, ground plane, damping)");
+    if (cfg->auto_reset) return no("auto_reset inside a differentiated call is not supported");
+    return 0;
+}
+
+int diff_sizes(const char* who, const GpdStepCfg* cfg, int32_t num_steps, int64_t ld) {
+    auto bad = [&](int code, const char* why) { return fail(code, (std::string(who) + ": " + why).c_str()); };
+    if (num_steps <= 0) return bad(GPD_EINVAL, "num_steps must be positive");
+    if (cfg->num_envs <= 0 || cfg->drones_per_env <= 0 || cfg->substeps <= 0)
+        return bad(GPD_EINVAL, "num_envs, drones_per_env and substeps must be positive");
+    if (cfg->act_type < GPD_ACT_RPM || cfg->act_type > GPD_ACT_DIRECT_RPM) return bad(GPD_EINVAL, "unknown act_type");
+    if (cfg->task < GPD_TASK_NONE || cfg->task > GPD_TASK_MULTIHOVER) return bad(GPD_EINVAL, "unknown task");
+    if (cfg->physics_flags & ~31u) return bad(GPD_EINVAL, "unknown physics flag");
+    if (ld <= 0 || ld > 0xffffffffLL) return bad(GPD_EINVAL, "ld must be in 1 .. 2^32 - 1 (floats)");
+    if (ld < static_cast<int64_t>(cfg->num_envs) * cfg->drones_per_env) return bad(GPD_EINVAL, "ld < num_envs*drones_per_env");
+    if (static_cast<int64_t>(cfg->num_envs) * cfg->drones_per_env > (1LL << 26)) return bad(GPD_ERANGE, "more than 2^26 drones per launch (32-bit byte offsets)");
+    return 0;
+}
+
+// act_type / physics flags / plant table -> <EXT, AW, PLANT>: every kernel of this file is launched from here
+template <class F>
+hipError_t diff_dispatch(const GpdStepCfg& c, bool plant, F&& launch) {
+    auto with = [&](auto ext, auto aw) {
+        return plant ? launch(ext, aw, Const<true>{}) : launch(ext, aw, Const<false>{});
+    };
+    auto with_ext = [&](auto aw) { return c.physics_flags != 0 ? with(Const<true>{}, aw) : with(Const<false>{}, aw); };
+    return c.act_type == GPD_ACT_ONE_D_RPM ? with_ext(Const<1>{}) : with_ext(Const<4>{});
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpd_rollout_tape_floats(const GpdStepCfg* cfg, int32_t num_steps, int64_t ld, int64_t* floats_out) {
+    const char* who = "gpd_rollout_tape_floats";
+    if (!cfg || !floats_out) return fail(GPD_EINVAL, "gpd_rollout_tape_floats: NULL cfg/floats_out");
+    if (int rc = diff_sizes(who, cfg, num_steps, ld)) return rc;
+    if (int rc = diff_unsupported(who, cfg)) return rc;
+    const int64_t rows = 13 * static_cast<int64_t>(num_steps) + 1;           // 13 per env step + the first drag term's rpm sum
+    if (rows > INT64_MAX / ld) return fail(GPD_ERANGE, "gpd_rollout_tape_floats: the tape does not fit 2^63 floats");
+    *floats_out = rows * ld;
+    return 0;
+}
+
+int gpd_rollout_tape(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, int32_t num_steps, const float* actions,
+                     int64_t action_step_stride, const float* target_pos, float* obs12, int64_t obs_step_stride, float* reward,
+                     uint8_t* terminated, uint8_t* truncated, int64_t env_step_stride, const float* plant_rows, float* tape, void* stream) {
+    const char* who = "gpd_rollout_tape";
+    auto bad = [&](int code, const char* msg) { return fail(code, (std::string(who) + ": " + msg).c_str()); };
+    if (!params || !state || !cfg) return bad(GPD_EINVAL, "NULL params/state/cfg");
+    if (!state->kin || !state->step_counter) return bad(GPD_EINVAL, "NULL state.kin/step_counter");
+    if (const char* why = state_layout_problem(state)) return bad(GPD_EINVAL, why);
+    if (!actions || !obs12 || !reward || !terminated || !truncated || !tape)
+        return bad(GPD_EINVAL, "NULL actions/obs12/reward/terminated/truncated/tape");
+    if (action_step_stride < 0 || obs_step_stride < 0 || env_step_stride < 0) return bad(GPD_EINVAL, "strides must be non-negative");
+    if (int rc = diff_sizes(who, cfg, num_steps, state->ld)) return rc;
+    if (int rc = diff_unsupported(who, cfg)) return rc;
+    if (state->dw_force) return bad(GPD_ENOTSUP, "state.dw_force (downwash computed outside the kernel) is not differentiable");
+    if ((cfg->physics_flags & GPD_PHYS_DRAG) && !state->last_rpm) return bad(GPD_EINVAL, "GPD_PHYS_DRAG needs state.last_rpm");
+    if (cfg->task != GPD_TASK_NONE && !target_pos) return bad(GPD_EINVAL, "task needs target_pos");
+    if ((reinterpret_cast<uintptr_t>(tape) & 15u) != 0) return bad(GPD_EINVAL, "tape must be 16-byte aligned");
+    if (plant_rows && (reinterpret_cast<uintptr_t>(plant_rows) & 15u) != 0) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
+    GpdStepCfg c = *cfg;
+    GpdState s = *state;
+    s.act_ring = nullptr;                                      // (a rollout never pushes into the action ring itself)
+    if (c.task == GPD_TASK_NONE) { target_pos = state->kin; c.target_per_env = 0; }      // a readable dummy, as in gpd_rollout
+    const dim3 grid(static_cast<unsigned>((static_cast<int64_t>(c.num_envs) + kBlock - 1) / kBlock));
+    const hipError_t e = diff_dispatch(c, plant_rows != nullptr, [&](auto ext, auto aw, auto pl) {
+        hipLaunchKernelGGL((gpd_rollout_tape_kernel<decltype(ext)::value, decltype(aw)::value, decltype(pl)::value>), grid, dim3(kBlock), 0,
+                           static_cast<hipStream_t>(stream), *params, s, c, num_steps, action_step_stride, obs_step_stride, env_step_stride, actions, target_pos, obs12, reward, terminated, truncated,
+                           plant_rows, tape);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return hip_fail(e, "gpd_rollout_tape launch");
+    return 0;
+}
+
+int gpd_rollout_vjp(const GpdParams* params, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, const float* actions,
+                    int64_t action_step_stride, const float* target_pos, const float* plant_rows, const float* tape,
+                    const float* g_obs12, int64_t obs_step_stride, const float* g_reward, int64_t env_step_stride, float* g_kin,
+                    float* g_actions, void* stream) {
+    const char* who = "gpd_rollout_vjp";
+    auto bad = [&](int code, const char* msg) { return fail(code, (std::string(who) + ": " + msg).c_str()); };
+    if (!params || !cfg) return bad(GPD_EINVAL, "NULL params/cfg");
+    if (!actions || !tape || !g_kin || !g_actions) return bad(GPD_EINVAL, "NULL actions/tape/g_kin/g_actions");
+    if (action_step_stride < 0 || obs_step_stride < 0 || env_step_stride < 0) return bad(GPD_EINVAL, "strides must be non-negative");
+    if (int rc = diff_sizes(who, cfg, num_steps, ld)) return rc;
+    if (int rc = diff_unsupported(who, cfg)) return rc;
+    if (cfg->task != GPD_TASK_NONE && !target_pos) return bad(GPD_EINVAL, "task needs target_pos");
+    if (((reinterpret_cast<uintptr_t>(tape) | reinterpret_cast<uintptr_t>(g_kin)) & 15u) != 0)
+        return bad(GPD_EINVAL, "tape and g_kin must be 16-byte aligned");
+    if (plant_rows && (reinterpret_cast<uintptr_t>(plant_rows) & 15u) != 0) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(g_actions) & 15u) != 0) return bad(GPD_EINVAL, "g_actions must be 16-byte aligned");
+    GpdStepCfg c = *cfg;
+    if (c.task == GPD_TASK_NONE) { target_pos = tape; c.target_per_env = 0; }          // a readable dummy
+    const dim3 grid(static_cast<unsigned>((static_cast<int64_t>(c.num_envs) + kBlock - 1) / kBlock));
+    const hipError_t e = diff_dispatch(c, plant_rows != nullptr, [&](auto ext, auto aw, auto pl) {
+        hipLaunchKernelGGL((gpd_rollout_vjp_kernel<decltype(ext)::value, decltype(aw)::value, decltype(pl)::value>), grid, dim3(kBlock), 0,
+                           static_cast<hipStream_t>(stream), *params, c, ld, num_steps, actions, action_step_stride, target_pos, plant_rows,
+                           tape, g_obs12, obs_step_stride, g_reward, env_step_stride, g_kin, g_actions);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return hip_fail(e, "gpd_rollout_vjp launch");
+    return 0;
+}
+
+}  // extern "C"

@@ -416,6 +416,15 @@ class SimCore:
                 self._latest_terminal(tobs, term, trunc, K)
         return obs, rew, term, trunc
 
+    def rollout_diff(self, actions: torch.Tensor, kin0: torch.Tensor = None, num_steps: int = None):
+        """`rollout()` that `.backward()` goes through (`diff.rollout_diff`: `gpd_rollout_tape` forward, `gpd_rollout_vjp` backward).
+        Returns fresh tensors `(obs12 [K,N,12], reward [K,E], kin_K [13*ld], terminated [K,E], truncated [K,E])`; obs12, reward and
+        kin_K carry gradients with respect to `actions` and `kin0` (None: the core's own state; else the plane layout, copied into the
+        state first -- `kin_K` of one call as `kin0` of the next chains the graph).  Single-drone aviaries, the RPM action types, no
+        add-on physics or drag, no auto-reset: GpdError otherwise."""
+        from . import diff
+        return diff.rollout_diff(self, actions, kin0, num_steps)
+
     def _fixed_args(self):
         """the arguments of gpd_step / gpd_rollout* that never change between two calls, as ctypes objects (set_target() drops them)"""
         self._step_args = tuple(_native.as_c(x) for x in (self._params, self._state, self._cfg, self.target, self.init_pose, self.obs12,

@@ -852,6 +852,46 @@ int gpd_debug_status(uint32_t out[4], int32_t reset, void* stream);
  */
 int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream);
 
+/*
+ * The differentiable rollout (additions to ABI 9): analytic gradients through the K-step kernel, for policy gradients through the
+ * physics and gradient-based trajectory optimisation.  The reference has no counterpart (its integrator is numpy,
+ * envs/BaseAviary.py:815-892; nothing in it carries a derivative).
+ *
+ * gpd_rollout_tape is gpd_rollout (plant_rows == NULL: the nominal airframe) or gpd_rollout_plant (plant_rows given, pitch state.ld)
+ * plus a record of what the reverse sweep needs.  Whatever it leaves behind -- state, last_rpm, step_counter, bad, obs12, reward and
+ * flags -- is bit for bit what gpd_rollout / gpd_rollout_plant leaves on the same inputs (the same map_action / env_step / substep
+ * code).  The tape is opaque, 16-byte aligned, gpd_rollout_tape_floats(cfg, num_steps, state.ld) floats: the 13 kinematic floats at
+ * the start of every env step in the plane layout of GpdState.kin (52 B per drone-step) and one row for the rpm sum the drag term of
+ * the call's first sub-step saw.
+ *
+ * gpd_rollout_vjp is the vector-Jacobian product of the map (kin_0, a_0 .. a_K-1) -> (kin_K, obs12_0 .., reward_0 ..) of that call:
+ *   ld, num_steps, actions, action_step_stride, target_pos, plant_rows   what the taped call was given (ld = state.ld)
+ *   g_obs12, g_reward   cotangents of the outputs, laid out like them (obs_step_stride / env_step_stride); NULL = zeros
+ *   g_kin               [13*ld], the four-plane layout of GpdState.kin, IN PLACE: on entry the cotangent of the final state, on return
+ *                       the cotangent of the initial state.  16-byte aligned
+ *   g_actions           [K][N][A] out, ALWAYS one block per step -- also when action_step_stride == 0: the caller sums the blocks of
+ *                       a shared action block.  16-byte aligned
+ * One lane per drone, steps K-1 .. 0; with S sub-steps per step the forward sub-steps are re-run from the taped state for each
+ * sub-step in reverse (S(S+1)/2 recomputations, no scratch memory).  No atomics: two calls give the same bits.  The adjoint is that
+ * of the function as executed: a select differentiates the branch taken (the |w| ~ 0 test of the quaternion update, the gimbal
+ * branches of the Euler extraction, the clip of GPD_ACT_RAW_RPM -- zero gradient outside its bounds --, max(0, .) of the reward).  The
+ * observed world angular velocity uses the pre-update rotation and the post-update rates, and so does its adjoint.  The drag term of
+ * a step's first sub-step sees the previous step's RPMs: inside one call that dependence is differentiated, the value carried in
+ * from before the call is a constant.  Plant rows and targets are constants of the sweep.
+ *
+ * Supported: drones_per_env == 1; GPD_TASK_NONE and GPD_TASK_HOVER; GPD_ACT_RPM, ONE_D_RPM, RAW_RPM and DIRECT_RPM; physics_flags 0
+ * or GPD_PHYS_DRAG; all three airframes; auto_reset == 0.  Everything else (the DSLPID action types, the other flags, D > 1,
+ * auto_reset, state.dw_force) returns GPD_ENOTSUP with a message that names the entry and the reason, before any device work.
+ */
+int gpd_rollout_tape_floats(const GpdStepCfg* cfg, int32_t num_steps, int64_t ld, int64_t* floats_out);
+int gpd_rollout_tape(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, int32_t num_steps, const float* actions,
+                     int64_t action_step_stride, const float* target_pos, float* obs12, int64_t obs_step_stride, float* reward,
+                     uint8_t* terminated, uint8_t* truncated, int64_t env_step_stride, const float* plant_rows, float* tape, void* stream);
+int gpd_rollout_vjp(const GpdParams* params, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, const float* actions,
+                    int64_t action_step_stride, const float* target_pos, const float* plant_rows, const float* tape,
+                    const float* g_obs12, int64_t obs_step_stride, const float* g_reward, int64_t env_step_stride, float* g_kin,
+                    float* g_actions, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""What the differentiable rollout costs, and what it is measured against.
+
+    python profiles/diff_bench.py [--out profiles/diff_mi355x.json] [--grad-figures FILE]
+
+65 536 single-drone HoverAviaries, Physics.DYN, ActionType.RPM, K = 20 env steps per launch, observation rows of every step stored, at
+S = 1 (240 Hz control) and S = 8 (30 Hz control) physics sub-steps per step.  Timed with device events in ONE process, in turns, each
+until it has run for at least 0.25 s after warm-up; us per ENV STEP:
+  rollout          the yardstick: `gpd_rollout` (the kernel this change does not touch) on the same box
+  rollout_tape     `gpd_rollout_tape`: the same arithmetic + the 52 B per drone-step tape
+  rollout_vjp      `gpd_rollout_vjp`: the reverse sweep (cotangents for every output)
+  torch_autograd   the user's alternative: the float32 torch restatement of tests/helpers/diff_f64.py on the device, forward +
+                   `.backward()` for the same gradient (one launch per arithmetic operation; timed for at least 3 passes)
+No time is a pass condition.  `--grad-figures`: a JSON file of measured gradient errors (tests/test_gpu_diff.py prints them) to record
+next to the timings.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests", "helpers"))
+
+import diff_f64 as ref  # noqa: E402
+from gym_pybullet_drones_amd import _native, engine  # noqa: E402
+from gym_pybullet_drones_amd.diff import tape_floats, unpack_kin  # noqa: E402
+
+N, K, MIN_SECONDS = 65536, 20, 0.25
+
+
+def timed(fn, calls):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(calls):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e-3
+
+
+def variants(S, dev):
+    core = engine.SimCore(num_envs=N, drones_per_env=1, pyb_freq=240, ctrl_freq=240 // S, act_code=0, task=engine.TASK_HOVER,
+                          target_pos=[[0.0, 0.0, 1.0]], auto_reset=False, track_rpm=True, device=dev)
+    g = torch.Generator(device=dev).manual_seed(S)
+    acts = (torch.rand((K, N, 4), generator=g, device=dev) * 2 - 1).contiguous()
+    kin0 = core.kin_store.clone()
+    tape = torch.empty(tape_floats(core, K), dtype=torch.float32, device=dev)
+    obs, rew = torch.empty((K, N, 12), device=dev), torch.empty((K, N), device=dev)
+    flags = torch.empty((2, K, N), dtype=torch.bool, device=dev)
+    g_obs, g_rew = torch.randn((K, N, 12), generator=g, device=dev), torch.randn((K, N), generator=g, device=dev)
+    g_kin, g_act = torch.randn(13 * core.ld, generator=g, device=dev), torch.empty((K, N, 4), device=dev)
+
+    def rollout():
+        core.kin_store.copy_(kin0)
+        core.rollout(acts, update_latest=False)
+
+    def rollout_tape():
+        core.kin_store.copy_(kin0)
+        _native.call("gpd_rollout_tape", dev, core._stream(), core._params, core._state, core._cfg, K, acts, N * 4, core.target, obs, N * 12,
+                     rew, flags[0], flags[1], N, None, tape)
+
+    def rollout_vjp():
+        _native.call("gpd_rollout_vjp", dev, core._stream(), core._params, core._cfg, core.ld, K, acts, N * 4, core.target, None, tape, g_obs,
+                     N * 12, g_rew, N, g_kin, g_act)
+
+    cfg = ref.config("cf2x", "rpm", S, False, "hover")
+    c = ref.consts(core.P, N, torch.float32, device=dev)
+    target = torch.tensor([0.0, 0.0, 1.0], device=dev).expand(N, 3)
+    zero = torch.zeros(N, device=dev)
+
+    def torch_autograd():
+        a = acts.clone().requires_grad_(True)
+        k0 = tuple(x.clone().requires_grad_(True) for x in unpack_kin(kin0, N))
+        o, r, kk = ref.rollout(c, cfg, k0, a, zero, target)
+        loss = (g_obs * o).sum() + (g_rew * r).sum() + sum((gk * x).sum() for gk, x in zip(unpack_kin(g_kin, N), kk))
+        torch.autograd.grad(loss, (a,) + k0)
+
+    rollout_tape()                                             # (the reverse sweep reads this tape)
+    return {"rollout": (rollout, 10), "rollout_tape": (rollout_tape, 10), "rollout_vjp": (rollout_vjp, 10), "torch_autograd": (torch_autograd, 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--grad-figures", default=None)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    res = {"method": "HIP events, >= 0.25 s per variant after warm-up (torch_autograd: >= 3 passes), the variants in turns in one process; "
+                     "rollout and rollout_tape include the 3.4 MB copy that restores the initial state",
+           "device": torch.cuda.get_device_name(0), "drones": N, "steps_per_launch": K, "us_per_env_step": {}, "tape_bytes_per_drone_step": 52}
+    for S in (1, 8):
+        jobs = variants(S, dev)
+        for fn, _ in jobs.values():                            # warm-up
+            fn()
+        torch.cuda.synchronize()
+        spent, done = dict.fromkeys(jobs, 0.0), dict.fromkeys(jobs, 0)
+
+        def enough(name):
+            return spent[name] >= MIN_SECONDS and done[name] >= 3
+        while not all(enough(n) for n in jobs):                # in turns: what drifts, drifts for all of them
+            for name, (fn, calls) in jobs.items():
+                if not enough(name):
+                    spent[name] += timed(fn, calls)
+                    done[name] += calls
+        u = {k: spent[k] / (done[k] * K) * 1e6 for k in jobs}
+        u["tape_over_rollout"] = u["rollout_tape"] / u["rollout"]
+        u["vjp_over_rollout"] = u["rollout_vjp"] / u["rollout"]
+        u["torch_autograd_over_tape_plus_vjp"] = u["torch_autograd"] / (u["rollout_tape"] + u["rollout_vjp"])
+        res["us_per_env_step"][f"S={S}"] = u
+        print(f"S={S}", json.dumps(u), flush=True)
+    if a.grad_figures and os.path.exists(a.grad_figures):
+        res["gradient_error_vs_float64"] = json.load(open(a.grad_figures))
+    print(json.dumps(res))
+    if a.out:
+        json.dump(res, open(a.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,244 @@
+"""The yardstick of the differentiable rollout (tests/test_host_diff.py, tests/test_gpu_diff.py): a torch restatement of one env step
+for the subset `gpd_rollout_tape` / `gpd_rollout_vjp` support -- single-drone aviaries, the four RPM action types, no add-on physics or
+drag, no task or the hover task, per-drone constants (the plant path).  It is dtype-generic; run in float64 under autograd it is the
+reference the device gradients are held against, and its forward is held against `oracle.batched_oracle` (1e-12).
+
+Selects are written so that the branch NOT taken cannot produce NaN gradients (`torch.where` multiplies the untaken branch's gradient
+by zero, and 0 * inf = NaN): every operand of an untaken branch is replaced by a harmless one first.  A plain sin(t) / |w| is NaN at rest.
+
+The same file holds the input generator of the GPU tests (`make_inputs`).  Test infrastructure."""
+import math
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+ACT_DIM = {"rpm": 4, "one_d_rpm": 1, "raw_rpm": 4, "direct_rpm": 4}
+ACT_CODE = {"rpm": 0, "one_d_rpm": 3, "raw_rpm": 5, "direct_rpm": 6}
+GIMBAL = 0.99999
+TURN_N2 = 1e-16
+#: order of the plant scale factors (include/gpd.h GPD_SCALE_*)
+SCALES = ("mass", "ixx", "iyy", "izz", "kf", "km", "drag_xy", "drag_z", "gnd_eff")
+
+
+def config(model="cf2x", act="rpm", S=1, drag=False, task="hover", pyb_freq=240):
+    """what one env step depends on besides the constants: airframe ("cf2x" | "cf2p" | "racer"), action type, sub-steps per step,
+    the drag term, the task ("none" | "hover")"""
+    return SimpleNamespace(model=model, act=act, S=int(S), drag=bool(drag), task=task, h=1.0 / pyb_freq)
+
+
+def consts(C, n, dtype=torch.float64, device="cpu", scales=None):
+    """Per-drone constants [n] from an object with the reference's attribute names (M, L, KF, KM, J, DRAG_COEFF, GRAVITY, HOVER_RPM,
+    MAX_RPM: `DroneParams` or the oracle's `UrdfConstants`); `scales` [9, n]: the plant path's scale factors (the action mapping's
+    HOVER_RPM and the MAX_RPM clip stay nominal, include/gpd.h)."""
+    s = np.ones((9, n)) if scales is None else np.asarray(scales, dtype=np.float64)
+    J = np.diag(np.asarray(C.J, dtype=np.float64))
+    drag = np.asarray(C.DRAG_COEFF, dtype=np.float64)
+    t = lambda v: torch.as_tensor(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)).copy(), dtype=dtype, device=device)   # noqa: E731
+    return SimpleNamespace(
+        M=t(C.M * s[0]), GRAVITY=t(C.G * C.M * s[0]), L=t(C.L), KF=t(C.KF * s[4]), KM=t(C.KM * s[5]),
+        J=torch.stack([t(J[0] * s[1]), t(J[1] * s[2]), t(J[2] * s[3])], dim=1),
+        DRAG=torch.stack([t(drag[0] * s[6]), t(drag[1] * s[6]), t(drag[2] * s[7])], dim=1),
+        HOVER_RPM=t(C.HOVER_RPM), MAX_RPM=t(C.MAX_RPM))
+
+
+def rpm_from_action(c, cfg, a):
+    """[n, A] -> [n, 4] (envs/BaseRLAviary.py:187-239, envs/CtrlAviary.py:140); the clip has zero gradient outside its bounds"""
+    if cfg.act == "rpm":
+        return c.HOVER_RPM[:, None] * (1 + 0.05 * a)
+    if cfg.act == "one_d_rpm":
+        return (c.HOVER_RPM[:, None] * (1 + 0.05 * a)).expand(-1, 4)
+    if cfg.act == "raw_rpm":
+        return torch.minimum(torch.maximum(a, torch.zeros_like(a)), c.MAX_RPM[:, None].expand_as(a))
+    return a
+
+
+def rotation(q):
+    """btMatrix3x3::setRotation: columns-of-rows list R[i][j], each [n]"""
+    x, y, z, w = q.unbind(-1)
+    s = 2.0 / (x * x + y * y + z * z + w * w)
+    xs, ys, zs = x * s, y * s, z * s
+    wx, wy, wz = w * xs, w * ys, w * zs
+    xx, xy, xz = x * xs, x * ys, x * zs
+    yy, yz, zz = y * ys, y * zs, z * zs
+    return [[1.0 - (yy + zz), xy - wz, xz + wy], [xy + wz, 1.0 - (xx + zz), yz - wx], [xz - wy, yz + wx, 1.0 - (xx + yy)]]
+
+
+def euler(q, stats=None):
+    """pybullet_getEulerFromQuaternion with its gimbal branches, NaN-safe selects"""
+    x, y, z, w = q.unbind(-1)
+    sarg = -2.0 * (x * z - w * y)
+    lo, hi = sarg <= -GIMBAL, sarg >= GIMBAL
+    gim = lo | hi
+    if stats is not None:
+        stats["sarg_max"] = max(stats.get("sarg_max", 0.0), float(sarg.detach().abs().max()))
+    one, zero = torch.ones_like(x), torch.zeros_like(x)
+    # regular branch on safe operands where the gimbal branch is taken ...
+    rb = torch.where(gim, one, w * w - x * x - y * y + z * z)
+    yb = torch.where(gim, one, w * w + x * x - y * y - z * z)
+    roll = torch.where(gim, zero, torch.atan2(2.0 * (y * z + w * x), rb))
+    pitch = torch.asin(torch.where(gim, zero, sarg))
+    yaw = torch.atan2(2.0 * (x * y + w * z), yb)
+    # ... and the gimbal branch on safe operands where it is not
+    gy = torch.where(gim, y, one)
+    yaw_g = torch.where(lo, 2.0 * torch.atan2(x, -gy), 2.0 * torch.atan2(-x, gy))
+    pitch = torch.where(lo, torch.full_like(x, -0.5 * math.pi), torch.where(hi, torch.full_like(x, 0.5 * math.pi), pitch))
+    return torch.stack([roll, pitch, torch.where(gim, yaw_g, yaw)], dim=-1)
+
+
+def substep(c, cfg, kin, rpm, drag_sum, stats=None):
+    """envs/BaseAviary.py:831-892 for the supported terms; returns the new (pos, quat, vel, rates) and the observed world ang_v"""
+    pos, quat, vel, w = kin
+    h = cfg.h
+    R = rotation(quat)
+    f = c.KF[:, None] * rpm ** 2
+    fz = f.sum(-1)
+    F = torch.stack([R[0][2] * fz, R[1][2] * fz, R[2][2] * fz - c.GRAVITY], dim=-1)
+    if cfg.drag:
+        F = F - c.DRAG * vel * (drag_sum * (2 * math.pi / 60))[:, None]
+    yaw_t = c.KM[:, None] * rpm ** 2 * (-1.0 if cfg.model == "racer" else 1.0)
+    tz = -yaw_t[:, 0] + yaw_t[:, 1] - yaw_t[:, 2] + yaw_t[:, 3]
+    if cfg.model == "cf2p":
+        tx, ty = (f[:, 1] - f[:, 3]) * c.L, (-f[:, 0] + f[:, 2]) * c.L
+    else:
+        arm = c.L / math.sqrt(2)
+        tx = (f[:, 0] + f[:, 1] - f[:, 2] - f[:, 3]) * arm
+        ty = (-f[:, 0] + f[:, 1] + f[:, 2] - f[:, 3]) * arm
+        if cfg.model == "cf2x":
+            tx = -tx
+    Jw = c.J * w
+    tau = torch.stack([tx, ty, tz], dim=-1) - torch.cross(w, Jw, dim=-1)
+    w = w + h * (tau / c.J)
+    vel = vel + h * (F / c.M[:, None])
+    pos = pos + h * vel
+    n2 = (w * w).sum(-1)
+    turn = n2 > TURN_N2                                            # !np.isclose(|w|, 0)
+    if stats is not None:
+        stats["n2_min"] = min(stats.get("n2_min", math.inf), float(n2.detach().min()))
+    n = torch.sqrt(torch.where(turn, n2, torch.ones_like(n2)))     # (safe: sqrt and the division never see 0)
+    th = n * h / 2
+    qx, qy, qz, qw = quat.unbind(-1)
+    p, q_, r = w.unbind(-1)
+    lam = torch.stack([r * qy - q_ * qz + p * qw, -r * qx + p * qz + q_ * qw, q_ * qx - p * qy + r * qw, -p * qx - q_ * qy - r * qz], dim=-1)
+    qn = torch.cos(th)[:, None] * quat + (torch.sin(th) / n)[:, None] * lam
+    quat_new = torch.where(turn[:, None], qn, quat)
+    ang_v = torch.stack([R[i][0] * p + R[i][1] * q_ + R[i][2] * r for i in range(3)], dim=-1)    # PRE-update rotation, post-update rates
+    return (pos, quat_new, vel, w), ang_v
+
+
+def step(c, cfg, kin, act, prev_sum, target=None, stats=None):
+    """one env step: -> kin', obs12 [n, 12], reward [n], this step's rpm sum (the next step's first drag term sees it)"""
+    rpm = rpm_from_action(c, cfg, act)
+    cur_sum = rpm.sum(-1)
+    ang_v = None
+    for s in range(cfg.S):
+        kin, ang_v = substep(c, cfg, kin, rpm, prev_sum if s == 0 else cur_sum, stats)
+    pos, quat, vel, _ = kin
+    obs = torch.cat([pos, euler(quat, stats), vel, ang_v], dim=-1)
+    if cfg.task == "hover":
+        d2 = ((target - pos) ** 2).sum(-1)
+        arg = 2.0 - d2 * d2
+        if stats is not None:
+            stats["reward_arg_min"] = min(stats.get("reward_arg_min", math.inf), float(arg.detach().min()))
+        reward = torch.where(arg > 0, arg, torch.zeros_like(arg))
+    else:
+        reward = -torch.ones_like(pos[:, 0])
+    return kin, obs, reward, cur_sum
+
+
+def rollout(c, cfg, kin0, actions, first_sum, target=None, stats=None):
+    """K steps: actions [K, n, A] -> obs12 [K, n, 12], reward [K, n], kin_K.  `first_sum` [n]: the rpm sum carried in from before the
+    call (a constant)."""
+    kin, prev, obs, rew = kin0, first_sum, [], []
+    for t in range(actions.shape[0]):
+        kin, o, r, prev = step(c, cfg, kin, actions[t], prev, target, stats)
+        obs.append(o)
+        rew.append(r)
+    return torch.stack(obs), torch.stack(rew), kin
+
+
+def quat_from_rpy(rpy):
+    """btQuaternion::setEulerZYX + normalize, numpy float64 [n, 3] -> [n, 4] xyzw"""
+    h = 0.5 * np.asarray(rpy, dtype=np.float64)
+    cr, sr, cp, sp, cy, sy = np.cos(h[:, 0]), np.sin(h[:, 0]), np.cos(h[:, 1]), np.sin(h[:, 1]), np.cos(h[:, 2]), np.sin(h[:, 2])
+    q = np.stack([sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy, cr * cp * cy + sr * sp * sy], axis=-1)
+    return q / np.linalg.norm(q, axis=-1, keepdims=True)
+
+
+def make_inputs(C, cfg, n, K, seed=0, at_rest=False, outside_clip=True):
+    """The GPU tests' inputs, every value representable in float32 (both precisions start from the same numbers): positions within
+    +-0.15 m of (0, 0, 1), small random attitudes (+-0.2 rad), velocities +-0.25 m/s, body rates +-1 rad/s (`at_rest`: exactly zero,
+    level), actions U(-1, 1) (the raw action types: RPMs around hover, and -- RAW_RPM with `outside_clip` -- a third of them outside
+    [0, MAX_RPM]), the rpm sum carried in, and random cotangents for every output.  numpy float64 arrays."""
+    rng = np.random.default_rng(seed)
+    f32 = lambda x: np.asarray(x, dtype=np.float32).astype(np.float64)     # noqa: E731
+    A = ACT_DIM[cfg.act]
+    pos = f32(np.array([0.0, 0.0, 1.0]) + rng.uniform(-0.15, 0.15, (n, 3)))
+    quat = f32(quat_from_rpy(rng.uniform(-0.2, 0.2, (n, 3))))
+    vel = f32(rng.uniform(-0.25, 0.25, (n, 3)))
+    rates = f32(rng.uniform(-1.0, 1.0, (n, 3)))
+    if at_rest:
+        quat = np.tile(np.array([0.0, 0.0, 0.0, 1.0]), (n, 1))
+        rates = np.zeros((n, 3))
+    u = rng.uniform(-1.0, 1.0, (K, n, A))
+    if cfg.act in ("raw_rpm", "direct_rpm"):
+        u = C.HOVER_RPM * (1 + 0.05 * u)
+        if cfg.act == "raw_rpm" and outside_clip:
+            pick = rng.uniform(size=u.shape)
+            u = np.where(pick < 1 / 6, -0.1 * u, np.where(pick < 1 / 3, C.MAX_RPM + 0.1 * u, u))
+    last_rpm = f32(C.HOVER_RPM * (1 + 0.05 * rng.uniform(-1, 1, (n, 4))))
+    return SimpleNamespace(n=n, K=K, A=A, pos=pos, quat=quat, vel=vel, rates=rates, actions=f32(u), last_rpm=last_rpm,
+                           first_sum=f32(((last_rpm[:, 0] + last_rpm[:, 1]) + last_rpm[:, 2]) + last_rpm[:, 3]),
+                           target=np.tile(np.array([0.0, 0.0, 1.0]), (n, 1)),
+                           g_obs=f32(rng.standard_normal((K, n, 12))), g_rew=f32(rng.standard_normal((K, n))),
+                           g_pos=f32(rng.standard_normal((n, 3))), g_quat=f32(rng.standard_normal((n, 4))),
+                           g_vel=f32(rng.standard_normal((n, 3))), g_rates=f32(rng.standard_normal((n, 3))))
+
+
+GROUPS = ("actions", "pos", "quat", "vel", "rates")
+
+
+def reference_grads(C, cfg, inp, dtype=torch.float64, scales=None, shared_action=False, stats=None, g_obs=True):
+    """Gradients of sum(cotangent * output) over every output with respect to the actions and the four groups of the initial state,
+    by torch autograd over the restatement: dict of numpy float64 arrays (GROUPS).  `shared_action`: actions[0] at every step."""
+    c = consts(C, inp.n, dtype, scales=scales)
+    T = lambda v: torch.as_tensor(v, dtype=dtype)     # noqa: E731
+    leaf = lambda v: T(v).clone().requires_grad_(True)     # noqa: E731
+    kin0 = tuple(leaf(v) for v in (inp.pos, inp.quat, inp.vel, inp.rates))
+    a = leaf(inp.actions[0:1] if shared_action else inp.actions)
+    acts = a.expand(inp.K, -1, -1) if shared_action else a
+    obs, rew, kin_k = rollout(c, cfg, kin0, acts, T(inp.first_sum), T(inp.target), stats)
+    loss = (T(inp.g_rew) * rew).sum() + sum((T(g) * k).sum() for g, k in zip((inp.g_pos, inp.g_quat, inp.g_vel, inp.g_rates), kin_k))
+    if g_obs:
+        loss = loss + (T(inp.g_obs) * obs).sum()
+    grads = torch.autograd.grad(loss, (a,) + kin0, allow_unused=True)
+    out = {k: (torch.zeros_like(x) if g is None else g).detach().to(torch.float64).numpy() for k, g, x in zip(GROUPS, grads, (a,) + kin0)}
+    out["forward"] = (obs.detach(), rew.detach(), tuple(k.detach() for k in kin_k))
+    return out
+
+
+def group_errors(got, want):
+    """max |g - g64| / max |g64| per group (the metric of the tests)"""
+    return {k: float(np.abs(np.asarray(got[k], dtype=np.float64) - want[k]).max() / max(float(np.abs(want[k]).max()), 1e-300)) for k in GROUPS}
+
+
+#: the gradient cases of tests/test_gpu_diff.py (and of the host tests that vouch for the reference on the same inputs): 70 drones
+#: (ld = 128: two waves, one ragged), task hover.  `scales`: plant scale factors drawn within +-20 %.
+GPU_CASES = {
+    "rpm_k32_s1": dict(model="cf2x", act="rpm", S=1, drag=False, K=32),
+    "rpm_k8_s8": dict(model="cf2x", act="rpm", S=8, drag=False, K=8),
+    "drag_k16_s8": dict(model="cf2x", act="rpm", S=8, drag=True, K=16),
+    "one_d_k5_s2": dict(model="cf2x", act="one_d_rpm", S=2, drag=False, K=5),
+    "raw_k3_clipped": dict(model="cf2x", act="raw_rpm", S=1, drag=False, K=3),
+    "cf2p_drag_k8_s2": dict(model="cf2p", act="rpm", S=2, drag=True, K=8),
+    "racer_k8_s1": dict(model="racer", act="rpm", S=1, drag=False, K=8),
+    "plant_drag_k8_s2": dict(model="cf2x", act="rpm", S=2, drag=True, K=8, scales=True),
+}
+
+
+def case(name, n=70, seed=1):
+    """(cfg, K, scales [9, n] or None) of a GPU case"""
+    d = dict(GPU_CASES[name])
+    K, with_scales = d.pop("K"), d.pop("scales", False)
+    scales = np.asarray(np.random.default_rng(seed + 100).uniform(0.8, 1.2, (9, n)), dtype=np.float32).astype(np.float64) if with_scales else None
+    return config(**d), K, scales
