@@ -321,7 +321,7 @@ int rccl_fail(ncclResult_t e, const char* where) {
 
 int need_rccl(const char* who) {
     if (rccl().handle) return 0;
-    return fail(GPD_ENOTSUP, (std::string(who) + ": RCCL is not available (" + rccl().why + ")").c_str());
+    return Refuse{who}(GPD_ENOTSUP, ("RCCL is not available (" + rccl().why + ")").c_str());
 }
 
 }  // namespace
@@ -338,8 +338,7 @@ void gpd_struct_sizes(int32_t out[3]) {
     out[2] = static_cast<int32_t>(sizeof(GpdStepCfg));
 }
 
-static int hist_args(const char* who, const GpdState* st, int32_t n_drones, int32_t D, int32_t A) {
-    auto bad = [&](int code, const char* msg) { return fail(code, (std::string(who) + ": " + msg).c_str()); };
+static int hist_args(Refuse bad, const GpdState* st, int32_t n_drones, int32_t D, int32_t A) {
     if (!st || !st->act_ring || !st->ring_pos || st->hist_len <= 0) return bad(GPD_EINVAL, "state has no action ring (act_ring / ring_pos / hist_len)");
     if (n_drones <= 0 || D <= 0 || n_drones % D != 0 || A <= 0 || A > 4)
         return bad(GPD_EINVAL, "n_drones must be a positive multiple of drones_per_env and act_dim in 1..4");
@@ -358,69 +357,62 @@ static int hist_rows_per_wg(int64_t W) {
 
 int gpd_hist_rows(const GpdState* state, int32_t n_drones, int32_t drones_per_env, int32_t act_dim, const float* obs12,
                   float* obs_full, void* stream) {
-    if (int rc = hist_args("gpd_hist_rows", state, n_drones, drones_per_env, act_dim)) return rc;
-    if (!obs12 || !obs_full) return fail(GPD_EINVAL, "gpd_hist_rows: NULL obs12/obs_full");
+    const Refuse bad{"gpd_hist_rows"};
+    if (int rc = hist_args(bad, state, n_drones, drones_per_env, act_dim)) return rc;
+    if (!obs12 || !obs_full) return bad(GPD_EINVAL, "NULL obs12/obs_full");
     const int64_t W = 12 + static_cast<int64_t>(state->hist_len) * act_dim;
     const int R = hist_rows_per_wg(W);
-    const dim3 grid(static_cast<unsigned>((n_drones + R - 1) / R));
+    const dim3 grid(blocks_for(n_drones, R));
     hipLaunchKernelGGL(gpd_hist_rows_kernel, grid, dim3(kBlock), static_cast<size_t>(R) * (W | 1) * 4,
                        static_cast<hipStream_t>(stream), static_cast<uint32_t>(n_drones), drones_per_env, act_dim, state->hist_len, R,
                        state->act_ring, state->ring_pos, obs12, static_cast<int64_t>(0), static_cast<const float*>(nullptr),
                        static_cast<int64_t>(0), obs_full, static_cast<int64_t>(0));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_hist_rows launch");
-    return 0;
+    return launched(bad.who);
 }
 
 int gpd_full_obs(const GpdState* state, int32_t num_steps, int32_t n_drones, int32_t drones_per_env, int32_t act_dim,
                  const float* obs12, int64_t obs_step_stride, const float* actions, int64_t action_step_stride,
                  float* obs_full, int64_t full_step_stride, void* stream) {
-    if (int rc = hist_args("gpd_full_obs", state, n_drones, drones_per_env, act_dim)) return rc;
-    if (!actions) return fail(GPD_EINVAL, "gpd_full_obs: NULL actions");
-    if (obs_full && !obs12) return fail(GPD_EINVAL, "gpd_full_obs: obs_full needs obs12");
-    if (num_steps <= 0 || num_steps > 65535) return fail(GPD_EINVAL, "gpd_full_obs: num_steps must be in 1..65535");
-    if (obs_step_stride < 0 || action_step_stride < 0 || full_step_stride < 0)
-        return fail(GPD_EINVAL, "gpd_full_obs: strides must be non-negative");
+    const Refuse bad{"gpd_full_obs"};
+    if (int rc = hist_args(bad, state, n_drones, drones_per_env, act_dim)) return rc;
+    if (!actions) return bad(GPD_EINVAL, "NULL actions");
+    if (obs_full && !obs12) return bad(GPD_EINVAL, "obs_full needs obs12");
+    if (num_steps <= 0 || num_steps > 65535) return bad(GPD_EINVAL, "num_steps must be in 1..65535");
+    if (int rc = check_steps(bad, num_steps, obs_step_stride, action_step_stride, full_step_stride)) return rc;
     const int H = state->hist_len;
     const int64_t W = 12 + static_cast<int64_t>(H) * act_dim;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (obs_full) {
         const int R = hist_rows_per_wg(W);
-        const dim3 grid(static_cast<unsigned>((n_drones + R - 1) / R), static_cast<unsigned>(num_steps));
+        const dim3 grid(blocks_for(n_drones, R), static_cast<unsigned>(num_steps));
         hipLaunchKernelGGL(gpd_hist_rows_kernel, grid, dim3(kBlock), static_cast<size_t>(R) * (W | 1) * 4, st,
                            static_cast<uint32_t>(n_drones), drones_per_env, act_dim, H, R, state->act_ring, state->ring_pos, obs12,
                            obs_step_stride, actions, action_step_stride, obs_full, full_step_stride);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "gpd_full_obs launch");
+        if (int rc = launched(bad.who)) return rc;
     }
     // the ring is read by the kernel above and updated by the next two: same stream, in order
     const int keep = num_steps < H ? num_steps : H;
-    const dim3 grid2(static_cast<unsigned>((n_drones + kBlock - 1) / kBlock), static_cast<unsigned>(keep));
+    const dim3 grid2(blocks_for(n_drones, kBlock), static_cast<unsigned>(keep));
     hipLaunchKernelGGL(gpd_hist_push_kernel, grid2, dim3(kBlock), 0, st, num_steps, static_cast<uint32_t>(n_drones),
                        drones_per_env, act_dim, H, actions, action_step_stride, state->act_ring, state->ring_pos);
     const int E = n_drones / drones_per_env;
-    hipLaunchKernelGGL(gpd_hist_advance_kernel, dim3(static_cast<unsigned>((E + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+    hipLaunchKernelGGL(gpd_hist_advance_kernel, dim3(blocks_for(E, kBlock)), dim3(kBlock), 0, st,
                        num_steps, E, H, state->ring_pos);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_full_obs (ring update) launch");
-    return 0;
+    return launched(bad.who, " (ring update) launch");
 }
 
 int gpd_reset(const GpdState* state, const float* init_pose, int32_t init_per_env, const uint8_t* mask,
               int32_t num_envs, int32_t drones_per_env, int32_t reset_pid, float* obs12, void* stream) {
-    if (!state || !state->kin || !state->step_counter || !init_pose)
-        return fail(GPD_EINVAL, "gpd_reset: NULL state/init_pose");
-    if (const char* why = state_layout_problem(state)) return fail(GPD_EINVAL, (std::string("gpd_reset: ") + why).c_str());
-    if (num_envs <= 0 || drones_per_env <= 0) return fail(GPD_EINVAL, "gpd_reset: sizes must be positive");
+    const Refuse bad{"gpd_reset"};
+    if (!state || !state->kin || !state->step_counter || !init_pose) return bad(GPD_EINVAL, "NULL state/init_pose");
+    if (const char* why = state_layout_problem(state)) return bad(GPD_EINVAL, why);
+    if (num_envs <= 0 || drones_per_env <= 0) return bad(GPD_EINVAL, "sizes must be positive");
     const int64_t N = static_cast<int64_t>(num_envs) * drones_per_env;
-    if (state->ld < N) return fail(GPD_EINVAL, "gpd_reset: state.ld < num_envs*drones_per_env");
-    const int64_t blocks = (N + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(gpd_reset_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0,
+    if (state->ld < N) return bad(GPD_EINVAL, "state.ld < num_envs*drones_per_env");
+    hipLaunchKernelGGL(gpd_reset_kernel, dim3(blocks_for(N, kBlock)), dim3(kBlock), 0,
                        static_cast<hipStream_t>(stream), *state, init_pose, init_per_env, mask, num_envs,
                        drones_per_env, reset_pid, obs12);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_reset launch");
-    return 0;
+    return launched(bad.who);
 }
 
 namespace {
@@ -428,18 +420,15 @@ int pid_impl(const char* who, const GpdParams* params, float* pid, int64_t ld, f
              const float* cur_quat, const float* cur_vel, const float* target_pos, const float* target_rpy,
              const float* target_vel, const float* target_rpy_rates, float* rpm, float* pos_e, float* yaw_e,
              int32_t n, void* stream, GpdDone* done) {
-    auto bad = [&](int code, const char* msg) { return fail(code, (std::string(who) + ": " + msg).c_str()); };
+    const Refuse bad{who};
     if (!params || !pid || !cur_pos || !cur_quat || !cur_vel || !target_pos || !rpm) return bad(GPD_EINVAL, "NULL argument");
     if (n <= 0 || ld < n) return bad(GPD_EINVAL, "need 0 < n <= ld");
     if (params->pid_kf <= 0.0f) return bad(GPD_ENOTSUP, "no DSLPID controller for this airframe");
-    const int blocks = (n + kBlock - 1) / kBlock;
     if (done != nullptr) done->used = done->flag != nullptr && n <= 64;          // one wave: see GpdDone
-    hipLaunchKernelGGL(gpd_pid_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), *params, pid,
+    hipLaunchKernelGGL(gpd_pid_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), *params, pid,
                        ld, ctrl_dt, cur_pos, cur_quat, cur_vel, target_pos, target_rpy, target_vel, target_rpy_rates,
                        rpm, pos_e, yaw_e, n, (done != nullptr && done->used) ? done->flag : nullptr, done != nullptr ? done->seq : 0u);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, (std::string(who) + " launch").c_str());
-    return 0;
+    return launched(who);
 }
 }  // namespace
 
@@ -463,19 +452,17 @@ int gpd_pid_sync(const GpdParams* params, float* pid, int64_t ld, float ctrl_dt,
 }
 
 int gpd_state_vectors(const GpdState* state, const float* obs12, float* state20, int32_t n, void* stream) {
-    if (!state || !state->kin || !obs12 || !state20) return fail(GPD_EINVAL, "gpd_state_vectors: NULL argument");
-    if (const char* why = state_layout_problem(state)) return fail(GPD_EINVAL, (std::string("gpd_state_vectors: ") + why).c_str());
-    if (n <= 0 || state->ld < n) return fail(GPD_EINVAL, "gpd_state_vectors: need 0 < n <= state.ld");
-    const int blocks = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(gpd_state20_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), *state,
+    const Refuse bad{"gpd_state_vectors"};
+    if (!state || !state->kin || !obs12 || !state20) return bad(GPD_EINVAL, "NULL argument");
+    if (const char* why = state_layout_problem(state)) return bad(GPD_EINVAL, why);
+    if (n <= 0 || state->ld < n) return bad(GPD_EINVAL, "need 0 < n <= state.ld");
+    hipLaunchKernelGGL(gpd_state20_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), *state,
                        obs12, state20, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_state_vectors launch");
-    return 0;
+    return launched(bad.who);
 }
 
 int gpd_comm_unique_id(uint8_t id[GPD_COMM_ID_BYTES]) {
-    if (!id) return fail(GPD_EINVAL, "gpd_comm_unique_id: NULL id");
+    if (!id) return Refuse{"gpd_comm_unique_id"}(GPD_EINVAL, "NULL id");
     if (int rc = need_rccl("gpd_comm_unique_id")) return rc;
     static_assert(GPD_COMM_ID_BYTES == sizeof(ncclUniqueId), "GPD_COMM_ID_BYTES must match ncclUniqueId");
     ncclUniqueId u;
@@ -486,8 +473,8 @@ int gpd_comm_unique_id(uint8_t id[GPD_COMM_ID_BYTES]) {
 }
 
 int gpd_comm_init(void** comm, const uint8_t id[GPD_COMM_ID_BYTES], int32_t rank, int32_t world_size) {
-    if (!comm || !id) return fail(GPD_EINVAL, "gpd_comm_init: NULL comm/id");
-    if (world_size < 1 || rank < 0 || rank >= world_size) return fail(GPD_EINVAL, "gpd_comm_init: need 0 <= rank < world_size");
+    if (!comm || !id) return Refuse{"gpd_comm_init"}(GPD_EINVAL, "NULL comm/id");
+    if (world_size < 1 || rank < 0 || rank >= world_size) return Refuse{"gpd_comm_init"}(GPD_EINVAL, "need 0 <= rank < world_size");
     if (int rc = need_rccl("gpd_comm_init")) return rc;
     ncclUniqueId u;
     memcpy(&u, id, sizeof(u));
@@ -499,7 +486,7 @@ int gpd_comm_init(void** comm, const uint8_t id[GPD_COMM_ID_BYTES], int32_t rank
 }
 
 int gpd_comm_count(void* comm, int32_t* n_ranks) {
-    if (!comm || !n_ranks) return fail(GPD_EINVAL, "gpd_comm_count: NULL comm/n_ranks");
+    if (!comm || !n_ranks) return Refuse{"gpd_comm_count"}(GPD_EINVAL, "NULL comm/n_ranks");
     if (int rc = need_rccl("gpd_comm_count")) return rc;
     int n = 0;
     ncclResult_t e = rccl().CommCount(static_cast<ncclComm_t>(comm), &n);
@@ -517,8 +504,8 @@ int gpd_comm_destroy(void* comm) {
 }
 
 int gpd_allgather_obs(void* comm, const float* shard, float* full, size_t count, void* stream) {
-    if (!comm || !shard || !full) return fail(GPD_EINVAL, "gpd_allgather_obs: NULL comm/shard/full");
-    if (count == 0) return fail(GPD_EINVAL, "gpd_allgather_obs: count must be positive");
+    if (!comm || !shard || !full) return Refuse{"gpd_allgather_obs"}(GPD_EINVAL, "NULL comm/shard/full");
+    if (count == 0) return Refuse{"gpd_allgather_obs"}(GPD_EINVAL, "count must be positive");
     if (int rc = need_rccl("gpd_allgather_obs")) return rc;
     ncclResult_t e = rccl().AllGather(shard, full, count, ncclFloat32, static_cast<ncclComm_t>(comm),
                                       static_cast<hipStream_t>(stream));
@@ -528,12 +515,12 @@ int gpd_allgather_obs(void* comm, const float* shard, float* full, size_t count,
 
 int gpd_p2p_group(void* comm, const GpdP2P* sends, int32_t n_sends, const GpdP2P* recvs, int32_t n_recvs, void* stream) {
     if (!comm || (n_sends > 0 && !sends) || (n_recvs > 0 && !recvs) || n_sends < 0 || n_recvs < 0)
-        return fail(GPD_EINVAL, "gpd_p2p_group: NULL comm / operation list");
+        return Refuse{"gpd_p2p_group"}(GPD_EINVAL, "NULL comm / operation list");
     if (int rc = need_rccl("gpd_p2p_group")) return rc;
     Rccl& R = rccl();
-    if (!R.GroupStart || !R.GroupEnd || !R.Send || !R.Recv) return fail(GPD_ENOTSUP, "gpd_p2p_group: this RCCL has no ncclSend / ncclRecv / ncclGroup*");
-    for (int i = 0; i < n_sends; ++i) if (!sends[i].ptr || sends[i].count <= 0 || sends[i].peer < 0) return fail(GPD_EINVAL, "gpd_p2p_group: bad send operation");
-    for (int i = 0; i < n_recvs; ++i) if (!recvs[i].ptr || recvs[i].count <= 0 || recvs[i].peer < 0) return fail(GPD_EINVAL, "gpd_p2p_group: bad receive operation");
+    if (!R.GroupStart || !R.GroupEnd || !R.Send || !R.Recv) return Refuse{"gpd_p2p_group"}(GPD_ENOTSUP, "this RCCL has no ncclSend / ncclRecv / ncclGroup*");
+    for (int i = 0; i < n_sends; ++i) if (!sends[i].ptr || sends[i].count <= 0 || sends[i].peer < 0) return Refuse{"gpd_p2p_group"}(GPD_EINVAL, "bad send operation");
+    for (int i = 0; i < n_recvs; ++i) if (!recvs[i].ptr || recvs[i].count <= 0 || recvs[i].peer < 0) return Refuse{"gpd_p2p_group"}(GPD_EINVAL, "bad receive operation");
     if (n_sends + n_recvs == 0) return 0;
     ncclComm_t c = static_cast<ncclComm_t>(comm);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -552,7 +539,7 @@ int gpd_p2p_group(void* comm, const GpdP2P* sends, int32_t n_sends, const GpdP2P
 
 int gpd_debug_status(uint32_t out[4], int32_t reset, void* stream) {
 #ifdef GPD_DEBUG_BOUNDS
-    if (!out) return fail(GPD_EINVAL, "gpd_debug_status: NULL out");
+    if (!out) return Refuse{"gpd_debug_status"}(GPD_EINVAL, "NULL out");
     // every unit whose kernels carry checks keeps its own record: the first one that holds a violation is reported, the counts add up
     out[0] = out[1] = out[2] = out[3] = 0u;
     int (*const readers[])(unsigned int*, int, void*) = {gpd_detail_dbg_read_step, gpd_detail_dbg_read_swarm, gpd_detail_dbg_read_policy};
@@ -566,12 +553,12 @@ int gpd_debug_status(uint32_t out[4], int32_t reset, void* stream) {
     return 0;
 #else
     (void)out; (void)reset; (void)stream;
-    return fail(GPD_ENOTSUP, "gpd_debug_status: this is a release build (no -DGPD_DEBUG_BOUNDS)");
+    return Refuse{"gpd_debug_status"}(GPD_ENOTSUP, "this is a release build (no -DGPD_DEBUG_BOUNDS)");
 #endif
 }
 
 int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
-    if (!shader_ghz) return fail(GPD_EINVAL, "gpd_clock_probe: NULL shader_ghz");
+    if (!shader_ghz) return Refuse{"gpd_clock_probe"}(GPD_EINVAL, "NULL shader_ghz");
     hipStream_t st = static_cast<hipStream_t>(stream);
     int dev = 0, wall_khz = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -590,7 +577,7 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
     }
     (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(e, "gpd_clock_probe");
-    if (h[1] == 0) return fail(GPD_ENOTSUP, "gpd_clock_probe: the wall clock did not advance");
+    if (h[1] == 0) return Refuse{"gpd_clock_probe"}(GPD_ENOTSUP, "the wall clock did not advance");
     const double secs = static_cast<double>(h[1]) / (static_cast<double>(wall_khz) * 1e3);
     *shader_ghz = static_cast<double>(h[0]) / secs * 1e-9;
     if (ns_per_fma) *ns_per_fma = secs * 1e9 / (static_cast<double>(iters) * 64.0);

@@ -348,41 +348,31 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_kernel(const GpdParams
     planes_store(g_kin, ld, n, A);
 }
 
-// what the two entries refuse, before any device work: `who` and the reason in the message
-int diff_unsupported(const char* who, const GpdStepCfg* cfg) {
-    auto no = [&](const char* why) { return fail(GPD_ENOTSUP, (std::string(who) + ": " + why).c_str()); };
-    if (cfg->drones_per_env != 1) return no("aviaries of more than one drone are not differentiable (drones_per_env must be 1)");
-    if (cfg->task != GPD_TASK_NONE && cfg->task != GPD_TASK_HOVER) return no("task must be GPD_TASK_NONE or GPD_TASK_HOVER");
-    if (cfg->act_type != GPD_ACT_RPM && cfg->act_type != GPD_ACT_ONE_D_RPM && cfg->act_type != GPD_ACT_RAW_RPM && cfg->act_type != GPD_ACT_DIRECT_RPM)
-        return no("the DSLPID action types are not differentiable (RPM, ONE_D_RPM, RAW_RPM and DIRECT_RPM are)");
-    if (cfg->physics_flags & ~static_cast<uint32_t>(GPD_PHYS_DRAG))
-        return no("physics_flags other than GPD_PHYS_DRAG are not differentiable (ground effect, downwash, ground plane, damping)");
-    if (cfg->auto_reset) return no("auto_reset inside a differentiated call is not supported");
-    return 0;
-}
-
-int diff_sizes(const char* who, const GpdStepCfg* cfg, int32_t num_steps, int64_t ld) {
-    auto bad = [&](int code, const char* why) { return fail(code, (std::string(who) + ": " + why).c_str()); };
-    if (num_steps <= 0) return bad(GPD_EINVAL, "num_steps must be positive");
-    if (cfg->num_envs <= 0 || cfg->drones_per_env <= 0 || cfg->substeps <= 0)
-        return bad(GPD_EINVAL, "num_envs, drones_per_env and substeps must be positive");
-    if (cfg->act_type < GPD_ACT_RPM || cfg->act_type > GPD_ACT_DIRECT_RPM) return bad(GPD_EINVAL, "unknown act_type");
-    if (cfg->task < GPD_TASK_NONE || cfg->task > GPD_TASK_MULTIHOVER) return bad(GPD_EINVAL, "unknown task");
-    if (cfg->physics_flags & ~31u) return bad(GPD_EINVAL, "unknown physics flag");
+// What the three entries check of the configuration and refuse of it, before any device work: the span and the sizes, then what is
+// not differentiable.  `ld` comes without the state in two of them.
+int diff_cfg(Refuse bad, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, int64_t stride0 = 0, int64_t stride1 = 0, int64_t stride2 = 0) {
+    if (int rc = check_steps(bad, num_steps, stride0, stride1, stride2)) return rc;
+    if (int rc = check_ranges(bad, cfg)) return rc;
+    if (int rc = check_positive(bad, cfg)) return rc;
+    if (int rc = check_flags(bad, cfg)) return rc;
     if (ld <= 0 || ld > 0xffffffffLL) return bad(GPD_EINVAL, "ld must be in 1 .. 2^32 - 1 (floats)");
-    if (ld < static_cast<int64_t>(cfg->num_envs) * cfg->drones_per_env) return bad(GPD_EINVAL, "ld < num_envs*drones_per_env");
-    if (static_cast<int64_t>(cfg->num_envs) * cfg->drones_per_env > (1LL << 26)) return bad(GPD_ERANGE, "more than 2^26 drones per launch (32-bit byte offsets)");
+    if (int rc = check_extent(bad, static_cast<int64_t>(cfg->num_envs) * cfg->drones_per_env, ld, "ld")) return rc;
+    if (cfg->drones_per_env != 1) return bad(GPD_ENOTSUP, "aviaries of more than one drone are not differentiable (drones_per_env must be 1)");
+    if (cfg->task != GPD_TASK_NONE && cfg->task != GPD_TASK_HOVER) return bad(GPD_ENOTSUP, "task must be GPD_TASK_NONE or GPD_TASK_HOVER");
+    if (cfg->act_type != GPD_ACT_RPM && cfg->act_type != GPD_ACT_ONE_D_RPM && cfg->act_type != GPD_ACT_RAW_RPM && cfg->act_type != GPD_ACT_DIRECT_RPM)
+        return bad(GPD_ENOTSUP, "the DSLPID action types are not differentiable (RPM, ONE_D_RPM, RAW_RPM and DIRECT_RPM are)");
+    if (cfg->physics_flags & ~static_cast<uint32_t>(GPD_PHYS_DRAG))
+        return bad(GPD_ENOTSUP, "physics_flags other than GPD_PHYS_DRAG are not differentiable (ground effect, downwash, ground plane, damping)");
+    if (cfg->auto_reset) return bad(GPD_ENOTSUP, "auto_reset inside a differentiated call is not supported");
     return 0;
 }
 
-// act_type / physics flags / plant table -> <EXT, AW, PLANT>: every kernel of this file is launched from here
+// act_type -> the action row's width, then <EXT, PLANT>: every kernel of this file is launched as launch(ext, aw, plant)
 template <class F>
-hipError_t diff_dispatch(const GpdStepCfg& c, bool plant, F&& launch) {
-    auto with = [&](auto ext, auto aw) {
-        return plant ? launch(ext, aw, Const<true>{}) : launch(ext, aw, Const<false>{});
-    };
-    auto with_ext = [&](auto aw) { return c.physics_flags != 0 ? with(Const<true>{}, aw) : with(Const<false>{}, aw); };
-    return c.act_type == GPD_ACT_ONE_D_RPM ? with_ext(Const<1>{}) : with_ext(Const<4>{});
+void diff_dispatch(const GpdStepCfg& c, bool plant, F&& launch) {
+    with_ext_plant(c.physics_flags != 0, plant, [&](auto ext, auto pl) {
+        if (c.act_type == GPD_ACT_ONE_D_RPM) launch(ext, Const<1>{}, pl); else launch(ext, Const<4>{}, pl);
+    });
 }
 
 }  // namespace
@@ -390,12 +380,11 @@ hipError_t diff_dispatch(const GpdStepCfg& c, bool plant, F&& launch) {
 extern "C" {
 
 int gpd_rollout_tape_floats(const GpdStepCfg* cfg, int32_t num_steps, int64_t ld, int64_t* floats_out) {
-    const char* who = "gpd_rollout_tape_floats";
-    if (!cfg || !floats_out) return fail(GPD_EINVAL, "gpd_rollout_tape_floats: NULL cfg/floats_out");
-    if (int rc = diff_sizes(who, cfg, num_steps, ld)) return rc;
-    if (int rc = diff_unsupported(who, cfg)) return rc;
+    const Refuse bad{"gpd_rollout_tape_floats"};
+    if (!cfg || !floats_out) return bad(GPD_EINVAL, "NULL cfg/floats_out");
+    if (int rc = diff_cfg(bad, cfg, ld, num_steps)) return rc;
     const int64_t rows = 13 * static_cast<int64_t>(num_steps) + 1;           // 13 per env step + the first drag term's rpm sum
-    if (rows > INT64_MAX / ld) return fail(GPD_ERANGE, "gpd_rollout_tape_floats: the tape does not fit 2^63 floats");
+    if (rows > INT64_MAX / ld) return bad(GPD_ERANGE, "the tape does not fit 2^63 floats");
     *floats_out = rows * ld;
     return 0;
 }
@@ -403,63 +392,50 @@ int gpd_rollout_tape_floats(const GpdStepCfg* cfg, int32_t num_steps, int64_t ld
 int gpd_rollout_tape(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, int32_t num_steps, const float* actions,
                      int64_t action_step_stride, const float* target_pos, float* obs12, int64_t obs_step_stride, float* reward,
                      uint8_t* terminated, uint8_t* truncated, int64_t env_step_stride, const float* plant_rows, float* tape, void* stream) {
-    const char* who = "gpd_rollout_tape";
-    auto bad = [&](int code, const char* msg) { return fail(code, (std::string(who) + ": " + msg).c_str()); };
+    const Refuse bad{"gpd_rollout_tape"};
     if (!params || !state || !cfg) return bad(GPD_EINVAL, "NULL params/state/cfg");
-    if (!state->kin || !state->step_counter) return bad(GPD_EINVAL, "NULL state.kin/step_counter");
-    if (const char* why = state_layout_problem(state)) return bad(GPD_EINVAL, why);
+    if (int rc = check_state(bad, state)) return rc;
     if (!actions || !obs12 || !reward || !terminated || !truncated || !tape)
         return bad(GPD_EINVAL, "NULL actions/obs12/reward/terminated/truncated/tape");
-    if (action_step_stride < 0 || obs_step_stride < 0 || env_step_stride < 0) return bad(GPD_EINVAL, "strides must be non-negative");
-    if (int rc = diff_sizes(who, cfg, num_steps, state->ld)) return rc;
-    if (int rc = diff_unsupported(who, cfg)) return rc;
+    if (int rc = diff_cfg(bad, cfg, state->ld, num_steps, action_step_stride, obs_step_stride, env_step_stride)) return rc;
     if (state->dw_force) return bad(GPD_ENOTSUP, "state.dw_force (downwash computed outside the kernel) is not differentiable");
-    if ((cfg->physics_flags & GPD_PHYS_DRAG) && !state->last_rpm) return bad(GPD_EINVAL, "GPD_PHYS_DRAG needs state.last_rpm");
-    if (cfg->task != GPD_TASK_NONE && !target_pos) return bad(GPD_EINVAL, "task needs target_pos");
-    if ((reinterpret_cast<uintptr_t>(tape) & 15u) != 0) return bad(GPD_EINVAL, "tape must be 16-byte aligned");
-    if (plant_rows && (reinterpret_cast<uintptr_t>(plant_rows) & 15u) != 0) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
+    if (int rc = check_needs(bad, params, state, cfg, target_pos, nullptr)) return rc;
+    if (misaligned16(tape)) return bad(GPD_EINVAL, "tape must be 16-byte aligned");
+    if (misaligned16(plant_rows)) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
     GpdStepCfg c = *cfg;
     GpdState s = *state;
     s.act_ring = nullptr;                                      // (a rollout never pushes into the action ring itself)
-    if (c.task == GPD_TASK_NONE) { target_pos = state->kin; c.target_per_env = 0; }      // a readable dummy, as in gpd_rollout
-    const dim3 grid(static_cast<unsigned>((static_cast<int64_t>(c.num_envs) + kBlock - 1) / kBlock));
-    const hipError_t e = diff_dispatch(c, plant_rows != nullptr, [&](auto ext, auto aw, auto pl) {
+    dummy_target(c, target_pos, state->kin);
+    const dim3 grid(blocks_for(c.num_envs, kBlock));
+    diff_dispatch(c, plant_rows != nullptr, [&](auto ext, auto aw, auto pl) {
         hipLaunchKernelGGL((gpd_rollout_tape_kernel<decltype(ext)::value, decltype(aw)::value, decltype(pl)::value>), grid, dim3(kBlock), 0,
                            static_cast<hipStream_t>(stream), *params, s, c, num_steps, action_step_stride, obs_step_stride, env_step_stride, actions, target_pos, obs12, reward, terminated, truncated,
                            plant_rows, tape);
-        return hipGetLastError();
     });
-    if (e != hipSuccess) return hip_fail(e, "gpd_rollout_tape launch");
-    return 0;
+    return launched(bad.who);
 }
 
 int gpd_rollout_vjp(const GpdParams* params, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, const float* actions,
                     int64_t action_step_stride, const float* target_pos, const float* plant_rows, const float* tape,
                     const float* g_obs12, int64_t obs_step_stride, const float* g_reward, int64_t env_step_stride, float* g_kin,
                     float* g_actions, void* stream) {
-    const char* who = "gpd_rollout_vjp";
-    auto bad = [&](int code, const char* msg) { return fail(code, (std::string(who) + ": " + msg).c_str()); };
+    const Refuse bad{"gpd_rollout_vjp"};
     if (!params || !cfg) return bad(GPD_EINVAL, "NULL params/cfg");
     if (!actions || !tape || !g_kin || !g_actions) return bad(GPD_EINVAL, "NULL actions/tape/g_kin/g_actions");
-    if (action_step_stride < 0 || obs_step_stride < 0 || env_step_stride < 0) return bad(GPD_EINVAL, "strides must be non-negative");
-    if (int rc = diff_sizes(who, cfg, num_steps, ld)) return rc;
-    if (int rc = diff_unsupported(who, cfg)) return rc;
-    if (cfg->task != GPD_TASK_NONE && !target_pos) return bad(GPD_EINVAL, "task needs target_pos");
-    if (((reinterpret_cast<uintptr_t>(tape) | reinterpret_cast<uintptr_t>(g_kin)) & 15u) != 0)
-        return bad(GPD_EINVAL, "tape and g_kin must be 16-byte aligned");
-    if (plant_rows && (reinterpret_cast<uintptr_t>(plant_rows) & 15u) != 0) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(g_actions) & 15u) != 0) return bad(GPD_EINVAL, "g_actions must be 16-byte aligned");
+    if (int rc = diff_cfg(bad, cfg, ld, num_steps, action_step_stride, obs_step_stride, env_step_stride)) return rc;
+    if (int rc = check_needs(bad, params, nullptr, cfg, target_pos, nullptr)) return rc;
+    if (misaligned16(tape) || misaligned16(g_kin)) return bad(GPD_EINVAL, "tape and g_kin must be 16-byte aligned");
+    if (misaligned16(plant_rows)) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
+    if (misaligned16(g_actions)) return bad(GPD_EINVAL, "g_actions must be 16-byte aligned");
     GpdStepCfg c = *cfg;
-    if (c.task == GPD_TASK_NONE) { target_pos = tape; c.target_per_env = 0; }          // a readable dummy
-    const dim3 grid(static_cast<unsigned>((static_cast<int64_t>(c.num_envs) + kBlock - 1) / kBlock));
-    const hipError_t e = diff_dispatch(c, plant_rows != nullptr, [&](auto ext, auto aw, auto pl) {
+    dummy_target(c, target_pos, tape);
+    const dim3 grid(blocks_for(c.num_envs, kBlock));
+    diff_dispatch(c, plant_rows != nullptr, [&](auto ext, auto aw, auto pl) {
         hipLaunchKernelGGL((gpd_rollout_vjp_kernel<decltype(ext)::value, decltype(aw)::value, decltype(pl)::value>), grid, dim3(kBlock), 0,
                            static_cast<hipStream_t>(stream), *params, c, ld, num_steps, actions, action_step_stride, target_pos, plant_rows,
                            tape, g_obs12, obs_step_stride, g_reward, env_step_stride, g_kin, g_actions);
-        return hipGetLastError();
     });
-    if (e != hipSuccess) return hip_fail(e, "gpd_rollout_vjp launch");
-    return 0;
+    return launched(bad.who);
 }
 
 }  // extern "C"

@@ -169,10 +169,74 @@ int hip_fail(hipError_t e, const char* where) {
 // What the kernels assume about GpdState.kin beyond "not NULL" (include/gpd.h, the plane layout): the planes are moved with
 // 16-byte vector accesses, so kin must be 16-byte aligned (ld is counted in floats, so every plane then is -- the planes start
 // at multiples of 4 ld floats), and the pitch travels to the kernels as a 32-bit argument.  nullptr = fine.
+[[maybe_unused]] bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
 [[maybe_unused]] const char* state_layout_problem(const GpdState* s) {
-    if ((reinterpret_cast<uintptr_t>(s->kin) & 15u) != 0) return "state.kin must be 16-byte aligned (the planes are read and written as float4)";
+    if (misaligned16(s->kin)) return "state.kin must be 16-byte aligned (the planes are read and written as float4)";
     if (s->ld <= 0 || s->ld > 0xffffffffLL) return "state.ld must be in 1 .. 2^32 - 1 (floats)";
     return nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The host side of an entry: what it refuses, its launch, `launched`.  An entry holds a Refuse with its own name -- every message
+// reads "<entry>: <reason>", built only when the entry refuses (an accepted call allocates nothing) -- and runs the shared checks
+// below in the order ITS codes need: what narrows an entry (GPD_ENOTSUP) stays in the entry, in front of the shared check it must
+// win against.  tests/c/arg_errors.expected is the recorded table of every entry's refusals.
+// ------------------------------------------------------------------------------------------------
+struct Refuse {
+    const char* who;
+    int operator()(int code, const char* msg, const char* more = "") const { return fail(code, (std::string(who) + ": " + msg + more).c_str()); }
+};
+
+// after an entry's last launch: 0, or the runtime's error under "<who><what>"
+[[maybe_unused]] int launched(const char* who, const char* what = " launch") {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, (std::string(who) + what).c_str());
+}
+[[maybe_unused]] unsigned blocks_for(int64_t n, int64_t per) { return static_cast<unsigned>((n + per - 1) / per); }
+
+[[maybe_unused]] int check_state(Refuse bad, const GpdState* s) {
+    if (!s->kin || !s->step_counter) return bad(GPD_EINVAL, "NULL state.kin/step_counter");
+    const char* const why = state_layout_problem(s);
+    return why ? bad(GPD_EINVAL, why) : 0;
+}
+[[maybe_unused]] int check_steps(Refuse bad, int32_t num_steps, int64_t stride0 = 0, int64_t stride1 = 0, int64_t stride2 = 0) {
+    if (num_steps <= 0) return bad(GPD_EINVAL, "num_steps must be positive");
+    return (stride0 < 0 || stride1 < 0 || stride2 < 0) ? bad(GPD_EINVAL, "strides must be non-negative") : 0;
+}
+[[maybe_unused]] int check_ranges(Refuse bad, const GpdStepCfg* cfg) {
+    if (cfg->act_type < GPD_ACT_RPM || cfg->act_type > GPD_ACT_DIRECT_RPM) return bad(GPD_EINVAL, "unknown act_type");
+    return (cfg->task < GPD_TASK_NONE || cfg->task > GPD_TASK_MULTIHOVER) ? bad(GPD_EINVAL, "unknown task") : 0;
+}
+[[maybe_unused]] int check_positive(Refuse bad, const GpdStepCfg* cfg) {
+    const bool ok = cfg->num_envs > 0 && cfg->drones_per_env > 0 && cfg->substeps > 0;
+    return ok ? 0 : bad(GPD_EINVAL, "num_envs, drones_per_env and substeps must be positive");
+}
+[[maybe_unused]] int check_flags(Refuse bad, const GpdStepCfg* cfg) { return (cfg->physics_flags & ~31u) ? bad(GPD_EINVAL, "unknown physics flag") : 0; }
+// N drones in rows of `ld` floats; `pitch`: what the caller knows `ld` as ("ld" where an entry takes the pitch without the state)
+[[maybe_unused]] int check_extent(Refuse bad, int64_t N, int64_t ld, const char* pitch = "state.ld") {
+    if (ld < N) return bad(GPD_EINVAL, pitch, " < num_envs*drones_per_env");
+    return N > (1LL << 26) ? bad(GPD_ERANGE, "more than 2^26 drones per launch (32-bit byte offsets)") : 0;
+}
+// what a configuration needs of the optional pointers (`state`: NULL where the entry has none)
+[[maybe_unused]] int check_needs(Refuse bad, const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, const float* target_pos,
+                                 const float* init_pose) {
+    const bool pid = cfg->act_type == GPD_ACT_PID || cfg->act_type == GPD_ACT_VEL || cfg->act_type == GPD_ACT_ONE_D_PID;
+    if (pid && state && !state->pid) return bad(GPD_EINVAL, "PID action type needs state.pid");
+    if (pid && params->pid_kf <= 0.0f) return bad(GPD_ENOTSUP, "no DSLPID controller for this airframe (CF2X/CF2P only)");
+    if ((cfg->physics_flags & GPD_PHYS_DRAG) && state && !state->last_rpm) return bad(GPD_EINVAL, "GPD_PHYS_DRAG needs state.last_rpm");
+    if (cfg->task != GPD_TASK_NONE && !target_pos) return bad(GPD_EINVAL, "task needs target_pos");
+    return (cfg->auto_reset && !init_pose) ? bad(GPD_EINVAL, "auto_reset needs init_pose") : 0;
+}
+// GPD_TASK_NONE never uses the target: hand the kernel a readable dummy so that its load section is branch-free
+[[maybe_unused]] void dummy_target(GpdStepCfg& c, const float*& target_pos, const float* readable) {
+    if (c.task == GPD_TASK_NONE) { target_pos = readable; c.target_per_env = 0; }
+}
+// any physics flag / a plant table -> f(Const<EXT>{}, Const<PLANT>{}): the run-time choice of the two template arguments the kernels share
+template <class F>
+auto with_ext_plant(bool ext, bool plant, F&& f) {
+    if (plant) return ext ? f(Const<true>{}, Const<true>{}) : f(Const<false>{}, Const<true>{});
+    return ext ? f(Const<true>{}, Const<false>{}) : f(Const<false>{}, Const<false>{});
 }
 
 // ------------------------------------------------------------------------------------------------

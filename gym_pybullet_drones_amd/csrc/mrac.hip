@@ -327,12 +327,10 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_mrac_kernel(
     reinterpret_cast<float4*>(rpm_carry)[n] = act;
 }
 
-bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-
 }  // namespace
 
 int gpd_sizeof_mrac(int32_t* size_out) {
-    if (!size_out) return fail(GPD_EINVAL, "gpd_sizeof_mrac: NULL size_out");
+    if (!size_out) return Refuse{"gpd_sizeof_mrac"}(GPD_EINVAL, "NULL size_out");
     *size_out = static_cast<int32_t>(sizeof(GpdMrac));
     return 0;
 }
@@ -340,28 +338,27 @@ int gpd_sizeof_mrac(int32_t* size_out) {
 int gpd_mrac(const GpdMrac* mrac, float* mrac_state, int32_t* counter, int64_t ld, float ctrl_dt, const float* cur_pos,
              const float* cur_quat, const float* cur_vel, const float* cur_ang_vel, const float* target_pos, const float* target_rpy,
              const float* target_vel, const float* target_rpy_rates, float* rpm, float* pos_e, float* rpy_e, int32_t n, void* stream) {
+    const Refuse bad{"gpd_mrac"};
     if (!mrac || !mrac_state || !counter || !cur_pos || !cur_quat || !cur_vel || !cur_ang_vel || !target_pos || !rpm)
-        return fail(GPD_EINVAL, "gpd_mrac: NULL argument");
-    if (n <= 0 || ld < n) return fail(GPD_EINVAL, "gpd_mrac: need 0 < n <= ld");
-    if (n > (1 << 26)) return fail(GPD_ERANGE, "gpd_mrac: more than 2^26 controllers per launch (32-bit byte offsets)");
-    if (!(ctrl_dt > 0.0f)) return fail(GPD_EINVAL, "gpd_mrac: ctrl_dt must be positive");
-    if (misaligned16(cur_quat) || misaligned16(rpm)) return fail(GPD_EINVAL, "gpd_mrac: cur_quat and rpm must be 16-byte aligned");
-    const int blocks = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(gpd_mrac_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), *mrac, mrac_state, counter, ld,
+        return bad(GPD_EINVAL, "NULL argument");
+    if (n <= 0 || ld < n) return bad(GPD_EINVAL, "need 0 < n <= ld");
+    if (n > (1 << 26)) return bad(GPD_ERANGE, "more than 2^26 controllers per launch (32-bit byte offsets)");
+    if (!(ctrl_dt > 0.0f)) return bad(GPD_EINVAL, "ctrl_dt must be positive");
+    if (misaligned16(cur_quat) || misaligned16(rpm)) return bad(GPD_EINVAL, "cur_quat and rpm must be 16-byte aligned");
+    hipLaunchKernelGGL(gpd_mrac_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), *mrac, mrac_state, counter, ld,
                        ctrl_dt, cur_pos, cur_quat, cur_vel, cur_ang_vel, target_pos, target_rpy, target_vel, target_rpy_rates, rpm,
                        pos_e, rpy_e, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_mrac launch");
-    return 0;
+    return launched(bad.who);
 }
 
 int gpd_mrac_reset(float* mrac_state, int32_t* counter, int64_t ld, const GpdMrac* mrac, const uint8_t* mask, int32_t n,
                    int32_t restore_gains, void* stream) {
-    if (!mrac_state || !counter) return fail(GPD_EINVAL, "gpd_mrac_reset: NULL mrac_state/counter");
-    if (restore_gains && !mrac) return fail(GPD_EINVAL, "gpd_mrac_reset: restore_gains needs the design (NULL mrac)");
-    if (n <= 0 || ld < n) return fail(GPD_EINVAL, "gpd_mrac_reset: need 0 < n <= ld");
-    if (n > (1 << 26)) return fail(GPD_ERANGE, "gpd_mrac_reset: more than 2^26 controllers per launch (32-bit byte offsets)");
-    const int blocks = (n + kBlock - 1) / kBlock;
+    const Refuse bad{"gpd_mrac_reset"};
+    if (!mrac_state || !counter) return bad(GPD_EINVAL, "NULL mrac_state/counter");
+    if (restore_gains && !mrac) return bad(GPD_EINVAL, "restore_gains needs the design (NULL mrac)");
+    if (n <= 0 || ld < n) return bad(GPD_EINVAL, "need 0 < n <= ld");
+    if (n > (1 << 26)) return bad(GPD_ERANGE, "more than 2^26 controllers per launch (32-bit byte offsets)");
+    const unsigned blocks = blocks_for(n, kBlock);
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(gpd_mrac_reset_kernel, dim3(blocks), dim3(kBlock), 0, st, counter, mask, n);
     if (restore_gains) {
@@ -370,32 +367,29 @@ int gpd_mrac_reset(float* mrac_state, int32_t* counter, int64_t ld, const GpdMra
         std::memcpy(g.v + 48, mrac->Kr0, 16 * sizeof(float));
         hipLaunchKernelGGL(gpd_mrac_restore_kernel, dim3(blocks), dim3(kBlock), 0, st, mrac_state, ld, g, mask, n);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_mrac_reset launch");
-    return 0;
+    return launched(bad.who);
 }
 
 int gpd_rollout_mrac(const GpdParams* params, const GpdMrac* mrac, const GpdState* state, const GpdStepCfg* cfg, float* mrac_state,
                      int32_t* counter, int64_t mrac_ld, const float* targets, int64_t target_step_stride, float* rpm_carry,
                      const float* plant_rows, float* obs12, int64_t obs_step_stride, int32_t num_steps, void* stream) {
-    auto bad = [](int code, const char* msg) { return fail(code, (std::string("gpd_rollout_mrac: ") + msg).c_str()); };
+    const Refuse bad{"gpd_rollout_mrac"};
     if (!params || !mrac || !state || !cfg) return bad(GPD_EINVAL, "NULL params/mrac/state/cfg");
-    if (!state->kin || !state->step_counter) return bad(GPD_EINVAL, "NULL state.kin/step_counter");
+    if (int rc = check_state(bad, state)) return rc;
     if (!mrac_state || !counter || !targets || !rpm_carry || !obs12) return bad(GPD_EINVAL, "NULL mrac_state/counter/targets/rpm_carry/obs12");
-    if (const char* why = state_layout_problem(state)) return bad(GPD_EINVAL, why);
-    if (cfg->num_envs <= 0 || cfg->substeps <= 0) return bad(GPD_EINVAL, "num_envs and substeps must be positive");
-    if (num_steps <= 0) return bad(GPD_EINVAL, "num_steps must be positive");
-    if (cfg->physics_flags & ~31u) return bad(GPD_EINVAL, "unknown physics flag");
+    if (int rc = check_steps(bad, num_steps, target_step_stride, obs_step_stride)) return rc;
+    if (int rc = check_flags(bad, cfg)) return rc;
+    // what the kernel serves, in front of the remaining shared checks (a configuration outside it answers GPD_ENOTSUP)
     if (cfg->drones_per_env != 1) return bad(GPD_ENOTSUP, "aviaries of one drone only (gpd_step + gpd_mrac serve every shape)");
     if (cfg->task != GPD_TASK_NONE || cfg->auto_reset) return bad(GPD_ENOTSUP, "GPD_TASK_NONE without auto-reset only");
     if (cfg->act_type != GPD_ACT_RAW_RPM && cfg->act_type != GPD_ACT_DIRECT_RPM)
         return bad(GPD_ENOTSUP, "act_type GPD_ACT_RAW_RPM or GPD_ACT_DIRECT_RPM (the controller's output is RPMs)");
     if ((cfg->physics_flags & GPD_PHYS_DW) || state->dw_force) return bad(GPD_ENOTSUP, "downwash needs mates (gpd_step + gpd_mrac)");
+    if (int rc = check_positive(bad, cfg)) return rc;
     const int64_t N = cfg->num_envs;
     if (state->ld < N || mrac_ld < N) return bad(GPD_EINVAL, "state.ld / mrac_ld < num_envs");
-    if (N > (1LL << 26)) return bad(GPD_ERANGE, "more than 2^26 drones per launch (32-bit byte offsets)");
-    if ((cfg->physics_flags & GPD_PHYS_DRAG) && !state->last_rpm) return bad(GPD_EINVAL, "GPD_PHYS_DRAG needs state.last_rpm");
-    if (target_step_stride < 0 || obs_step_stride < 0) return bad(GPD_EINVAL, "strides must be non-negative");
+    if (int rc = check_extent(bad, N, state->ld)) return rc;
+    if (int rc = check_needs(bad, params, state, cfg, nullptr, nullptr)) return rc;
     if ((target_step_stride != 0 && target_step_stride < 12 * N) || (obs_step_stride != 0 && obs_step_stride < 12 * N))
         return bad(GPD_EINVAL, "a non-zero step stride must be at least 12*num_envs floats");
     if ((target_step_stride & 3) || (obs_step_stride & 3)) return bad(GPD_EINVAL, "step strides must be multiples of 4 floats (16-byte rows)");
@@ -405,16 +399,12 @@ int gpd_rollout_mrac(const GpdParams* params, const GpdMrac* mrac, const GpdStat
     GpdStepCfg C = *cfg;
     C.target_per_env = 0; C.init_per_env = 0; C.auto_reset = 0; C.task = GPD_TASK_NONE; C.drones_per_env = 1;
     const bool ext = (C.physics_flags & 31u) != 0;
-    const dim3 grid(static_cast<unsigned>((N + kBlock - 1) / kBlock));
+    const dim3 grid(blocks_for(N, kBlock));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    auto launch = [&](auto ext_, auto plant_) {
+    with_ext_plant(ext, plant_rows != nullptr, [&](auto ext_, auto plant_) {
         hipLaunchKernelGGL((gpd_rollout_mrac_kernel<decltype(ext_)::value, decltype(plant_)::value>), grid, dim3(kBlock), 0, st, *params, *mrac,
                            state->kin, state->last_rpm, state->step_counter, state->bad, static_cast<uint32_t>(state->ld), C, mrac_state, counter,
                            mrac_ld, targets, target_step_stride, rpm_carry, plant_rows, obs12, obs_step_stride, num_steps);
-    };
-    if (plant_rows) { if (ext) launch(Const<true>{}, Const<true>{}); else launch(Const<false>{}, Const<true>{}); }
-    else { if (ext) launch(Const<true>{}, Const<false>{}); else launch(Const<false>{}, Const<false>{}); }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_rollout_mrac launch");
-    return 0;
+    });
+    return launched(bad.who);
 }

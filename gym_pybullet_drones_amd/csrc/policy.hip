@@ -15,31 +15,26 @@ int gpd_rollout_policy(const GpdParams* params, const GpdState* state, const Gpd
                        float* actions_out, float* obs12, int64_t obs_step_stride, float* reward, uint8_t* terminated,
                        uint8_t* truncated, int64_t env_step_stride, const float* noise, const float* action_std, float* mean_out,
                        float* term_obs12, void* stream) {
-    auto bad = [&](int code, const char* msg) { return fail(code, (std::string("gpd_rollout_policy: ") + msg).c_str()); };
+    const Refuse bad{"gpd_rollout_policy"};
     if ((noise != nullptr) != (action_std != nullptr)) return bad(GPD_EINVAL, "noise and action_std come together");
     if (mean_out && !noise) return bad(GPD_EINVAL, "mean_out is written by the sampling kernels only (pass noise)");
     if (!params || !state || !cfg || !policy) return bad(GPD_EINVAL, "NULL params/state/cfg/policy");
-    if (!state->kin || !state->step_counter) return bad(GPD_EINVAL, "NULL state.kin/step_counter");
-    if (const char* why = state_layout_problem(state)) return bad(GPD_EINVAL, why);
+    if (int rc = check_state(bad, state)) return rc;
     if (!obs12_in || !obs12 || !reward || !terminated || !truncated) return bad(GPD_EINVAL, "NULL obs12_in/obs12/reward/terminated/truncated");
     if (!policy->w1 || !policy->b1 || !policy->w2 || !policy->b2 || !policy->w3 || !policy->b3) return bad(GPD_EINVAL, "NULL policy weights");
-    if (num_steps <= 0 || obs_step_stride < 0 || env_step_stride < 0) return bad(GPD_EINVAL, "num_steps must be positive, strides non-negative");
-    if (cfg->num_envs <= 0 || cfg->substeps <= 0) return bad(GPD_EINVAL, "num_envs and substeps must be positive");
+    if (int rc = check_steps(bad, num_steps, obs_step_stride, env_step_stride)) return rc;
+    // what the kernel serves, in front of the shared checks (a drones_per_env or act_type outside it answers GPD_ENOTSUP)
     if (cfg->drones_per_env != 1) return bad(GPD_ENOTSUP, "single-drone aviaries only (drones_per_env == 1)");
     if (cfg->act_type < GPD_ACT_RPM || cfg->act_type > GPD_ACT_ONE_D_PID) return bad(GPD_ENOTSUP, "one of the five ActionTypes (RPM, PID, VEL, ONE_D_RPM, ONE_D_PID)");
-    const bool pid = cfg->act_type == GPD_ACT_PID || cfg->act_type == GPD_ACT_VEL || cfg->act_type == GPD_ACT_ONE_D_PID;
-    if (pid && !state->pid) return bad(GPD_EINVAL, "PID action type needs state.pid");
-    if (pid && params->pid_kf <= 0.0f) return bad(GPD_ENOTSUP, "no DSLPID controller for this airframe (CF2X/CF2P only)");
-    if (cfg->task < GPD_TASK_NONE || cfg->task > GPD_TASK_MULTIHOVER) return bad(GPD_EINVAL, "unknown task");
-    if (cfg->physics_flags & ~31u) return bad(GPD_EINVAL, "unknown physics flag");
+    if (int rc = check_positive(bad, cfg)) return rc;
+    if (int rc = check_ranges(bad, cfg)) return rc;
+    if (int rc = check_flags(bad, cfg)) return rc;
     if (policy->hidden != kPolHidden) return bad(GPD_ENOTSUP, "hidden must be 64");
     if (policy->activation != 0 && policy->activation != 1) return bad(GPD_EINVAL, "activation must be 0 (tanh) or 1 (relu)");
     const int64_t N = cfg->num_envs;
-    if (state->ld < N) return bad(GPD_EINVAL, "state.ld < num_envs");
-    if (N > (1LL << 26)) return bad(GPD_ERANGE, "more than 2^26 drones per launch");
-    if ((cfg->physics_flags & GPD_PHYS_DRAG) && !state->last_rpm) return bad(GPD_EINVAL, "GPD_PHYS_DRAG needs state.last_rpm");
-    if (cfg->task != GPD_TASK_NONE && !target_pos) return bad(GPD_EINVAL, "task needs target_pos");
-    if (cfg->auto_reset && !init_pose) return bad(GPD_EINVAL, "auto_reset needs init_pose");
+    if (int rc = check_extent(bad, N, state->ld)) return rc;
+    if (int rc = check_needs(bad, params, state, cfg, target_pos, init_pose)) return rc;
+    const bool pid = cfg->act_type == GPD_ACT_PID || cfg->act_type == GPD_ACT_VEL || cfg->act_type == GPD_ACT_ONE_D_PID;
     const int A = (cfg->act_type == GPD_ACT_RPM || cfg->act_type == GPD_ACT_VEL) ? 4 : (cfg->act_type == GPD_ACT_PID ? 3 : 1);
     const int cap = 16 * pol_nk1(A, true) - 12;                       // history features the kernel's registers hold
     const bool hist = policy->in_dim != 12;
@@ -51,9 +46,9 @@ int gpd_rollout_policy(const GpdParams* params, const GpdState* state, const Gpd
         return bad(GPD_EINVAL, "state.act_ring without ring_pos / hist_len");
     }
     GpdStepCfg c = *cfg;
-    if (cfg->task == GPD_TASK_NONE) { target_pos = state->kin; c.target_per_env = 0; }
+    dummy_target(c, target_pos, state->kin);
     const Span T{num_steps, 0, obs_step_stride, env_step_stride, 2};
-    const unsigned grid = static_cast<unsigned>((N + kBlock - 1) / kBlock);
+    const unsigned grid = blocks_for(N, kBlock);
     const GpdPolicyLaunch a{params, state, &c, &T, policy, obs12_in, target_pos, init_pose, actions_out, obs12, reward, terminated,
                             truncated, stream, grid, hist ? 1 : 0, term_obs12};
     if (noise) {                 // sampling: the RPM action types (the ones examples/learn.py and the reference's learn.py train)
@@ -71,9 +66,7 @@ int gpd_rollout_policy(const GpdParams* params, const GpdState* state, const Gpd
     } else {
         launch_policy<false>(a);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_rollout_policy launch");
-    return 0;
+    return launched(bad.who);
 }
 
 }  // extern "C"

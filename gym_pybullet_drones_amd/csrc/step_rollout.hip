@@ -774,7 +774,7 @@ hipError_t launch_step(bool multi, hipStream_t st, const GpdParams& P, const Gpd
     const bool sized = sized_variants();
     if (T.num_steps == 1) {      // gpd_step, or a rollout of one step: the low-latency single-step kernel
         const int lanes = multi ? (kBlock / Dm) * Dm : (kBlock / 64) * C.lanes_per_wave;
-        const dim3 grid(static_cast<unsigned>((N + lanes - 1) / lanes));
+        const dim3 grid(blocks_for(N, lanes));
         // the completion word is for launches whose drones all sit in wave 0 of workgroup 0 (see the end of gpd_step_kernel)
         uint32_t* const done_flag = (done != nullptr && N <= (multi ? 64 : C.lanes_per_wave)) ? done->flag : nullptr;
         const uint32_t done_seq = done != nullptr ? done->seq : 0u;
@@ -796,7 +796,7 @@ hipError_t launch_step(bool multi, hipStream_t st, const GpdParams& P, const Gpd
     const bool roll1 = term_obs12 == nullptr && (!multi || Dm <= 64);
     const bool pow2 = Dm <= 64 && (Dm & (Dm - 1)) == 0;
     const int lanes = multi && roll1 ? 4 * ((64 / Dm) * Dm) : (multi ? (kBlock / Dm) * Dm : kBlock);
-    const dim3 grid(static_cast<unsigned>((N + lanes - 1) / lanes));
+    const dim3 grid(blocks_for(N, lanes));
     Span Tr = T;
     Tr.ring = ((!multi || pow2) && grid.x <= 2u * 256u) ? 4 : 2;   // <= 2 workgroups per CU: LDS is not what limits occupancy
     if (!roll1) {
@@ -880,28 +880,18 @@ int step_impl(const char* who, const GpdParams* params, const GpdState* state, c
               const float* action, const float* target_pos, const float* init_pose, float* obs12, float* reward,
               uint8_t* terminated, uint8_t* truncated, float* term_obs12, void* stream, GpdDone* done = nullptr,
               const float* plant = nullptr) {
-    auto bad = [&](int code, const char* msg) { return fail(code, (std::string(who) + ": " + msg).c_str()); };
+    const Refuse bad{who};
     if (!params || !state || !cfg) return bad(GPD_EINVAL, "NULL params/state/cfg");
-    if (!state->kin || !state->step_counter) return bad(GPD_EINVAL, "NULL state.kin/step_counter");
-    if (const char* why = state_layout_problem(state)) return bad(GPD_EINVAL, why);
+    if (int rc = check_state(bad, state)) return rc;
     if (!action || !obs12 || !reward || !terminated || !truncated)
         return bad(GPD_EINVAL, "NULL action/obs12/reward/terminated/truncated");
-    if (cfg->num_envs <= 0 || cfg->drones_per_env <= 0 || cfg->substeps <= 0)
-        return bad(GPD_EINVAL, "num_envs, drones_per_env and substeps must be positive");
+    if (int rc = check_positive(bad, cfg)) return rc;
     if (cfg->drones_per_env > kBlock) return bad(GPD_ERANGE, "drones_per_env > 256 is not supported");
-    if (cfg->act_type < GPD_ACT_RPM || cfg->act_type > GPD_ACT_DIRECT_RPM) return bad(GPD_EINVAL, "unknown act_type");
-    if (cfg->task < GPD_TASK_NONE || cfg->task > GPD_TASK_MULTIHOVER) return bad(GPD_EINVAL, "unknown task");
-    if (cfg->physics_flags & ~31u) return bad(GPD_EINVAL, "unknown physics flag");
+    if (int rc = check_ranges(bad, cfg)) return rc;
+    if (int rc = check_flags(bad, cfg)) return rc;
     const int64_t N = static_cast<int64_t>(cfg->num_envs) * cfg->drones_per_env;
-    if (state->ld < N) return bad(GPD_EINVAL, "state.ld < num_envs*drones_per_env");
-    if (N > (1LL << 26)) return bad(GPD_ERANGE, "more than 2^26 drones per launch (32-bit byte offsets)");
-    const bool pid = cfg->act_type == GPD_ACT_PID || cfg->act_type == GPD_ACT_VEL || cfg->act_type == GPD_ACT_ONE_D_PID;
-    if (pid && !state->pid) return bad(GPD_EINVAL, "PID action type needs state.pid");
-    if (pid && params->pid_kf <= 0.0f)
-        return bad(GPD_ENOTSUP, "no DSLPID controller for this airframe (CF2X/CF2P only)");
-    if ((cfg->physics_flags & GPD_PHYS_DRAG) && !state->last_rpm) return bad(GPD_EINVAL, "GPD_PHYS_DRAG needs state.last_rpm");
-    if (cfg->task != GPD_TASK_NONE && !target_pos) return bad(GPD_EINVAL, "task needs target_pos");
-    if (cfg->auto_reset && !init_pose) return bad(GPD_EINVAL, "auto_reset needs init_pose");
+    if (int rc = check_extent(bad, N, state->ld)) return rc;
+    if (int rc = check_needs(bad, params, state, cfg, target_pos, init_pose)) return rc;
     const bool multi = cfg->drones_per_env > 1;
     GpdStepCfg c = *cfg;
     if (c.lanes_per_wave == 0) c.lanes_per_wave = 64;
@@ -911,18 +901,15 @@ int step_impl(const char* who, const GpdParams* params, const GpdState* state, c
     if ((N + min_lanes - 1) / min_lanes > 0x7fffffffLL) return bad(GPD_ERANGE, "too many drones for one launch");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool ext = cfg->physics_flags != 0;
-    // task NONE never uses the target: hand the kernel a readable dummy so that its load section is branch-free
-    if (cfg->task == GPD_TASK_NONE) { target_pos = state->kin; c.target_per_env = 0; }
+    dummy_target(c, target_pos, state->kin);
     // act_type -> <PID, AW, ACT>, any physics flag -> EXT, a plant table -> PLANT with the action type from the argument block within its
     // row width (ACT = -1: compiled<>)
     auto launch = [&](auto pid, auto aw, auto act) {
-        auto with = [&](auto ext_, auto plant_) {
+        return with_ext_plant(ext, plant != nullptr, [&](auto ext_, auto plant_) {
             constexpr bool PL = decltype(plant_)::value;
             return launch_step<decltype(pid)::value, decltype(ext_)::value, decltype(aw)::value, PL ? -1 : decltype(act)::value, PL>(
                 multi, st, *params, *state, c, T, action, target_pos, init_pose, obs12, reward, terminated, truncated, term_obs12, done, plant);
-        };
-        if (plant) return ext ? with(Const<true>{}, Const<true>{}) : with(Const<false>{}, Const<true>{});
-        return ext ? with(Const<true>{}, Const<false>{}) : with(Const<false>{}, Const<false>{});
+        });
     };
     hipError_t e;
     switch (cfg->act_type) {
@@ -934,8 +921,7 @@ int step_impl(const char* who, const GpdParams* params, const GpdState* state, c
         case GPD_ACT_DIRECT_RPM: e = launch(Const<false>{}, Const<4>{}, Const<GPD_ACT_DIRECT_RPM>{}); break;
         default: e = launch(Const<false>{}, Const<4>{}, Const<GPD_ACT_RPM>{}); break;
     }
-    if (e != hipSuccess) return hip_fail(e, who);
-    return 0;
+    return e == hipSuccess ? 0 : hip_fail(e, who);
 }
 
 // What gpd_rollout, gpd_rollout_history and gpd_rollout_plant share: the checks of the span, then the entry's own (`more`: 0, or the
@@ -947,9 +933,8 @@ int rollout_impl(const char* who, bool keep_ring, More&& more, const GpdParams* 
                  int32_t num_steps, const float* actions, int64_t action_step_stride, const float* target_pos, const float* init_pose,
                  float* obs12, int64_t obs_step_stride, float* reward, uint8_t* terminated, uint8_t* truncated, int64_t env_step_stride,
                  float* term_obs12, void* stream, const float* plant = nullptr) {
-    auto bad = [&](int code, const char* msg) { return fail(code, (std::string(who) + ": " + msg).c_str()); };
-    if (num_steps <= 0) return bad(GPD_EINVAL, "num_steps must be positive");
-    if (action_step_stride < 0 || obs_step_stride < 0 || env_step_stride < 0) return bad(GPD_EINVAL, "strides must be non-negative");
+    const Refuse bad{who};
+    if (int rc = check_steps(bad, num_steps, action_step_stride, obs_step_stride, env_step_stride)) return rc;
     if (int rc = more(bad)) return rc;
     const Span T{num_steps, action_step_stride, obs_step_stride, env_step_stride, 2};
     GpdState s;
@@ -993,7 +978,7 @@ int gpd_rollout(const GpdParams* params, const GpdState* state, const GpdStepCfg
                 const float* actions, int64_t action_step_stride, const float* target_pos, const float* init_pose,
                 float* obs12, int64_t obs_step_stride, float* reward, uint8_t* terminated, uint8_t* truncated,
                 int64_t env_step_stride, float* term_obs12, void* stream) {
-    return rollout_impl("gpd_rollout", false, [](auto&) { return 0; }, params, state, cfg, num_steps, actions, action_step_stride,
+    return rollout_impl("gpd_rollout", false, [](const Refuse&) { return 0; }, params, state, cfg, num_steps, actions, action_step_stride,
                         target_pos, init_pose, obs12, obs_step_stride, reward, terminated, truncated, env_step_stride, term_obs12, stream);
 }
 
@@ -1001,7 +986,7 @@ int gpd_rollout_history(const GpdParams* params, const GpdState* state, const Gp
                         const float* actions, int64_t action_step_stride, const float* target_pos, const float* init_pose,
                         float* obs12, int64_t obs_step_stride, float* reward, uint8_t* terminated, uint8_t* truncated,
                         int64_t env_step_stride, void* stream) {
-    auto more = [&](auto& bad) {
+    auto more = [&](const Refuse& bad) {
         if (!state || !state->act_ring || !state->ring_pos || state->hist_len <= 0)
             return bad(GPD_EINVAL, "state has no action ring (act_ring / ring_pos / hist_len)");
         if (cfg && cfg->drones_per_env > 64)
@@ -1014,25 +999,24 @@ int gpd_rollout_history(const GpdParams* params, const GpdState* state, const Gp
 
 int gpd_plant_derive(const GpdParams* nominal, const float* scales, const uint8_t* env_mask, int32_t num_envs, int32_t drones_per_env,
                      int64_t ld, float* rows, void* stream) {
-    if (!nominal || !scales || !rows) return fail(GPD_EINVAL, "gpd_plant_derive: NULL nominal/scales/rows");
-    if (num_envs <= 0 || drones_per_env <= 0) return fail(GPD_EINVAL, "gpd_plant_derive: num_envs and drones_per_env must be positive");
+    const Refuse bad{"gpd_plant_derive"};
+    if (!nominal || !scales || !rows) return bad(GPD_EINVAL, "NULL nominal/scales/rows");
+    if (num_envs <= 0 || drones_per_env <= 0) return bad(GPD_EINVAL, "num_envs and drones_per_env must be positive");
     const int64_t n = static_cast<int64_t>(num_envs) * drones_per_env;
-    if (ld < n) return fail(GPD_EINVAL, "gpd_plant_derive: ld < num_envs*drones_per_env");
-    if (n > (1LL << 26)) return fail(GPD_ERANGE, "gpd_plant_derive: more than 2^26 drones");
-    if (reinterpret_cast<uintptr_t>(rows) & 15u) return fail(GPD_EINVAL, "gpd_plant_derive: rows must be 16-byte aligned");
-    hipLaunchKernelGGL(gpd_plant_derive_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    if (int rc = check_extent(bad, n, ld, "ld")) return rc;
+    if (misaligned16(rows)) return bad(GPD_EINVAL, "rows must be 16-byte aligned");
+    hipLaunchKernelGGL(gpd_plant_derive_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        *nominal, scales, env_mask, static_cast<uint32_t>(n), static_cast<uint32_t>(drones_per_env), ld, rows);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "gpd_plant_derive");
-    return 0;
+    return launched(bad.who, "");
 }
 
 int gpd_rollout_plant(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, int32_t num_steps,
                       const float* actions, int64_t action_step_stride, const float* target_pos, const float* init_pose,
                       float* obs12, int64_t obs_step_stride, float* reward, uint8_t* terminated, uint8_t* truncated,
                       int64_t env_step_stride, float* term_obs12, const float* plant_rows, void* stream) {
-    auto more = [&](auto& bad) {
+    auto more = [&](const Refuse& bad) {
         if (!plant_rows) return bad(GPD_EINVAL, "NULL plant_rows");
-        if (reinterpret_cast<uintptr_t>(plant_rows) & 15u) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
+        if (misaligned16(plant_rows)) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
         if (state && state->dw_force)
             return bad(GPD_ENOTSUP, "state.dw_force (downwash computed outside the kernel) is not served by the plant path");
         return 0;

@@ -1097,7 +1097,7 @@ DwGrid grid_of(const GpdSwarm& w) {
 void dwg_sort(hipStream_t st, const DwPos& src, int n, const DwGrid& G, const int* visit, int* count, int* start, int* order,
               float4* sorted, float* dw_out, const DwBinOut& B, const GpdState* vec_state = nullptr, const float* vec_obs12 = nullptr,
               float* vec_out = nullptr) {
-    const dim3 grid(static_cast<unsigned>((n + kBlock - 1) / kBlock));
+    const dim3 grid(blocks_for(n, kBlock));
     const int keys = G.nx * G.ny * G.nz;
     int* const cursors = count + keys + 1;
     if (vec_out) hipLaunchKernelGGL(dwg_count_kernel<true>, grid, dim3(kBlock), 0, st, src, n, G, visit, count, *vec_state, vec_obs12, vec_out);
@@ -1123,35 +1123,33 @@ int gpd_downwash_global(const GpdParams* params, const float* kin, int64_t ld, i
                         float y0, int32_t nx, int32_t ny, float z0, float zbin, int32_t nz, const int32_t* visit_order,
                         int32_t* cell_count, int32_t* cell_start, int32_t* order, float* sorted_xyzc, float* dw_out,
                         const GpdState* vec_state, const float* vec_obs12, float* vec_out, void* stream) {
+    const Refuse bad{"gpd_downwash_global"};
     if (!params || !kin || !cell_count || !cell_start || !order || !sorted_xyzc || !dw_out)
-        return fail(GPD_EINVAL, "gpd_downwash_global: NULL argument");
-    if (n <= 0 || ld < n) return fail(GPD_EINVAL, "gpd_downwash_global: need 0 < n <= ld");
-    if ((reinterpret_cast<uintptr_t>(kin) & 15u) != 0) return fail(GPD_EINVAL, "gpd_downwash_global: kin must be 16-byte aligned (plane P is read as float4)");
-    if (visit_order == order) return fail(GPD_EINVAL, "gpd_downwash_global: visit_order must not alias order (ping-pong two buffers)");
-    if (!(cell >= 10.0f)) return fail(GPD_EINVAL, "gpd_downwash_global: cell must be >= 10 m (the model's lateral cut-off)");
-    if (nz < 1 || nz > kBlock || (nz > 1 && !(zbin > 0.0f))) return fail(GPD_EINVAL, "gpd_downwash_global: need 1 <= nz <= 256 and zbin > 0");
+        return bad(GPD_EINVAL, "NULL argument");
+    if (n <= 0 || ld < n) return bad(GPD_EINVAL, "need 0 < n <= ld");
+    if (misaligned16(kin)) return bad(GPD_EINVAL, "kin must be 16-byte aligned (plane P is read as float4)");
+    if (visit_order == order) return bad(GPD_EINVAL, "visit_order must not alias order (ping-pong two buffers)");
+    if (!(cell >= 10.0f)) return bad(GPD_EINVAL, "cell must be >= 10 m (the model's lateral cut-off)");
+    if (nz < 1 || nz > kBlock || (nz > 1 && !(zbin > 0.0f))) return bad(GPD_EINVAL, "need 1 <= nz <= 256 and zbin > 0");
     if (nx < 3 || ny < 3 || static_cast<int64_t>(nx) * ny * nz > 65536)
-        return fail(GPD_ERANGE, "gpd_downwash_global: need nx, ny >= 3 (periodic 3x3 search) and nx*ny*nz <= 65536");
+        return bad(GPD_ERANGE, "need nx, ny >= 3 (periodic 3x3 search) and nx*ny*nz <= 65536");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const DwGrid G{1.0f / cell, x0, y0, nx, ny, z0, nz > 1 ? 1.0f / zbin : 0.0f, nz};
     if (vec_out) {
-        if (!vec_state || !vec_state->kin || !vec_obs12) return fail(GPD_EINVAL, "gpd_downwash_global: vec_out needs vec_state and vec_obs12");
-        if (vec_state->ld < n) return fail(GPD_EINVAL, "gpd_downwash_global: vec_state.ld < n");
+        if (!vec_state || !vec_state->kin || !vec_obs12) return bad(GPD_EINVAL, "vec_out needs vec_state and vec_obs12");
+        if (vec_state->ld < n) return bad(GPD_EINVAL, "vec_state.ld < n");
     }
     const DwBinOut B{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, n, 0.0f, 0};
     dwg_sort(st, DwPos{kin, ld, nullptr}, n, G, visit_order, cell_count, cell_start, order, reinterpret_cast<float4*>(sorted_xyzc), dw_out, B,
              vec_state, vec_obs12, vec_out);
     const DwWorld Wd{nullptr, nullptr, nullptr, 0, n, 0, 0, 0, cell, nullptr, 0.0f, n};
-    hipLaunchKernelGGL(dwg_force_kernel<0>, dim3(static_cast<unsigned>((n + 63) / 64)), dim3(kBlock), 0, st, static_cast<uint32_t*>(nullptr),
+    hipLaunchKernelGGL(dwg_force_kernel<0>, dim3(blocks_for(n, 64)), dim3(kBlock), 0, st, static_cast<uint32_t*>(nullptr),
                        static_cast<unsigned short*>(nullptr), static_cast<int*>(nullptr), Wd.pos4, order,
                        reinterpret_cast<const float4*>(sorted_xyzc), 0, Wd.n_slots, *params, G, Wd, DwLists{}, cell_start, dw_out, cell_count);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_downwash_global launch");
-    return 0;
+    return launched(bad.who);
 }
 
-static int swarm_args(const char* who, const GpdSwarm* w, bool sorted_buffers) {
-    auto bad = [&](int code, const char* msg) { return fail(code, (std::string(who) + ": " + msg).c_str()); };
+static int swarm_args(Refuse bad, const GpdSwarm* w, bool sorted_buffers) {
     if (!w) return bad(GPD_EINVAL, "NULL swarm");
     if (w->world_size < 1 || w->world_size > kBlock || w->rank < 0 || w->rank >= w->world_size) return bad(GPD_EINVAL, "need 0 <= rank < world_size <= 256");
     if (w->meta_rows < 1 || w->own_count < 0 || w->own_count > w->slab - w->meta_rows)
@@ -1176,23 +1174,22 @@ static int swarm_args(const char* who, const GpdSwarm* w, bool sorted_buffers) {
 
 int gpd_swarm_step(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, const GpdSwarm* swarm,
                    const float* action, float* obs12, float* vec_out, void* stream) {
-    auto bad = [&](int code, const char* msg) { return fail(code, (std::string("gpd_swarm_step: ") + msg).c_str()); };
+    const Refuse bad{"gpd_swarm_step"};
     if (!params || !state || !cfg || !action || !obs12) return bad(GPD_EINVAL, "NULL params/state/cfg/action/obs12");
-    if (int rc = swarm_args("gpd_swarm_step", swarm, false)) return rc;
-    if (!state->kin || !state->step_counter) return bad(GPD_EINVAL, "NULL state.kin/step_counter");
-    if (const char* why = state_layout_problem(state)) return bad(GPD_EINVAL, why);
+    if (int rc = swarm_args(bad, swarm, false)) return rc;
+    if (int rc = check_state(bad, state)) return rc;
     if (cfg->drones_per_env != 1 || cfg->num_envs != swarm->own_count || cfg->num_envs <= 0) return bad(GPD_EINVAL, "need drones_per_env == 1 and num_envs == swarm.own_count > 0");
     if (cfg->substeps != 1 || cfg->task != GPD_TASK_NONE || cfg->auto_reset) return bad(GPD_ENOTSUP, "one physics sub-step per call, no task, no auto-reset");
     if (cfg->act_type != GPD_ACT_RPM && cfg->act_type != GPD_ACT_RAW_RPM && cfg->act_type != GPD_ACT_DIRECT_RPM)
         return bad(GPD_ENOTSUP, "act_type RPM, RAW_RPM or DIRECT_RPM (waypoints: gpd_pid first)");
-    if (cfg->physics_flags & ~31u) return bad(GPD_EINVAL, "unknown physics flag");
-    if (state->ld < cfg->num_envs) return bad(GPD_EINVAL, "state.ld < num_envs");
-    if ((cfg->physics_flags & GPD_PHYS_DRAG) && !state->last_rpm) return bad(GPD_EINVAL, "GPD_PHYS_DRAG needs state.last_rpm");
+    if (int rc = check_flags(bad, cfg)) return rc;
+    if (int rc = check_extent(bad, cfg->num_envs, state->ld)) return rc;          // (swarm_args: no more than 2^26 rows)
+    if (int rc = check_needs(bad, params, state, cfg, nullptr, nullptr)) return rc;
     const size_t lo = static_cast<size_t>(swarm->rank) * swarm->slab;
     const SwarmOut O{reinterpret_cast<float4*>(swarm->pos4) + lo, reinterpret_cast<const float4*>(swarm->bin_pos) + lo,
                      swarm->pos4 + (lo + swarm->slab - swarm->meta_rows) * 4, swarm->slot_of ? swarm->slot_of + lo : nullptr,
                      reinterpret_cast<float4*>(swarm->pos_sorted), swarm->drift, vec_out};
-    const dim3 grid(static_cast<unsigned>((cfg->num_envs + kBlock - 1) / kBlock));
+    const dim3 grid(blocks_for(cfg->num_envs, kBlock));
     hipStream_t st = static_cast<hipStream_t>(stream);
     auto launch = [&](auto act) {
         hipLaunchKernelGGL(gpd_swarm_step_kernel<decltype(act)::value>, grid, dim3(kBlock), 0, st, state->kin, action, state->last_rpm,
@@ -1207,54 +1204,51 @@ int gpd_swarm_step(const GpdParams* params, const GpdState* state, const GpdStep
     // (too many meta rows for every force workgroup to read: leave the rank's maximum in its first meta row)
     if (static_cast<int64_t>(swarm->world_size) * swarm->meta_rows > 1024)
         hipLaunchKernelGGL(dwg_reduce_meta_kernel, dim3(1), dim3(kBlock), 0, st, O.meta_own, static_cast<int>(grid.x));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_swarm_step launch");
-    return 0;
+    return launched(bad.who);
 }
 
 int gpd_swarm_pack(const GpdState* state, const GpdSwarm* swarm, const float* obs12, float* vec_out, void* stream) {
-    if (!state || !state->kin) return fail(GPD_EINVAL, "gpd_swarm_pack: NULL state / state.kin");
-    if (const char* why = state_layout_problem(state)) return fail(GPD_EINVAL, (std::string("gpd_swarm_pack: ") + why).c_str());
-    if (int rc = swarm_args("gpd_swarm_pack", swarm, false)) return rc;
-    if (state->ld < swarm->own_count) return fail(GPD_EINVAL, "gpd_swarm_pack: state.ld < own_count");
-    if (vec_out && !obs12) return fail(GPD_EINVAL, "gpd_swarm_pack: vec_out needs obs12");
+    const Refuse bad{"gpd_swarm_pack"};
+    if (!state || !state->kin) return bad(GPD_EINVAL, "NULL state / state.kin");
+    if (const char* why = state_layout_problem(state)) return bad(GPD_EINVAL, why);
+    if (int rc = swarm_args(bad, swarm, false)) return rc;
+    if (state->ld < swarm->own_count) return bad(GPD_EINVAL, "state.ld < own_count");
+    if (vec_out && !obs12) return bad(GPD_EINVAL, "vec_out needs obs12");
     const size_t lo = static_cast<size_t>(swarm->rank) * swarm->slab;
-    hipLaunchKernelGGL(gpd_swarm_pack_kernel, dim3(static_cast<unsigned>((swarm->slab + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(gpd_swarm_pack_kernel, dim3(blocks_for(swarm->slab, kBlock)), dim3(kBlock), 0,
                        static_cast<hipStream_t>(stream), *state, swarm->own_count, swarm->slab, reinterpret_cast<float4*>(swarm->pos4) + lo,
                        obs12, vec_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_swarm_pack launch");
-    return 0;
+    return launched(bad.who);
 }
 
 int gpd_swarm_bin(const GpdSwarm* w, void* stream) {
-    if (int rc = swarm_args("gpd_swarm_bin", w, true)) return rc;
-    if (!w->dw_force) return fail(GPD_EINVAL, "gpd_swarm_bin: NULL dw_force (a drone without a finite position gets force 0 here)");
+    const Refuse bad{"gpd_swarm_bin"};
+    if (int rc = swarm_args(bad, w, true)) return rc;
+    if (!w->dw_force) return bad(GPD_EINVAL, "NULL dw_force (a drone without a finite position gets force 0 here)");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const DwBinOut B{w->slot_key, w->slot_of, w->visit_out, w->list_ok, reinterpret_cast<float4*>(w->bin_pos), w->pos4, w->drift, w->slab, w->world_size, w->meta_rows, w->rank * w->slab, w->own_count,
                      w->pair_list ? w->list_delta : 0.0f, w->list_adapt != 0};
     dwg_sort(st, DwPos{nullptr, 0, reinterpret_cast<const float4*>(w->pos4)}, w->n_rows, grid_of(*w), w->visit, w->cell_count, w->cell_start,
              w->order, reinterpret_cast<float4*>(w->pos_sorted), w->dw_force, B);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_swarm_bin launch");
-    return 0;
+    return launched(bad.who);
 }
 
 int gpd_swarm_forces(const GpdParams* params, const GpdSwarm* w, int32_t build_lists, void* stream) {
-    if (!params) return fail(GPD_EINVAL, "gpd_swarm_forces: NULL params");
-    if (int rc = swarm_args("gpd_swarm_forces", w, true)) return rc;
-    if (!w->dw_force) return fail(GPD_EINVAL, "gpd_swarm_forces: NULL dw_force");
+    const Refuse bad{"gpd_swarm_forces"};
+    if (!params) return bad(GPD_EINVAL, "NULL params");
+    if (int rc = swarm_args(bad, w, true)) return rc;
+    if (!w->dw_force) return bad(GPD_EINVAL, "NULL dw_force");
     const bool lists = w->pair_list != nullptr;
     if (lists && (!w->pair_nb || !w->list_ok || w->list_cap < 4 || w->list_cap > 65535 || !(w->list_delta >= 0.0f)))
-        return fail(GPD_EINVAL, "gpd_swarm_forces: pair_list needs pair_nb, list_ok, 4 <= list_cap <= 65535 and list_delta >= 0");
+        return bad(GPD_EINVAL, "pair_list needs pair_nb, list_ok, 4 <= list_cap <= 65535 and list_delta >= 0");
     // (an entry is lane << 26 | index and 0xffffffff marks an empty lane: index 2^26 - 1 of lane 63 must not exist)
-    if (lists && w->n_rows >= (1 << 26)) return fail(GPD_ERANGE, "gpd_swarm_forces: wake lists address fewer than 2^26 rows");
+    if (lists && w->n_rows >= (1 << 26)) return bad(GPD_ERANGE, "wake lists address fewer than 2^26 rows");
     const DwGrid G = grid_of(*w);
     const float4* const p4 = reinterpret_cast<const float4*>(w->pos4);
     const DwWorld Wd{w->pos_sorted ? nullptr : p4, w->slot_key, p4, w->rank * w->slab, w->own_count, w->slab, w->world_size, w->meta_rows, w->cell,
                      w->drift, 1.0f / static_cast<float>(w->total_drones), w->n_rows};
     const DwLists Ls{w->pair_list, w->pair_nb, w->list_ok, w->list_cap, w->list_delta};
-    const dim3 grid(static_cast<unsigned>((w->n_rows + 63) / 64) + 1u);        // (+ the workgroup that computes the drift)
+    const dim3 grid(blocks_for(w->n_rows, 64) + 1u);        // (+ the workgroup that computes the drift)
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float4* const srt = reinterpret_cast<const float4*>(w->pos_sorted);
     auto launch = [&](auto mode) {      // 0: no wake lists, 1: the sweep that builds them, 2: their replay
@@ -1264,24 +1258,22 @@ int gpd_swarm_forces(const GpdParams* params, const GpdSwarm* w, int32_t build_l
     if (!lists) launch(Const<0>{});
     else if (build_lists) launch(Const<1>{});
     else launch(Const<2>{});
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_swarm_forces launch");
-    return 0;
+    return launched(bad.who);
 }
 
 int gpd_neighbors(const float* pos4, int32_t n_rows, int32_t query_first, int32_t query_count, float radius, int32_t k,
                   int32_t drones_per_env, float cell, float x0, float y0, float x1, float y1, const int32_t* visit_order,
                   int32_t* cell_count, int32_t* cell_start, int32_t* order, float* sorted_xyzc, int32_t* nbr_count,
                   int32_t* nbr_idx, float* nbr_rel, uint8_t* adjacency, void* stream) {
-    auto bad = [&](int code, const char* msg) { return fail(code, (std::string("gpd_neighbors: ") + msg).c_str()); };
+    const Refuse bad{"gpd_neighbors"};
     if (!pos4 || !nbr_count) return bad(GPD_EINVAL, "NULL pos4 / nbr_count");
     if (n_rows <= 0) return bad(GPD_EINVAL, "need n_rows > 0");
     if (k < 1 || k > 32) return bad(GPD_ERANGE, "need 1 <= k <= 32");
     if (!(radius > 0.0f) || !std::isfinite(radius)) return bad(GPD_EINVAL, "radius must be positive and finite");
     if (query_first < 0 || query_count <= 0 || static_cast<int64_t>(query_first) + query_count > n_rows)
         return bad(GPD_ERANGE, "the query range must lie inside the rows (0 <= query_first, 0 < query_count, query_first + query_count <= n_rows)");
-    if ((reinterpret_cast<uintptr_t>(pos4) & 15u) != 0) return bad(GPD_EINVAL, "pos4 must be 16-byte aligned (rows are read as float4)");
-    if (nbr_rel && (reinterpret_cast<uintptr_t>(nbr_rel) & 15u) != 0) return bad(GPD_EINVAL, "nbr_rel must be 16-byte aligned (entries are written as float4)");
+    if (misaligned16(pos4)) return bad(GPD_EINVAL, "pos4 must be 16-byte aligned (rows are read as float4)");
+    if (misaligned16(nbr_rel)) return bad(GPD_EINVAL, "nbr_rel must be 16-byte aligned (entries are written as float4)");
     const int D = drones_per_env;
     if (D != 0 && (D < 2 || D > kBlock)) return bad(GPD_EINVAL, "drones_per_env must be 0 (one world) or 2 .. 256");
     if (adjacency && D == 0) return bad(GPD_EINVAL, "adjacency needs drones_per_env >= 2 (one world has no dense matrix)");
@@ -1300,12 +1292,12 @@ int gpd_neighbors(const float* pos4, int32_t n_rows, int32_t query_first, int32_
         if (n_rows % D != 0 || query_first % D != 0 || query_count % D != 0)
             return bad(GPD_EINVAL, "with drones_per_env = D the rows and the query range are whole aviaries (multiples of D)");
         const int G = kBlock / D, E = query_count / D;
-        const dim3 grid(static_cast<unsigned>((E + G - 1) / G));
+        const dim3 grid(blocks_for(E, G));
         with_k([&](auto kk) { hipLaunchKernelGGL(nbr_env_kernel<decltype(kk)::value>, grid, dim3(kBlock), 0, st, p4, D, G, E, r2, O); });
     } else {
         if (!cell_count || !cell_start || !order || !sorted_xyzc) return bad(GPD_EINVAL, "one world needs the sort's scratch: cell_count, cell_start, order, sorted_xyzc");
         if (visit_order == order) return bad(GPD_EINVAL, "visit_order must not alias order (ping-pong two buffers)");
-        if ((reinterpret_cast<uintptr_t>(sorted_xyzc) & 15u) != 0) return bad(GPD_EINVAL, "sorted_xyzc must be 16-byte aligned");
+        if (misaligned16(sorted_xyzc)) return bad(GPD_EINVAL, "sorted_xyzc must be 16-byte aligned");
         if (!std::isfinite(x0) || !std::isfinite(y0) || !std::isfinite(x1) || !std::isfinite(y1) || x1 < x0 || y1 < y0)
             return bad(GPD_EINVAL, "the box x0 <= x1, y0 <= y1 the grid is laid over must be finite");
         if (!(cell >= 0.0f) || !std::isfinite(cell)) return bad(GPD_EINVAL, "cell must be 0 (the smallest that is exact) or a finite size in metres");
@@ -1320,15 +1312,13 @@ int gpd_neighbors(const float* pos4, int32_t n_rows, int32_t query_first, int32_
         const DwBinOut B{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0.0f, 0};     // (own_cnt = 0: no force array)
         float4* const srt = reinterpret_cast<float4*>(sorted_xyzc);
         dwg_sort(st, DwPos{nullptr, 0, p4}, n_rows, G, visit_order, cell_count, cell_start, order, srt, nullptr, B);
-        const dim3 sgrid(static_cast<unsigned>((n_rows + 63) / 64));
+        const dim3 sgrid(blocks_for(n_rows, 64));
         with_k([&](auto kk) {
             hipLaunchKernelGGL(nbr_world_kernel<decltype(kk)::value>, sgrid, dim3(64), 0, st, p4, order, srt, cell_start, n_rows, nx, ny, r2, O,
                                cell_count);
         });
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gpd_neighbors launch");
-    return 0;
+    return launched(bad.who);
 }
 
 }  // extern "C"

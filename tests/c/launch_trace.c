@@ -148,6 +148,82 @@ static void mrac(void) {
         }
 }
 
+/* the differentiable rollout: both act widths, with and without drag (EXT) and a plant table */
+static void differentiable(void) {
+    static const int acts[] = {GPD_ACT_RPM, GPD_ACT_ONE_D_RPM, GPD_ACT_RAW_RPM, GPD_ACT_DIRECT_RPM};
+    C.num_envs = 4096; C.drones_per_env = 1; C.substeps = 1; C.auto_reset = 0; S.ld = 4096;
+    for (int vjp = 0; vjp < 2; ++vjp)
+        for (int ai = 0; ai < 4; ++ai)
+            for (int drag = 0; drag < 2; ++drag)
+                for (int plant = 0; plant < 2; ++plant)
+                    for (int task = GPD_TASK_NONE; task <= GPD_TASK_HOVER; ++task) {
+                        const int A = acts[ai] == GPD_ACT_ONE_D_RPM ? 1 : 4;
+                        C.act_type = acts[ai]; C.physics_flags = drag ? GPD_PHYS_DRAG : 0; C.task = task;
+                        entry = vjp ? "gpd_rollout_vjp" : "gpd_rollout_tape";
+                        snprintf(what, sizeof what, "act=%d,flags=%u,plant=%d,task=%d", C.act_type, C.physics_flags, plant, task);
+                        const float* const rows = plant ? DEV(61) : NULL;
+                        if (vjp) done(gpd_rollout_vjp(&P, &C, S.ld, 8, DEV(3), 4096 * A, DEV(4), rows, DEV(64), DEV(65), 4096 * 12, DEV(66), 4096, DEV(67), DEV(68), NULL));
+                        else done(gpd_rollout_tape(&P, &S, &C, 8, DEV(3), 4096 * A, DEV(4), DEV(6), 4096 * 12, DEV(7), DEV(8), DEV(9), 4096, rows, DEV(64), NULL));
+                    }
+    C.task = GPD_TASK_HOVER; C.auto_reset = 1; C.physics_flags = 0;
+}
+
+/* the entries with one launch path each, on both sides of what their grids depend on */
+static void small_entries(void) {
+    static GpdMrac M;
+    static const int ns[] = {1, 64, 257, 4096};
+    C.act_type = GPD_ACT_RPM; C.physics_flags = 0; C.drones_per_env = 1; C.substeps = 1;
+    for (int ni = 0; ni < 4; ++ni) {
+        const int n = ns[ni];
+        S.ld = (n + 63) / 64 * 64; C.num_envs = n;
+        snprintf(what, sizeof what, "n=%d", n);
+        entry = "gpd_reset"; done(gpd_reset(&S, DEV(5), 0, NULL, n, 1, 1, DEV(6), NULL));
+        entry = "gpd_state_vectors"; done(gpd_state_vectors(&S, DEV(6), DEV(23), n, NULL));
+        entry = "gpd_pid"; done(gpd_pid(&P, DEV(11), S.ld, 1.0f / 240, DEV(24), DEV(25), DEV(26), DEV(27), NULL, NULL, NULL, DEV(28), NULL, NULL, n, NULL));
+        entry = "gpd_pid_sync"; done(gpd_pid_sync(&P, DEV(11), S.ld, 1.0f / 240, DEV(24), DEV(25), DEV(26), DEV(27), NULL, NULL, NULL, DEV(28), NULL, NULL, n, NULL));
+        entry = "gpd_step_sync"; done(gpd_step_sync(&P, &S, &C, DEV(3), DEV(4), DEV(5), DEV(6), DEV(7), DEV(8), DEV(9), NULL, NULL));
+        entry = "gpd_mrac"; done(gpd_mrac(&M, DEV(57), DEV(58), S.ld, 1.0f / 240, DEV(24), DEV(25), DEV(26), DEV(62), DEV(27), NULL, NULL, NULL, DEV(28), NULL, NULL, n, NULL));
+        entry = "gpd_plant_derive"; done(gpd_plant_derive(&P, DEV(63), NULL, n, 1, S.ld, DEV(61), NULL));
+        entry = "gpd_mrac_reset";
+        for (int restore = 0; restore < 2; ++restore) {
+            snprintf(what, sizeof what, "n=%d,restore_gains=%d", n, restore);
+            done(gpd_mrac_reset(DEV(57), DEV(58), S.ld, &M, NULL, n, restore, NULL));
+        }
+    }
+    entry = "gpd_plant_derive"; snprintf(what, sizeof what, "E=100,D=3"); done(gpd_plant_derive(&P, DEV(63), DEV(69), 100, 3, 320, DEV(61), NULL));
+    entry = "gpd_reset"; done(gpd_reset(&S, DEV(5), 1, DEV(69), 100, 3, 0, NULL, NULL));
+    /* the history rows: rows per workgroup follow the row length (12 + hist_len * act_dim floats against 48 KiB of LDS) */
+    static const int hs[] = {15, 120, 1000};
+    S.act_ring = DEV(13); S.ring_pos = DEV(14);
+    for (int hi = 0; hi < 3; ++hi)
+        for (int A = 1; A <= 4; A += 3)
+            for (int D = 1; D <= 2; ++D) {
+                S.hist_len = hs[hi];
+                snprintf(what, sizeof what, "hist_len=%d,act_dim=%d,D=%d", hs[hi], A, D);
+                const int64_t W = 12 + hs[hi] * A;
+                entry = "gpd_hist_rows"; done(gpd_hist_rows(&S, 4096, D, A, DEV(6), DEV(15), NULL));
+                entry = "gpd_full_obs";
+                for (int K = 8; K <= 2000; K += 1992)
+                    for (int full = 0; full < 2; ++full) {
+                        snprintf(what, sizeof what, "hist_len=%d,act_dim=%d,D=%d,K=%d,obs_full=%d", hs[hi], A, D, K, full);
+                        done(gpd_full_obs(&S, K, 4096, D, A, DEV(6), 4096 * 12, DEV(3), 4096 * A, full ? DEV(15) : NULL, 4096 * W, NULL));
+                    }
+            }
+    S.act_ring = NULL; S.ring_pos = NULL; S.hist_len = 0;
+    /* gpd_swarm_pack: one lane per row of the rank's slab */
+    GpdSwarm W;
+    memset(&W, 0, sizeof W);
+    W.world_size = 2; W.nx = W.ny = 32; W.nz = 1; W.cell = 10.5f; W.zbin = 1.0f; W.pos4 = DEV(40); W.bin_pos = DEV(41); W.drift = DEV(53);
+    entry = "gpd_swarm_pack";
+    for (int rank = 0; rank < 2; ++rank)
+        for (int own = 1000; own <= 65536; own += 64536) {
+            W.rank = rank; W.own_count = own; W.meta_rows = (own + 255) / 256; W.slab = own + W.meta_rows; W.n_rows = 2 * W.slab; W.total_drones = 2 * own;
+            S.ld = 65536;
+            snprintf(what, sizeof what, "rank=%d,own_count=%d", rank, own);
+            done(gpd_swarm_pack(&S, &W, DEV(6), rank ? DEV(23) : NULL, NULL));
+        }
+}
+
 int main(void) {
     hipstub_on_launch(on_launch);
     P.pid_kf = 3.16e-10f;
@@ -157,5 +233,8 @@ int main(void) {
     policies();
     one_world();
     mrac();
+    C.task = GPD_TASK_HOVER; C.auto_reset = 1;
+    differentiable();
+    small_entries();
     return 0;
 }

@@ -3,7 +3,8 @@ launch arithmetic, the choice of the kernel -- compiled from the five product un
 mrac.hip) with AddressSanitizer + UndefinedBehaviorSanitizer (`hipcc --cuda-host-only`: no device code, seconds), linked against a HIP
 runtime that launches nothing and names what it was asked to launch (tests/stubs/hip_stub.c), and driven through every entry of
 include/gpd.h by a plain C program (tests/c/asan_host.c); tests/c/launch_trace.c then lists which kernel serves which call over the
-shapes at which a launch path decides something.  No GPU needed."""
+shapes at which a launch path decides something, and tests/c/arg_errors.c what every entry refuses, one broken argument at a time, against
+the recorded table tests/c/arg_errors.expected.  No GPU needed."""
 import os
 import re
 import subprocess
@@ -40,7 +41,7 @@ def test_host_side_of_the_c_abi_under_asan_and_ubsan(tmp_path):
     res = subprocess.run(link, capture_output=True, text=True)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     exes = {}
-    for name in ("asan_host", "launch_trace"):
+    for name in ("asan_host", "launch_trace", "arg_errors"):
         exes[name] = str(tmp_path / name)
         res = subprocess.run([clang] + san + ["-std=c11", "-I", _native.INCLUDE, os.path.join(REPO, "tests", "c", name + ".c"), lib, f"-Wl,-rpath,{tmp_path}", "-o", exes[name]],
                              capture_output=True, text=True)
@@ -70,3 +71,14 @@ def test_host_side_of_the_c_abi_under_asan_and_ubsan(tmp_path):
     changed = [(a, b) for a, b in zip(sized, generic) if a != b]
     assert changed                                                                     # (the hook does something)
     assert not [(a, b) for a, b in changed if not (any(k in a for k in rollout_kernels) and any(k in b for k in rollout_kernels))][:5]
+
+    # what every entry refuses: the recorded codes, and a message that names the entry, row by row
+    run = subprocess.run([exes["arg_errors"]], capture_output=True, text=True, env=env, timeout=120)
+    assert "AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-4000:]
+    assert run.returncode == 0, run.stderr[-2000:]
+    row = re.compile(r"(\w+) (.+) -> rc (-?\d+) \| (.*)")
+    rows = [row.fullmatch(l).groups() for l in run.stdout.splitlines()]
+    recorded = [row.fullmatch(l).groups() for l in open(os.path.join(REPO, "tests", "c", "arg_errors.expected")).read().splitlines()]
+    assert len(recorded) > 700
+    assert [r[:3] for r in rows] == [r[:3] for r in recorded], [(a, b) for a, b in zip(rows, recorded) if a[:3] != b[:3]][:5]
+    assert not [r for r in rows if int(r[2]) == 0 or not r[3].startswith(r[0] + ": ") or len(r[3]) <= len(r[0]) + 2][:5]
