@@ -39,7 +39,7 @@ MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 HIPCC_FLAGS = COMMON_FLAGS + MAX_ILP + ["-shared"]        # (kept under this name for the ISA tests)
 UNITS = (("step_rollout.hip", MAX_ILP + KERNARG_PRELOAD), ("policy.hip", []), ("swarm.hip", MAX_ILP + KERNARG_PRELOAD), ("abi.hip", MAX_ILP), ("mrac.hip", MAX_ILP))
-HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc")
+HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc")
 
 
 class GpdError(RuntimeError):
@@ -203,6 +203,10 @@ _SIGNATURES = {
                                         ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, _P]),
     "gpd_rollout_vjp": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdStepCfg), ctypes.c_int64, ctypes.c_int32, _P,
                                        ctypes.c_int64, _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P]),
+    # ... and the gradients with respect to the plant: the sweep that also returns the plant rows' cotangents, rows -> scale factors
+    "gpd_rollout_vjp_plant": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdStepCfg), ctypes.c_int64, ctypes.c_int32, _P,
+                                             ctypes.c_int64, _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P]),
+    "gpd_plant_derive_vjp": (ctypes.c_int, [ctypes.POINTER(GpdParams), _P, _P, ctypes.c_int32, ctypes.c_int64, _P, _P]),
 }
 COMM_ID_BYTES = 128
 GPD_EINVAL, GPD_ERANGE, GPD_ENOTSUP = -1, -2, -3

@@ -7,9 +7,15 @@
 //                             action row and the cotangent rows, re-runs the forward sub-steps from the taped state for each sub-step in
 //                             reverse (S(S+1)/2 recomputations, no scratch memory, no per-sub-step tape), pushes the adjoint through them
 //                             and writes the action gradient of the step.  No atomics: every output word has one writer.
+//                             <.., PLANT, GP> (gpd_rollout_vjp_plant, DESIGN.md section 3.13): the same lane also sums the cotangents of
+//                             the plant rows it reads, 16 registers, and stores them once after the loop;
+//   gpd_plant_derive_vjp_kernel  those cotangents -> the nine scale factors: the transpose of gpd_plant_derive's Jacobian
+//                             (plant_derive_vjp.inc, which the host tests compile too).
 // The adjoint is that of the function AS EXECUTED: a select differentiates the branch taken (the `turn` test of the quaternion update,
 // the gimbal fix-up of quat_to_rpy, the clip of GPD_ACT_RAW_RPM, max(0, .) of the reward).  The cos / sinc polynomials of the quaternion
 // exponential are differentiated as the polynomials they are (the exact path beyond |t| = 1 rad as cos / sinc).
+#include "plant_derive_vjp.inc"
+
 namespace {
 
 __device__ __forceinline__ float norm_thrust_of(const GpdParams& P) { return P.hover_thrust; }
@@ -113,16 +119,27 @@ __device__ __forceinline__ void rpy_vjp(float x, float y, float z, float w, floa
     aw = gimbal ? 0.0f : rw;
 }
 
+// Cotangents of the plant rows the sweep reads (gpd_rollout_vjp_plant), one drone's, in registers for all K steps: the 16 rows of
+// include/gpd.h GPD_PLANT_* that the supported configurations read, as named scalars (an indexed member would live in scratch memory).
+// NoCot stands in where nobody asks for them: the sweep's code is then what it was.
+struct PlantCot {
+    float inv_m = 0.0f, gravity = 0.0f, kf = 0.0f, resid = 0.0f, norm_thrust = 0.0f, norm_gap = 0.0f;
+    float j0 = 0.0f, j1 = 0.0f, j2 = 0.0f, ji0 = 0.0f, ji1 = 0.0f, ji2 = 0.0f, km_over_kf = 0.0f, d0 = 0.0f, d1 = 0.0f, d2 = 0.0f;
+};
+struct NoCot {};
+template <bool GP> using plant_cot_t = std::conditional_t<GP, PlantCot, NoCot>;
+
 // Adjoint of one physics sub-step (substep<> of gpd_common.inc, the terms this entry supports: thrust, torques, Euler's equation, drag,
 // semi-implicit Euler, the exponential quaternion update, the observed world angular velocity).
 //   k        the state the sub-step STARTED from (recomputed by the caller)
 //   a        in: cotangent of the state it left; out: cotangent of the state it started from
 //   b*       AV: cotangent of the observed world angular velocity (pre-update rotation, post-update rates)
 //   ag[4]    += cotangent of the rotor thrust deviations;   a_drag  += cotangent of the rpm sum the drag term saw
-template <bool EXT, bool AV>
+//   G        GP: += cotangents of the plant rows the sub-step reads (inv_M, GRAVITY, J, J_INV, km_over_kf, the drag coefficients)
+template <bool EXT, bool AV, bool GP = false>
 __device__ __forceinline__ void substep_vjp(const GpdParams& P, const float h, const uint32_t flags, const float g[4], const float drag_sum,
                                             const Kin& k, Kin& a, const float bx, const float by, const float bz, float ag[4],
-                                            float& a_drag) {
+                                            float& a_drag, plant_cot_t<GP>& G) {
     const bool drag = EXT && (flags & GPD_PHYS_DRAG);
     // ---- forward: what the reverse pass needs of it
     const Mat3 R = quat_to_mat(k.qx, k.qy, k.qz, k.qw);
@@ -130,7 +147,8 @@ __device__ __forceinline__ void substep_vjp(const GpdParams& P, const float h, c
     const float T = P.GRAVITY + dev;
     const float wsum = drag ? drag_sum * (6.28318530717958647692f / 60.0f) : 0.0f;
     const float kz = (P.drone_model == GPD_MODEL_RACE) ? -P.km_over_kf : P.km_over_kf;
-    const float tz = kz * (((-g[0] + g[1]) - g[2]) + g[3]);
+    const float gz = ((-g[0] + g[1]) - g[2]) + g[3];
+    const float tz = kz * gz;
     const float arm = P.L * 0.70710678118654752440f;
     const float arm_x = (P.drone_model == GPD_MODEL_CF2X) ? -arm : arm;
     const bool plus = P.drone_model == GPD_MODEL_CF2P;
@@ -192,6 +210,15 @@ __device__ __forceinline__ void substep_vjp(const GpdParams& P, const float h, c
     a.wx = awx - fmaf(aty, k.wz * j02, atz * (k.wy * j10));
     a.wy = awy - fmaf(atx, k.wz * j21, atz * (k.wx * j10));
     a.wz = awz - fmaf(atx, k.wy * j21, aty * (k.wx * j02));
+    if constexpr (GP) {
+        // w'_i = w_i + h J_INV[i] tq_i;  tq = t - w x (J w), J w row by row;  tz = +-km_over_kf (-g0 + g1 - g2 + g3)
+        G.ji0 = fmaf(h * tqx, awx, G.ji0); G.ji1 = fmaf(h * tqy, awy, G.ji1); G.ji2 = fmaf(h * tqz, awz, G.ji2);
+        G.j0 = fmaf(fmaf(atz, k.wy, -(aty * k.wz)), k.wx, G.j0);
+        G.j1 = fmaf(fmaf(atx, k.wz, -(atz * k.wx)), k.wy, G.j1);
+        G.j2 = fmaf(fmaf(aty, k.wx, -(atx * k.wy)), k.wz, G.j2);
+        const float a_kz = atz * gz;
+        G.km_over_kf += (P.drone_model == GPD_MODEL_RACE) ? -a_kz : a_kz;
+    }
     const float kzt = kz * atz;
     ag[0] -= kzt; ag[1] += kzt; ag[2] -= kzt; ag[3] += kzt;
     if (plus) {
@@ -209,6 +236,21 @@ __device__ __forceinline__ void substep_vjp(const GpdParams& P, const float h, c
         a.vz = fmaf(-(P.drag_coeff[2] * wsum), afz, a.vz);
         const float a_wsum = -fmaf(P.drag_coeff[0] * k.vx, afx, fmaf(P.drag_coeff[1] * k.vy, afy, (P.drag_coeff[2] * k.vz) * afz));
         a_drag += a_wsum * (6.28318530717958647692f / 60.0f);
+    }
+    if constexpr (GP) {
+        // v' = v + h inv_M F: the force as substep<> assembles it (F_z from the deviation, 1 - R22 computed directly)
+        float Fx = R.r02 * T, Fy = R.r12 * T, Fz = fmaf(R.r22, dev, -(P.GRAVITY * R.m22));
+        if (drag) {
+            Fx = fmaf(-(P.drag_coeff[0] * k.vx), wsum, Fx);
+            Fy = fmaf(-(P.drag_coeff[1] * k.vy), wsum, Fy);
+            Fz = fmaf(-(P.drag_coeff[2] * k.vz), wsum, Fz);
+            G.d0 = fmaf(-(k.vx * wsum), afx, G.d0);
+            G.d1 = fmaf(-(k.vy * wsum), afy, G.d1);
+            G.d2 = fmaf(-(k.vz * wsum), afz, G.d2);
+        }
+        G.inv_m = fmaf(h, fmaf(Fx, avx, fmaf(Fy, avy, Fz * avz)), G.inv_m);
+        // GRAVITY twice: in T = GRAVITY + sum g (the cotangent of T) and in -GRAVITY e_z; together afx R02 + afy R12 - afz (1 - R22)
+        G.gravity += fmaf(afx, R.r02, fmaf(afy, R.r12, -(afz * R.m22)));
     }
     // F = R[:, 2] T - (0, 0, GRAVITY)
     const float a_T = fmaf(afx, R.r02, fmaf(afy, R.r12, afz * R.r22));
@@ -234,18 +276,33 @@ __device__ __forceinline__ void substep_vjp(const GpdParams& P, const float h, c
 
 // Adjoint of map_action<false, AW> (the four RPM action types): out[AW] = cotangent of the raw action row
 //   ag[4]  cotangent of the thrust deviations;  a_sum  cotangent of the step's rpm sum (what the drag terms saw of it)
-template <int AW, class PP>
+//   G      GP: += cotangents of the plant rows the mapping reads: norm_thrust and norm_gap (g = norm_thrust e (2 + e) - norm_gap), or
+//          KF and hover_resid (g = KF (rpm - h)(rpm + h) + hover_resid, at the CLIPPED rpm: a rotor outside the clip still has a thrust)
+template <int AW, bool GP = false, class PP>
 __device__ __forceinline__ void action_vjp(const PP& P, const GpdStepCfg& C, const float4 act, const float rpm[4], const float ag[4],
-                                           const float a_sum, float out[4]) {
+                                           const float a_sum, float out[4], plant_cot_t<GP>& G) {
     const float nt = norm_thrust_of(P);
     if (AW == 1) {                        // one value drives the four rotors
         const float e = 0.05f * act.x;
-        out[0] = 0.05f * fmaf(((ag[0] + ag[1]) + ag[2]) + ag[3], nt * (2.0f + 2.0f * e), 4.0f * a_sum * P.hover_rpm);
+        const float ag_sum = ((ag[0] + ag[1]) + ag[2]) + ag[3];
+        out[0] = 0.05f * fmaf(ag_sum, nt * (2.0f + 2.0f * e), 4.0f * a_sum * P.hover_rpm);
         out[1] = out[2] = out[3] = 0.0f;
+        if constexpr (GP) {
+            G.norm_thrust = fmaf(ag_sum, e * (2.0f + e), G.norm_thrust);
+            G.norm_gap -= ag_sum;
+        }
     } else if (C.act_type == GPD_ACT_RPM) {
         const float av[4] = {act.x, act.y, act.z, act.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) out[i] = 0.05f * fmaf(ag[i], nt * (2.0f + 2.0f * (0.05f * av[i])), a_sum * P.hover_rpm);
+        if constexpr (GP) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float e = 0.05f * av[i];
+                G.norm_thrust = fmaf(ag[i], e * (2.0f + e), G.norm_thrust);
+            }
+            G.norm_gap -= ((ag[0] + ag[1]) + ag[2]) + ag[3];
+        }
     } else {                              // RAW_RPM: zero outside the clip; DIRECT_RPM: as is
         const bool clip = C.act_type == GPD_ACT_RAW_RPM;
         const float av[4] = {act.x, act.y, act.z, act.w};
@@ -254,17 +311,25 @@ __device__ __forceinline__ void action_vjp(const PP& P, const GpdStepCfg& C, con
             const bool inside = !clip || (av[i] >= 0.0f && av[i] <= P.max_rpm);
             out[i] = inside ? fmaf(ag[i], 2.0f * P.KF * rpm[i], a_sum) : 0.0f;
         }
+        if constexpr (GP) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) G.kf = fmaf(ag[i], (rpm[i] - P.hover_rpm) * (rpm[i] + P.hover_rpm), G.kf);
+            G.resid += ((ag[0] + ag[1]) + ag[2]) + ag[3];
+        }
     }
 }
 
-template <bool EXT, int AW, bool PLANT>
+// GP (only with PLANT): the lane also accumulates the cotangents of its drone's plant rows over the whole sweep and stores them once,
+// after the loop, into g_plant [GPD_PLANT_ROWS][ld] -- rows no supported configuration reads as exactly 0.  g_plant is NULL otherwise.
+template <bool EXT, int AW, bool PLANT, bool GP = false>
 __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_kernel(const GpdParams P, const GpdStepCfg C, const int64_t ld, const int K,
                                                                  const float* __restrict__ actions, const int64_t a_stride,
                                                                  const float* __restrict__ target_pos, const float* __restrict__ plant,
                                                                  const float* __restrict__ tape, const float* __restrict__ g_obs12,
                                                                  const int64_t o_stride, const float* __restrict__ g_reward,
                                                                  const int64_t e_stride, float* __restrict__ g_kin,
-                                                                 float* __restrict__ g_actions) {
+                                                                 float* __restrict__ g_actions, float* __restrict__ g_plant) {
+    static_assert(PLANT || !GP, "the plant rows' cotangents need a plant table");
     const uint32_t N = static_cast<uint32_t>(C.num_envs);
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     if (n >= N) return;
@@ -278,6 +343,7 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_kernel(const GpdParams
     const int S = C.substeps;
     Kin A = planes_load(g_kin, ld, n);                         // cotangent of the state after the step in hand
     float a_next = 0.0f;                                       // cotangent of this step's rpm sum from the NEXT step's first drag term
+    plant_cot_t<GP> G;                                         // GP: cotangents of the plant rows, summed over the sweep
     const float first_sum = drag ? tape[static_cast<int64_t>(K) * 13 * ld + n] : 0.0f;
     for (int t = K - 1; t >= 0; --t) {
         const Kin k0 = planes_load(tape + static_cast<int64_t>(t) * 13 * ld, ld, n);
@@ -331,24 +397,49 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_kernel(const GpdParams
                     const float gr = fmaf(-dd, dd, 2.0f) > 0.0f ? 4.0f * dd * grew : 0.0f;
                     A.px = fmaf(gr, ex, A.px); A.py = fmaf(gr, ey, A.py); A.pz = fmaf(gr, ez, A.pz);
                 }
-                substep_vjp<EXT, true>(Q, h, flags, g, ds, k, A, go[9], go[10], go[11], ag, a_drag);
+                substep_vjp<EXT, true, GP>(Q, h, flags, g, ds, k, A, go[9], go[10], go[11], ag, a_drag, G);
             } else {
-                substep_vjp<EXT, false>(Q, h, flags, g, ds, k, A, 0.0f, 0.0f, 0.0f, ag, a_drag);
+                substep_vjp<EXT, false, GP>(Q, h, flags, g, ds, k, A, 0.0f, 0.0f, 0.0f, ag, a_drag, G);
             }
             a_prev += j == 0 ? a_drag : 0.0f;                  // (selects: a branch here makes the two sums an indexed array in scratch)
             a_cur += j == 0 ? 0.0f : a_drag;
         }
         float ga[4];
-        action_vjp<AW>(Q, C, act, rpm, ag, a_cur, ga);
+        action_vjp<AW, GP>(Q, C, act, rpm, ag, a_cur, ga, G);
         float* dst = g_actions + (static_cast<size_t>(t) * N + n) * AW;
         if (AW == 4) *reinterpret_cast<f4v*>(dst) = f4v{ga[0], ga[1], ga[2], ga[3]};
         else dst[0] = ga[0];
         a_next = a_prev;
     }
     planes_store(g_kin, ld, n, A);
+    if constexpr (GP) {
+        const float rows[GPD_PLANT_ROWS] = {0.0f /* M */, G.inv_m, G.kf, G.gravity, G.j0, G.j1, G.j2, G.ji0, G.ji1, G.ji2, G.km_over_kf,
+                                            0.0f /* GND_EFF */, G.d0, G.d1, G.d2, 0.0f /* HOVER_THRUST */, G.resid, G.norm_thrust, G.norm_gap};
+#pragma unroll
+        for (int r = 0; r < GPD_PLANT_ROWS; ++r) st_row(g_plant, ld, r, n * 4u, rows[r]);
+    } else {
+        (void)g_plant;
+    }
 }
 
-// What the three entries check of the configuration and refuse of it, before any device work: the span and the sizes, then what is
+// gpd_plant_derive_vjp: one lane per drone, the transpose of gpd_plant_derive_kernel's Jacobian at the drone's scales -- the formulas of
+// plant_derive_vjp.inc in float64 from the fp32 inputs, one rounding per output, as the derivation itself.
+__global__ __launch_bounds__(256) void gpd_plant_derive_vjp_kernel(const GpdParams P, const float* __restrict__ scales,
+                                                                   const float* __restrict__ g_rows, const uint32_t n, const int64_t ld,
+                                                                   float* __restrict__ g_scales) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    double s[GPD_NUM_SCALES], g[GPD_PLANT_ROWS], out[GPD_NUM_SCALES];
+#pragma unroll
+    for (int k = 0; k < GPD_NUM_SCALES; ++k) s[k] = scales[k * ld + i];
+#pragma unroll
+    for (int r = 0; r < GPD_PLANT_ROWS; ++r) g[r] = g_rows[r * ld + i];
+    gpd_plant_derive_vjp_one(&P, s, g, out);
+#pragma unroll
+    for (int k = 0; k < GPD_NUM_SCALES; ++k) g_scales[k * ld + i] = static_cast<float>(out[k]);
+}
+
+// What the entries of the rollout check of the configuration and refuse of it, before any device work: the span and the sizes, then what is
 // not differentiable.  `ld` comes without the state in two of them.
 int diff_cfg(Refuse bad, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, int64_t stride0 = 0, int64_t stride1 = 0, int64_t stride2 = 0) {
     if (int rc = check_steps(bad, num_steps, stride0, stride1, stride2)) return rc;
@@ -373,6 +464,37 @@ void diff_dispatch(const GpdStepCfg& c, bool plant, F&& launch) {
     with_ext_plant(c.physics_flags != 0, plant, [&](auto ext, auto pl) {
         if (c.act_type == GPD_ACT_ONE_D_RPM) launch(ext, Const<1>{}, pl); else launch(ext, Const<4>{}, pl);
     });
+}
+
+// argument checks + launch shared by gpd_rollout_vjp and gpd_rollout_vjp_plant (g_plant: the plant rows' cotangents, or NULL)
+int vjp_impl(Refuse bad, const GpdParams* params, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, const float* actions,
+             int64_t action_step_stride, const float* target_pos, const float* plant_rows, const float* tape, const float* g_obs12,
+             int64_t obs_step_stride, const float* g_reward, int64_t env_step_stride, float* g_kin, float* g_actions, float* g_plant,
+             void* stream) {
+    if (!params || !cfg) return bad(GPD_EINVAL, "NULL params/cfg");
+    if (!actions || !tape || !g_kin || !g_actions) return bad(GPD_EINVAL, "NULL actions/tape/g_kin/g_actions");
+    if (int rc = diff_cfg(bad, cfg, ld, num_steps, action_step_stride, obs_step_stride, env_step_stride)) return rc;
+    if (int rc = check_needs(bad, params, nullptr, cfg, target_pos, nullptr)) return rc;
+    if (misaligned16(tape) || misaligned16(g_kin)) return bad(GPD_EINVAL, "tape and g_kin must be 16-byte aligned");
+    if (misaligned16(plant_rows)) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
+    if (misaligned16(g_actions)) return bad(GPD_EINVAL, "g_actions must be 16-byte aligned");
+    GpdStepCfg c = *cfg;
+    dummy_target(c, target_pos, tape);
+    const dim3 grid(blocks_for(c.num_envs, kBlock));
+    diff_dispatch(c, plant_rows != nullptr, [&](auto ext, auto aw, auto pl) {
+        constexpr bool EXT = decltype(ext)::value, PLANT = decltype(pl)::value;
+        constexpr int AW = decltype(aw)::value;
+        auto launch = [&](auto gp) {
+            hipLaunchKernelGGL((gpd_rollout_vjp_kernel<EXT, AW, PLANT, decltype(gp)::value>), grid, dim3(kBlock), 0,
+                               static_cast<hipStream_t>(stream), *params, c, ld, num_steps, actions, action_step_stride, target_pos,
+                               plant_rows, tape, g_obs12, obs_step_stride, g_reward, env_step_stride, g_kin, g_actions, g_plant);
+        };
+        if constexpr (PLANT) {
+            if (g_plant) return launch(Const<true>{});
+        }
+        launch(Const<false>{});
+    });
+    return launched(bad.who);
 }
 
 }  // namespace
@@ -419,22 +541,30 @@ int gpd_rollout_vjp(const GpdParams* params, const GpdStepCfg* cfg, int64_t ld, 
                     int64_t action_step_stride, const float* target_pos, const float* plant_rows, const float* tape,
                     const float* g_obs12, int64_t obs_step_stride, const float* g_reward, int64_t env_step_stride, float* g_kin,
                     float* g_actions, void* stream) {
-    const Refuse bad{"gpd_rollout_vjp"};
-    if (!params || !cfg) return bad(GPD_EINVAL, "NULL params/cfg");
-    if (!actions || !tape || !g_kin || !g_actions) return bad(GPD_EINVAL, "NULL actions/tape/g_kin/g_actions");
-    if (int rc = diff_cfg(bad, cfg, ld, num_steps, action_step_stride, obs_step_stride, env_step_stride)) return rc;
-    if (int rc = check_needs(bad, params, nullptr, cfg, target_pos, nullptr)) return rc;
-    if (misaligned16(tape) || misaligned16(g_kin)) return bad(GPD_EINVAL, "tape and g_kin must be 16-byte aligned");
-    if (misaligned16(plant_rows)) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
-    if (misaligned16(g_actions)) return bad(GPD_EINVAL, "g_actions must be 16-byte aligned");
-    GpdStepCfg c = *cfg;
-    dummy_target(c, target_pos, tape);
-    const dim3 grid(blocks_for(c.num_envs, kBlock));
-    diff_dispatch(c, plant_rows != nullptr, [&](auto ext, auto aw, auto pl) {
-        hipLaunchKernelGGL((gpd_rollout_vjp_kernel<decltype(ext)::value, decltype(aw)::value, decltype(pl)::value>), grid, dim3(kBlock), 0,
-                           static_cast<hipStream_t>(stream), *params, c, ld, num_steps, actions, action_step_stride, target_pos, plant_rows,
-                           tape, g_obs12, obs_step_stride, g_reward, env_step_stride, g_kin, g_actions);
-    });
+    return vjp_impl(Refuse{"gpd_rollout_vjp"}, params, cfg, ld, num_steps, actions, action_step_stride, target_pos, plant_rows, tape, g_obs12,
+                    obs_step_stride, g_reward, env_step_stride, g_kin, g_actions, nullptr, stream);
+}
+
+int gpd_rollout_vjp_plant(const GpdParams* params, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, const float* actions,
+                          int64_t action_step_stride, const float* target_pos, const float* plant_rows, const float* tape,
+                          const float* g_obs12, int64_t obs_step_stride, const float* g_reward, int64_t env_step_stride, float* g_kin,
+                          float* g_actions, float* g_plant_rows, void* stream) {
+    const Refuse bad{"gpd_rollout_vjp_plant"};
+    if (!plant_rows || !g_plant_rows) return bad(GPD_EINVAL, "NULL plant_rows/g_plant_rows (the plant rows' cotangents need a plant table)");
+    if (misaligned16(g_plant_rows)) return bad(GPD_EINVAL, "g_plant_rows must be 16-byte aligned");
+    return vjp_impl(bad, params, cfg, ld, num_steps, actions, action_step_stride, target_pos, plant_rows, tape, g_obs12, obs_step_stride,
+                    g_reward, env_step_stride, g_kin, g_actions, g_plant_rows, stream);
+}
+
+int gpd_plant_derive_vjp(const GpdParams* nominal, const float* scales, const float* g_rows, int32_t n, int64_t ld, float* g_scales,
+                         void* stream) {
+    const Refuse bad{"gpd_plant_derive_vjp"};
+    if (!nominal || !scales || !g_rows || !g_scales) return bad(GPD_EINVAL, "NULL nominal/scales/g_rows/g_scales");
+    if (n <= 0) return bad(GPD_EINVAL, "n must be > 0");
+    if (ld <= 0 || ld > 0xffffffffLL) return bad(GPD_EINVAL, "ld must be in 1 .. 2^32 - 1 (floats)");
+    if (int rc = check_extent(bad, n, ld, "ld")) return rc;
+    hipLaunchKernelGGL(gpd_plant_derive_vjp_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), *nominal, scales,
+                       g_rows, static_cast<uint32_t>(n), ld, g_scales);
     return launched(bad.who);
 }
 

@@ -10,6 +10,13 @@ actions and the initial kinematic state (the `[13 * ld]` plane layout of `SimCor
 Feeding `kin_K` of one call into `kin0` of the next chains the graph: K = 1 is the closed-loop primitive, with a torch policy between
 steps.  Supported: single-drone aviaries, no task or the hover task, the four RPM action types, no add-on physics or drag, with or
 without a plant table, no auto-reset; everything else raises `GpdError` with the library's message.  First derivatives only.
+
+    obs12, *_ = core.rollout_diff(actions, plant_scales=scales)                       # scales [9, E] or [9, E, 1], requires_grad
+    loss(obs12).backward()                                                            # scales.grad: d loss / d (the nine scale factors)
+
+With `plant_scales=` the per-drone plant (`SimCore.set_plant`) is the third differentiable input: the call installs the scales as the
+core's plant table, and the backward is `gpd_rollout_vjp_plant` (the same sweep, which also sums the cotangents of the plant rows it
+reads) followed by `gpd_plant_derive_vjp` (rows -> scale factors).  System identification and calibration: examples/sysid.py.
 """
 import ctypes
 
@@ -47,10 +54,12 @@ def tape_floats(core, K: int) -> int:
 
 
 class RolloutDiff(torch.autograd.Function):
-    """forward: `gpd_rollout_tape` from `kin0` (copied into the core's state first); backward: `gpd_rollout_vjp`"""
+    """forward: `gpd_rollout_tape` from `kin0` (copied into the core's state first); backward: `gpd_rollout_vjp`, or -- when
+    `plant_scales` (the scales `rollout_diff` has just installed with `set_plant`) asks for a gradient -- `gpd_rollout_vjp_plant`
+    and `gpd_plant_derive_vjp`"""
 
     @staticmethod
-    def forward(ctx, core, kin0, actions, K, a_stride):
+    def forward(ctx, core, kin0, actions, K, a_stride, plant_scales=None, own_plant=False):
         dev, N, E = core.device, core.N, core.E
         size = tape_floats(core, K)                            # (also the configuration check, before anything is touched)
         if kin0.data_ptr() != core.kin_store.data_ptr():
@@ -67,6 +76,11 @@ class RolloutDiff(torch.autograd.Function):
         core._publish_latest(obs, rew, term, trunc, K)          # (the core's latest-step tensors follow its state, as after rollout())
         ctx.core, ctx.K, ctx.a_stride, ctx.plant = core, K, a_stride, core.plant_rows
         ctx.target = core.target
+        ctx.scales = None
+        if own_plant:          # (copies: the next plant_scales= rewrites the core's tables in place; the backward needs the ones this call flew)
+            ctx.plant = core.plant_rows.clone()
+            if plant_scales is not None and plant_scales.requires_grad:
+                ctx.scales, ctx.scales_shape = core.plant_scales.clone(), plant_scales.shape
         ctx.save_for_backward(actions, tape)
         ctx.mark_non_differentiable(term, trunc)
         ctx.set_materialize_grads(False)                       # (an output nobody differentiates arrives as None: NULL = zeros)
@@ -82,20 +96,32 @@ class RolloutDiff(torch.autograd.Function):
         g_rew = None if g_rew is None else g_rew.to(torch.float32).contiguous()
         g_kin = torch.zeros_like(core.kin_store) if g_kin is None else g_kin.to(torch.float32).clone(memory_format=torch.contiguous_format)
         g_act = torch.empty((K, N, core.A), dtype=torch.float32, device=dev)
-        _native.call("gpd_rollout_vjp", dev, core._stream(), core._params, core._cfg, core.ld, K, actions, ctx.a_stride, ctx.target,
-                     ctx.plant, tape, g_obs, N * 12, g_rew, E, g_kin, g_act)
+        g_scales = None
+        if ctx.scales is None or not ctx.needs_input_grad[5]:
+            _native.call("gpd_rollout_vjp", dev, core._stream(), core._params, core._cfg, core.ld, K, actions, ctx.a_stride, ctx.target,
+                         ctx.plant, tape, g_obs, N * 12, g_rew, E, g_kin, g_act)
+        else:
+            g_rows = torch.empty((_native.PLANT_ROWS, core.ld), dtype=torch.float32, device=dev)     # (both kernels write drones 0 .. N-1)
+            g_table = torch.empty((len(_native.SCALE_FIELDS), core.ld), dtype=torch.float32, device=dev)
+            _native.call("gpd_rollout_vjp_plant", dev, core._stream(), core._params, core._cfg, core.ld, K, actions, ctx.a_stride,
+                         ctx.target, ctx.plant, tape, g_obs, N * 12, g_rew, E, g_kin, g_act, g_rows)
+            _native.call("gpd_plant_derive_vjp", dev, core._stream(), core._params, ctx.scales, g_rows, N, core.ld, g_table)
+            g_scales = g_table[:, :N].reshape(ctx.scales_shape)
         if ctx.a_stride == 0:                                  # a shared action block: its gradient is the sum over the steps
             g_act = g_act.sum(dim=0)
-        return None, g_kin, g_act.view(actions.shape), None, None
+        return None, g_kin, g_act.view(actions.shape), None, None, g_scales, None
 
 
-def rollout_diff(core, actions, kin0=None, num_steps: int = None):
-    """`SimCore.rollout_diff`: K env steps in one launch, differentiable with respect to `actions` and `kin0`.
+def rollout_diff(core, actions, kin0=None, num_steps: int = None, plant_scales=None):
+    """`SimCore.rollout_diff`: K env steps in one launch, differentiable with respect to `actions`, `kin0` and `plant_scales`.
 
     `actions`: float32 device tensor with K x N x A elements (K leading), or -- with `num_steps=K` -- ONE block of N x A elements
     applied at every step (its gradient is the sum over the steps).  `kin0`: None (start from the core's own state) or a `[13 * ld]`
     tensor in the plane layout (`pack_kin`), copied into the state first.  Returns fresh tensors
-    `(obs12 [K,N,12], reward [K,E], kin_K [13*ld], terminated [K,E], truncated [K,E])`; the first three carry gradients."""
+    `(obs12 [K,N,12], reward [K,E], kin_K [13*ld], terminated [K,E], truncated [K,E])`; the first three carry gradients.
+    `plant_scales`: None (the core's plant, or none, as it stands: a constant) or the scale factors in any form `set_plant` accepts.
+    They REPLACE the core's plant table (`set_plant(plant_scales.detach())`, with its validation), the forward then is the one above;
+    a float tensor `[9, E]` / `[9, E, 1]` that requires grad receives its gradient in its own shape."""
     per = core.N * core.A
     if actions.device != core.device or actions.dtype != torch.float32:
         actions = actions.to(device=core.device, dtype=torch.float32)
@@ -120,4 +146,13 @@ def rollout_diff(core, actions, kin0=None, num_steps: int = None):
         if kin0.numel() != 13 * core.ld:
             raise ValueError(f"kin0 has {kin0.numel()} elements, expected 13 x ld = {13 * core.ld} (the plane layout: pack_kin)")
         kin0 = kin0.to(device=core.device, dtype=torch.float32).reshape(-1).contiguous()
-    return RolloutDiff.apply(core, kin0, actions, K, a_stride)
+    if plant_scales is None:
+        return RolloutDiff.apply(core, kin0, actions, K, a_stride)
+    tape_floats(core, K)                                       # (the configuration check, before the plant table is touched)
+    if isinstance(plant_scales, torch.Tensor):
+        plant_scales = plant_scales.to(device=core.device, dtype=torch.float32)
+        core.set_plant(plant_scales.detach())
+    else:
+        core.set_plant(plant_scales)
+        plant_scales = None
+    return RolloutDiff.apply(core, kin0, actions, K, a_stride, plant_scales, True)

@@ -416,14 +416,17 @@ class SimCore:
                 self._latest_terminal(tobs, term, trunc, K)
         return obs, rew, term, trunc
 
-    def rollout_diff(self, actions: torch.Tensor, kin0: torch.Tensor = None, num_steps: int = None):
+    def rollout_diff(self, actions: torch.Tensor, kin0: torch.Tensor = None, num_steps: int = None, plant_scales=None):
         """`rollout()` that `.backward()` goes through (`diff.rollout_diff`: `gpd_rollout_tape` forward, `gpd_rollout_vjp` backward).
         Returns fresh tensors `(obs12 [K,N,12], reward [K,E], kin_K [13*ld], terminated [K,E], truncated [K,E])`; obs12, reward and
         kin_K carry gradients with respect to `actions` and `kin0` (None: the core's own state; else the plane layout, copied into the
         state first -- `kin_K` of one call as `kin0` of the next chains the graph).  Single-drone aviaries, the RPM action types, no
-        add-on physics or drag, no auto-reset: GpdError otherwise."""
+        add-on physics or drag, no auto-reset: GpdError otherwise.
+        `plant_scales` (anything `set_plant` accepts) REPLACES the core's plant table, as `set_plant` does, before the forward; a
+        float tensor `[9, E]` / `[9, E, 1]` among them that requires grad is the third differentiable input (`gpd_rollout_vjp_plant`
+        and `gpd_plant_derive_vjp` in the backward) and receives its gradient in its own shape."""
         from . import diff
-        return diff.rollout_diff(self, actions, kin0, num_steps)
+        return diff.rollout_diff(self, actions, kin0, num_steps, plant_scales)
 
     def _fixed_args(self):
         """the arguments of gpd_step / gpd_rollout* that never change between two calls, as ctypes objects (set_target() drops them)"""

@@ -172,12 +172,13 @@ class VectorAviary:
             self.core.full_obs(actions, num_steps=K, want_rows=False)      # ring update only
         return obs.view(K, self.NUM_ENVS, self.NUM_DRONES, -1), reward, terminated, truncated
 
-    def rollout_diff(self, actions: torch.Tensor, kin0: torch.Tensor = None):
+    def rollout_diff(self, actions: torch.Tensor, kin0: torch.Tensor = None, plant_scales=None):
         """The differentiable rollout (`SimCore.rollout_diff`): actions (K, E, 1, A) -> (obs12 (K,E,1,12), reward (K,E), kin_K [13*ld],
         terminated (K,E), truncated (K,E)); obs12, reward and kin_K carry gradients with respect to `actions` and `kin0` (the plane
         layout of the kinematic state, `diff.pack_kin`; None: the current state).  The kinematic rows only: the action history is
-        neither pushed nor differentiated."""
-        obs, reward, kin_k, terminated, truncated = self.core.rollout_diff(actions, kin0)
+        neither pushed nor differentiated.  `plant_scales` ([9, E] / [9, E, 1], or anything else `set_plant` accepts) replaces the
+        plant table first, as `set_plant` does, and -- a float tensor that requires grad -- receives its gradient too."""
+        obs, reward, kin_k, terminated, truncated = self.core.rollout_diff(actions, kin0, plant_scales=plant_scales)
         return obs.view(-1, self.NUM_ENVS, self.NUM_DRONES, 12), reward, kin_k, terminated, truncated
 
     def rollout_policy(self, policy, num_steps: int, noise: torch.Tensor = None, action_std=None, mean_out: torch.Tensor = None):

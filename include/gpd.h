@@ -877,7 +877,21 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream);
  * branches of the Euler extraction, the clip of GPD_ACT_RAW_RPM -- zero gradient outside its bounds --, max(0, .) of the reward).  The
  * observed world angular velocity uses the pre-update rotation and the post-update rates, and so does its adjoint.  The drag term of
  * a step's first sub-step sees the previous step's RPMs: inside one call that dependence is differentiated, the value carried in
- * from before the call is a constant.  Plant rows and targets are constants of the sweep.
+ * from before the call is a constant.  Targets are constants of the sweep, and so are the plant rows in gpd_rollout_vjp.
+ *
+ * gpd_rollout_vjp_plant is gpd_rollout_vjp on a taped call that had a plant table (plant_rows != NULL, else GPD_EINVAL), and writes
+ * g_kin and g_actions exactly as it does; the lane that walks the steps also sums, in registers, the cotangent of every plant row
+ * the sweep reads and stores them once after the loop (no atomics):
+ *   g_plant_rows        [GPD_PLANT_ROWS][ld] out, 16-byte aligned, drones 0 .. N-1 of every row overwritten: the cotangents of
+ *                       INV_M, GRAVITY (it enters the total thrust and the weight), KF and HOVER_RESID (the raw RPM action types, at the
+ *                       CLIPPED rpm), NORM_THRUST and NORM_GAP (the normalised action types), J[0..2] and J_INV[0..2] (independent rows,
+ *                       as the forward reads them), KM_OVER_KF, DRAG[0..2].  Rows the supported configurations never read -- M, GND_EFF,
+ *                       HOVER_THRUST, and the drag rows without GPD_PHYS_DRAG -- are exactly 0
+ * gpd_plant_derive_vjp takes them to the nine scale factors: g_scales [GPD_NUM_SCALES][ld] (drones 0 .. n-1 overwritten) is the
+ * transpose of gpd_plant_derive's Jacobian at `scales` applied to g_rows [GPD_PLANT_ROWS][ld], in double with one rounding per
+ * output, e.g.  g_mass = M_n g_M - inv_M_n / s_mass^2 g_INV_M + GRAVITY_n g_GRAVITY + hover_thrust_n (g_HOVER_THRUST - g_HOVER_RESID
+ * + g_NORM_GAP).  The action mapping's HOVER_RPM and the MAX_RPM clip are nominal and have no cotangent; targets and the RPMs carried
+ * in from before the call stay constants.
  *
  * Supported: drones_per_env == 1; GPD_TASK_NONE and GPD_TASK_HOVER; GPD_ACT_RPM, ONE_D_RPM, RAW_RPM and DIRECT_RPM; physics_flags 0
  * or GPD_PHYS_DRAG; all three airframes; auto_reset == 0.  Everything else (the DSLPID action types, the other flags, D > 1,
@@ -891,6 +905,12 @@ int gpd_rollout_vjp(const GpdParams* params, const GpdStepCfg* cfg, int64_t ld, 
                     int64_t action_step_stride, const float* target_pos, const float* plant_rows, const float* tape,
                     const float* g_obs12, int64_t obs_step_stride, const float* g_reward, int64_t env_step_stride, float* g_kin,
                     float* g_actions, void* stream);
+int gpd_rollout_vjp_plant(const GpdParams* params, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, const float* actions,
+                          int64_t action_step_stride, const float* target_pos, const float* plant_rows, const float* tape,
+                          const float* g_obs12, int64_t obs_step_stride, const float* g_reward, int64_t env_step_stride, float* g_kin,
+                          float* g_actions, float* g_plant_rows, void* stream);
+int gpd_plant_derive_vjp(const GpdParams* nominal, const float* scales, const float* g_rows, int32_t n, int64_t ld, float* g_scales,
+                         void* stream);
 
 #ifdef __cplusplus
 }

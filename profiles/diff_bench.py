@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What the differentiable rollout costs, and what it is measured against.
 
-    python profiles/diff_bench.py [--out profiles/diff_mi355x.json] [--grad-figures FILE]
+    python profiles/diff_bench.py [--out profiles/diff_mi355x.json] [--grad-figures FILE] [--registers FILE] [--no-torch]
 
 65 536 single-drone HoverAviaries, Physics.DYN, ActionType.RPM, K = 20 env steps per launch, observation rows of every step stored, at
 S = 1 (240 Hz control) and S = 8 (30 Hz control) physics sub-steps per step.  Timed with device events in ONE process, in turns, each
@@ -9,10 +9,15 @@ until it has run for at least 0.25 s after warm-up; us per ENV STEP:
   rollout          the yardstick: `gpd_rollout` (the kernel this change does not touch) on the same box
   rollout_tape     `gpd_rollout_tape`: the same arithmetic + the 52 B per drone-step tape
   rollout_vjp      `gpd_rollout_vjp`: the reverse sweep (cotangents for every output)
+  vjp_table        `gpd_rollout_vjp` on a per-drone plant table (scales within +-20 %): the sweep without the rows' cotangents
+  vjp_plant        `gpd_rollout_vjp_plant` on the same table and tape: the sweep that also sums the cotangents of the plant rows
+  derive_vjp       `gpd_plant_derive_vjp`: rows -> scale factors (us per CALL / K, to add to vjp_plant)
   torch_autograd   the user's alternative: the float32 torch restatement of tests/helpers/diff_f64.py on the device, forward +
-                   `.backward()` for the same gradient (one launch per arithmetic operation; timed for at least 3 passes)
-No time is a pass condition.  `--grad-figures`: a JSON file of measured gradient errors (tests/test_gpu_diff.py prints them) to record
-next to the timings.
+                   `.backward()` for the same gradient (one launch per arithmetic operation; timed for at least 3 passes; `--no-torch`
+                   leaves it out)
+No time is a pass condition.  `--grad-figures`: a JSON file of measured gradient errors (tests/test_gpu_diff.py and
+tests/test_gpu_sysid.py print them), `--registers`: a JSON file of the kernels' register counts (the compiler's
+`-Rpass-analysis=kernel-resource-usage` remarks), both to record next to the timings.
 """
 import argparse
 import json
@@ -42,7 +47,7 @@ def timed(fn, calls):
     return a.elapsed_time(b) * 1e-3
 
 
-def variants(S, dev):
+def variants(S, dev, with_torch=True):
     core = engine.SimCore(num_envs=N, drones_per_env=1, pyb_freq=240, ctrl_freq=240 // S, act_code=0, task=engine.TASK_HOVER,
                           target_pos=[[0.0, 0.0, 1.0]], auto_reset=False, track_rpm=True, device=dev)
     g = torch.Generator(device=dev).manual_seed(S)
@@ -79,21 +84,47 @@ def variants(S, dev):
         loss = (g_obs * o).sum() + (g_rew * r).sum() + sum((gk * x).sum() for gk, x in zip(unpack_kin(g_kin, N), kk))
         torch.autograd.grad(loss, (a,) + k0)
 
-    rollout_tape()                                             # (the reverse sweep reads this tape)
-    return {"rollout": (rollout, 10), "rollout_tape": (rollout_tape, 10), "rollout_vjp": (rollout_vjp, 10), "torch_autograd": (torch_autograd, 1)}
+    # the same drones with a plant table: a core of its own, so that the nominal variants above keep the uniform kernels
+    plant = engine.SimCore(num_envs=N, drones_per_env=1, pyb_freq=240, ctrl_freq=240 // S, act_code=0, task=engine.TASK_HOVER,
+                           target_pos=[[0.0, 0.0, 1.0]], auto_reset=False, track_rpm=True, device=dev)
+    plant.set_plant(torch.rand((9, N), generator=g, device=dev) * 0.4 + 0.8)
+    p_tape = torch.empty_like(tape)
+    g_rows = torch.empty((_native.PLANT_ROWS, plant.ld), device=dev)
+    g_scales = torch.empty((len(_native.SCALE_FIELDS), plant.ld), device=dev)
+    sweep = (plant._params, plant._cfg, plant.ld, K, acts, N * 4, plant.target, plant.plant_rows, p_tape, g_obs, N * 12, g_rew, N, g_kin, g_act)
+
+    def vjp_table():
+        _native.call("gpd_rollout_vjp", dev, plant._stream(), *sweep)
+
+    def vjp_plant():
+        _native.call("gpd_rollout_vjp_plant", dev, plant._stream(), *sweep, g_rows)
+
+    def derive_vjp():
+        _native.call("gpd_plant_derive_vjp", dev, plant._stream(), plant._params, plant.plant_scales, g_rows, N, plant.ld, g_scales)
+
+    rollout_tape()                                             # (the reverse sweeps read these tapes)
+    _native.call("gpd_rollout_tape", dev, plant._stream(), plant._params, plant._state, plant._cfg, K, acts, N * 4, plant.target, obs, N * 12,
+                 rew, flags[0], flags[1], N, plant.plant_rows, p_tape)
+    jobs = {"rollout": (rollout, 10), "rollout_tape": (rollout_tape, 10), "rollout_vjp": (rollout_vjp, 10), "vjp_table": (vjp_table, 10),
+            "vjp_plant": (vjp_plant, 10), "derive_vjp": (derive_vjp, 10)}
+    if with_torch:
+        jobs["torch_autograd"] = (torch_autograd, 1)
+    return jobs
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--grad-figures", default=None)
+    ap.add_argument("--registers", default=None)
+    ap.add_argument("--no-torch", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     res = {"method": "HIP events, >= 0.25 s per variant after warm-up (torch_autograd: >= 3 passes), the variants in turns in one process; "
                      "rollout and rollout_tape include the 3.4 MB copy that restores the initial state",
            "device": torch.cuda.get_device_name(0), "drones": N, "steps_per_launch": K, "us_per_env_step": {}, "tape_bytes_per_drone_step": 52}
     for S in (1, 8):
-        jobs = variants(S, dev)
+        jobs = variants(S, dev, not a.no_torch)
         for fn, _ in jobs.values():                            # warm-up
             fn()
         torch.cuda.synchronize()
@@ -109,11 +140,15 @@ def main():
         u = {k: spent[k] / (done[k] * K) * 1e6 for k in jobs}
         u["tape_over_rollout"] = u["rollout_tape"] / u["rollout"]
         u["vjp_over_rollout"] = u["rollout_vjp"] / u["rollout"]
-        u["torch_autograd_over_tape_plus_vjp"] = u["torch_autograd"] / (u["rollout_tape"] + u["rollout_vjp"])
+        u["vjp_plant_over_vjp_table"] = u["vjp_plant"] / u["vjp_table"]
+        if "torch_autograd" in u:
+            u["torch_autograd_over_tape_plus_vjp"] = u["torch_autograd"] / (u["rollout_tape"] + u["rollout_vjp"])
         res["us_per_env_step"][f"S={S}"] = u
         print(f"S={S}", json.dumps(u), flush=True)
     if a.grad_figures and os.path.exists(a.grad_figures):
         res["gradient_error_vs_float64"] = json.load(open(a.grad_figures))
+    if a.registers and os.path.exists(a.registers):
+        res["registers"] = json.load(open(a.registers))
     print(json.dumps(res))
     if a.out:
         json.dump(res, open(a.out, "w"), indent=1)

@@ -1,0 +1,296 @@
+"""Gradients with respect to the plant scales on the device (include/gpd.h `gpd_rollout_vjp_plant` / `gpd_plant_derive_vjp`,
+`rollout_diff(..., plant_scales=)` of gym_pybullet_drones_amd/diff.py): against float64 autograd over the restatement of
+tests/helpers/sysid_f64.py (which tests/test_host_sysid.py holds against finite differences), the sweep's other outputs bit for bit
+those of `gpd_rollout_vjp`, determinism, the scaling identity, the unchanged forward, chaining, the input's shapes, the refusal, and
+what the gradients are for: recovering hidden airframes from their recorded flight.  N = 70 drones (ld = 128: two waves, one ragged)
+unless stated otherwise."""
+import importlib.util
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import REPO
+
+sys.path.insert(0, os.path.join(REPO, "tests", "helpers"))
+import diff_f64 as ref  # noqa: E402
+import sysid_f64 as sid  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+N = 70
+MODELS = {"cf2x": "CF2X", "cf2p": "CF2P", "racer": "RACE"}
+
+
+def _core(cfg, dev, n=N, task="hover"):
+    from gym_pybullet_drones_amd import engine
+    from gym_pybullet_drones_amd.utils.enums import DroneModel
+    return engine.SimCore(drone_model=getattr(DroneModel, MODELS[cfg.model]), num_envs=n, drones_per_env=1, physics=2 if cfg.drag else 0,
+                          pyb_freq=240, ctrl_freq=240 // cfg.S, act_code=ref.ACT_CODE[cfg.act],
+                          task=engine.TASK_HOVER if task == "hover" else engine.TASK_NONE, target_pos=[[0.0, 0.0, 1.0]], auto_reset=False,
+                          track_rpm=True, device=dev)
+
+
+def _set(core, inp):
+    """the inputs' state into the core (the logical [13, n] rows; the RPMs the first drag term sees)"""
+    kin = np.concatenate([inp.pos, inp.quat, inp.vel, inp.rates], axis=1).T
+    core.set_state(kin=torch.as_tensor(kin, dtype=torch.float32), last_rpm=torch.as_tensor(inp.last_rpm.T, dtype=torch.float32),
+                   step_counter=torch.zeros(core.E, dtype=torch.int32))
+
+
+def _loss(inp, dev, obs, rew, kin_k, n):
+    from gym_pybullet_drones_amd.diff import unpack_kin
+    T = lambda v: torch.as_tensor(v, dtype=torch.float32, device=dev)     # noqa: E731
+    loss = (T(inp.g_rew) * rew).sum() + (T(inp.g_obs) * obs).sum()
+    if kin_k is not None:
+        loss = loss + sum((T(g) * k).sum() for g, k in zip((inp.g_pos, inp.g_quat, inp.g_vel, inp.g_rates), unpack_kin(kin_k, n)))
+    return loss
+
+
+def device_scale_grads(core, inp, scales, dev, flat=False):
+    """gradient of sum(cotangent * output) with respect to the scales through `SimCore.rollout_diff(..., plant_scales=)`: the tensor
+    as autograd returns it ([9, N, 1], or [9, N] with `flat`)"""
+    _set(core, inp)
+    s = torch.as_tensor(scales, dtype=torch.float32, device=dev).view((9, N) if flat else (9, N, 1)).requires_grad_(True)
+    a = torch.as_tensor(inp.actions, dtype=torch.float32, device=dev)
+    obs, rew, kin_k, _, _ = core.rollout_diff(a, plant_scales=s)
+    (g,) = torch.autograd.grad(_loss(inp, dev, obs, rew, kin_k, inp.n), [s])
+    assert g.shape == s.shape and g.dtype == torch.float32
+    return g
+
+
+@pytest.fixture(scope="module")
+def runs(gpu_device):
+    """every run once: (cfg, scales, the float64 reference [9, N], the device's gradient [9, N] as float64)"""
+    out = {}
+    for name, ones in sid.RUNS:
+        cfg, K, scales = sid.case(name, ones=ones)
+        core = _core(cfg, gpu_device)
+        inp = ref.make_inputs(core.P, cfg, N, K, seed=1)
+        g64 = sid.scale_grads(core.P, cfg, inp, scales, torch.float64)
+        got = device_scale_grads(core, inp, scales, gpu_device).view(9, N).cpu().numpy().astype(np.float64)
+        out[name, ones] = (cfg, scales, g64, got)
+    return out
+
+
+# ---- 1. gradients against the float64 reference -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,ones", sid.RUNS)
+def test_scale_gradients_match_float64_autograd(runs, name, ones):
+    """max |g32 - g64| / max |g64| per scale, the four cases and the all-ones run: below 1e-4, the project's fp32 tolerance (DESIGN.md
+    section 4) and the first-run bound of tests/test_gpu_diff.py.  Scales the configuration does not read come out exactly 0."""
+    cfg, _, g64, got = runs[name, ones]
+    err = sid.scale_errors(got, g64)
+    print("MEASURED", name, "ones" if ones else "random", " ".join(f"{k}={v:.2e}" for k, v in err.items()))
+    assert np.isfinite(got).all()
+    assert not got[sid.SCALES.index("gnd_eff")].any()
+    if not cfg.drag:
+        assert not got[sid.SCALES.index("drag_xy")].any() and not got[sid.SCALES.index("drag_z")].any()
+    if cfg.act == "one_d_rpm":          # four equal thrusts: no yaw torque, whatever KM is
+        assert np.abs(got[sid.SCALES.index("km")]).max() <= 1e-6 * np.abs(g64).max(axis=1).max()
+    assert set(err) | {"km"} == set(sid.SCALES) - {"gnd_eff"} - (set() if cfg.drag else {"drag_xy", "drag_z"})
+    assert max(err.values()) < 1e-4, err
+
+
+# ---- 2. / 3. the same sweep, deterministic ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["drag_k8_s2", "one_d_racer_k2_s8"])
+def test_sweep_writes_the_bits_of_gpd_rollout_vjp_and_two_sweeps_agree(gpu_device, name):
+    """g_kin and g_actions of gpd_rollout_vjp_plant are bit for bit those of gpd_rollout_vjp on the same tape; two sweeps give the same
+    bits, the rows' cotangents included; rows M, GND_EFF and HOVER_THRUST are exactly 0 and nothing past drone N - 1 is written"""
+    from gym_pybullet_drones_amd import _native
+    from gym_pybullet_drones_amd.diff import tape_floats
+    cfg, K, scales = sid.case(name)
+    core = _core(cfg, gpu_device)
+    core.set_plant(torch.as_tensor(scales, dtype=torch.float32, device=gpu_device).view(9, N, 1))
+    inp = ref.make_inputs(core.P, cfg, N, K, seed=1)
+    _set(core, inp)
+    T = lambda v: torch.as_tensor(v, dtype=torch.float32, device=gpu_device).contiguous()     # noqa: E731
+    A = inp.A
+    acts, tape = T(inp.actions), torch.empty(tape_floats(core, K), dtype=torch.float32, device=gpu_device)
+    obs, rew = torch.empty((K, N, 12), device=gpu_device), torch.empty((K, N), device=gpu_device)
+    flags = torch.empty((2, K, N), dtype=torch.bool, device=gpu_device)
+    _native.call("gpd_rollout_tape", gpu_device, core._stream(), core._params, core._state, core._cfg, K, acts, N * A, core.target, obs,
+                 N * 12, rew, flags[0], flags[1], N, core.plant_rows, tape)
+    g_kin0 = torch.randn(13 * core.ld, device=gpu_device)
+    g_obs, g_rew = T(inp.g_obs), T(inp.g_rew)
+
+    def sweep(with_rows):
+        g_kin, g_act = g_kin0.clone(), torch.full((K, N, A), float("nan"), device=gpu_device)
+        g_rows = torch.full((_native.PLANT_ROWS, core.ld), 7.0, device=gpu_device)
+        args = (core._params, core._cfg, core.ld, K, acts, N * A, core.target, core.plant_rows, tape, g_obs, N * 12, g_rew, N, g_kin, g_act)
+        if with_rows:
+            _native.call("gpd_rollout_vjp_plant", gpu_device, core._stream(), *args, g_rows)
+        else:
+            _native.call("gpd_rollout_vjp", gpu_device, core._stream(), *args)
+        return g_kin, g_act, g_rows
+
+    plain, first, second = sweep(False), sweep(True), sweep(True)
+    assert torch.equal(plain[0], first[0]) and torch.equal(plain[1], first[1]) and bool(torch.isfinite(first[1]).all())
+    assert all(torch.equal(a, b) for a, b in zip(first, second))
+    rows = first[2]
+    assert bool((rows[:, N:] == 7.0).all()) and bool(torch.isfinite(rows[:, :N]).all())
+    fields = _native.PLANT_ROW_FIELDS
+    for unread in ("M", "gnd_eff_coeff", "hover_thrust"):
+        assert not rows[fields.index(unread), :N].any(), unread
+    for k in range(3):
+        assert bool(rows[fields.index(f"drag_coeff[{k}]"), :N].any()) == cfg.drag
+    for read in ("inv_M", "GRAVITY", "J[0]", "J[1]", "J[2]", "J_INV[0]", "J_INV[1]", "J_INV[2]", "norm_thrust", "norm_gap"):
+        assert rows[fields.index(read), :N].all(), read
+    assert not rows[fields.index("KF"), :N].any() and not rows[fields.index("hover_resid"), :N].any()      # (the raw RPM types' rows)
+
+
+# ---- 4. the scaling identity --------------------------------------------------------------------------------------------------------
+def test_scaling_identity_on_the_device(runs):
+    """mass, the inertias, KF, KM and the drag scaled by one factor change nothing: |sum_{i<8} s_i g_i| <= 1e-4 sum |s_i g_i| per
+    drone on drag_k8_s2 (the float32 restatement gives 2.4e-6)"""
+    _, scales, _, got = runs["drag_k8_s2", False]
+    terms = scales[:8] * got[:8]
+    rel = np.abs(terms.sum(axis=0)) / np.abs(terms).sum(axis=0)
+    print("MEASURED scaling identity", f"{rel.max():.2e}")
+    assert rel.max() <= 1e-4
+
+
+# ---- 5. the forward is unchanged ---------------------------------------------------------------------------------------------------
+def test_forward_with_plant_scales_is_bitwise_set_plant_and_rollout(gpu_device):
+    cfg, K, scales = sid.case("drag_k8_s2")
+    a_core, b_core = _core(cfg, gpu_device), _core(cfg, gpu_device)
+    inp = ref.make_inputs(a_core.P, cfg, N, K, seed=4)
+    acts = torch.as_tensor(inp.actions, dtype=torch.float32, device=gpu_device)
+    s = torch.as_tensor(scales, dtype=torch.float32, device=gpu_device).view(9, N, 1)
+    _set(a_core, inp)
+    _set(b_core, inp)
+    a_core.set_plant(s)
+    want = [t.clone() for t in a_core.rollout(acts)]
+    got = b_core.rollout_diff(acts, plant_scales=s.clone().requires_grad_(True))
+    for w, g in zip(want, (got[0], got[1], got[3], got[4])):
+        assert torch.equal(w.view(g.shape), g)
+    for name in ("kin_store", "last_rpm", "step_counter"):
+        assert torch.equal(getattr(a_core, name), getattr(b_core, name)), name
+    for name in ("plant_scales", "plant_rows"):          # (the tables' padding past N is never written)
+        assert torch.equal(getattr(a_core, name)[:, :N], getattr(b_core, name)[:, :N]), name
+    assert got[0].requires_grad and torch.equal(b_core.plant_view(), s)          # (the core's table was replaced, as set_plant does)
+
+
+# ---- 6. chaining ---------------------------------------------------------------------------------------------------------------------
+def test_three_chained_calls_sharing_one_scales_tensor_match_one_call(gpu_device):
+    """K = 12 in one call and three chained calls of 4 (kin_K of one as kin0 of the next, the same scales tensor in each): autograd
+    sums the three contributions in another order than the one sweep does, so 1e-4 per scale, not the bits"""
+    cfg = ref.config("cf2x", "rpm", 2, True, "hover")
+    _, _, scales = sid.case("drag_k8_s2")
+    core = _core(cfg, gpu_device)
+    inp = ref.make_inputs(core.P, cfg, N, 12, seed=6)
+    one = device_scale_grads(core, inp, scales, gpu_device).view(9, N).cpu().numpy().astype(np.float64)
+    _set(core, inp)
+    s = torch.as_tensor(scales, dtype=torch.float32, device=gpu_device).view(9, N, 1).requires_grad_(True)
+    a = torch.as_tensor(inp.actions, dtype=torch.float32, device=gpu_device)
+    kin, obs, rew = None, [], []
+    for i in range(3):
+        o, r, kin, _, _ = core.rollout_diff(a[4 * i:4 * i + 4], kin, plant_scales=s)
+        obs.append(o)
+        rew.append(r)
+    (g,) = torch.autograd.grad(_loss(inp, gpu_device, torch.cat(obs), torch.cat(rew), kin, N), [s])
+    err = sid.scale_errors(g.view(9, N).cpu().numpy(), one)
+    print("MEASURED chained", " ".join(f"{k}={v:.2e}" for k, v in err.items()))
+    assert len(err) == 8 and max(err.values()) < 1e-4, err
+
+
+# ---- 7. the input's shapes, the aviary's method -----------------------------------------------------------------------------------
+def test_a_9_by_e_input_gets_a_9_by_e_gradient(gpu_device, runs):
+    cfg, K, scales = sid.case("rpm_k3_s1")
+    core = _core(cfg, gpu_device)
+    inp = ref.make_inputs(core.P, cfg, N, K, seed=1)
+    g = device_scale_grads(core, inp, scales, gpu_device, flat=True)
+    assert g.shape == (9, N)
+    assert np.array_equal(g.cpu().numpy().astype(np.float64), runs["rpm_k3_s1", False][3])          # (the bits of the [9, E, 1] input's)
+    # a tensor that asks for no gradient, and a dict: the plant is installed, the existing sweep serves the backward
+    a = torch.as_tensor(inp.actions, dtype=torch.float32, device=gpu_device).requires_grad_(True)
+    for form in (torch.as_tensor(scales, dtype=torch.float32, device=gpu_device), {"mass": 1.1}):
+        _set(core, inp)
+        obs = core.rollout_diff(a, plant_scales=form)[0]
+        (ga,) = torch.autograd.grad(obs.sum(), [a])
+        assert bool(torch.isfinite(ga).all()) and bool(ga.any())
+    assert float(core.plant_view()[0].min()) == float(core.plant_view()[0].max()) == pytest.approx(1.1)
+
+
+def test_a_pending_backward_reads_the_table_its_call_flew(gpu_device):
+    """two calls with different plant_scales that ask for no gradient, then the backward of the FIRST: its action gradient is that of
+    the first call alone, bit for bit (the second call rewrote the core's tables in place; the first keeps a copy of its rows)"""
+    cfg, K, scales = sid.case("rpm_k3_s1")
+    core = _core(cfg, gpu_device)
+    inp = ref.make_inputs(core.P, cfg, N, K, seed=1)
+    first = torch.as_tensor(scales, dtype=torch.float32, device=gpu_device)
+    a = torch.as_tensor(inp.actions, dtype=torch.float32, device=gpu_device).requires_grad_(True)
+    _set(core, inp)
+    (alone,) = torch.autograd.grad(core.rollout_diff(a, plant_scales=first)[0].sum(), [a])
+    _set(core, inp)
+    obs = core.rollout_diff(a, plant_scales=first)[0]
+    _set(core, inp)
+    core.rollout_diff(a, plant_scales={"mass": 1.3, "kf": 0.7})
+    (pending,) = torch.autograd.grad(obs.sum(), [a])
+    assert torch.equal(alone, pending)
+
+
+def test_vector_aviary_rollout_diff_takes_plant_scales(gpu_device):
+    from gym_pybullet_drones_amd.envs import VectorHoverAviary
+    from gym_pybullet_drones_amd.utils.enums import ActionType
+    env = VectorHoverAviary(N, act=ActionType.RPM, ctrl_freq=30, auto_reset=False, device=gpu_device)
+    env.reset()
+    s = torch.ones((9, N), device=gpu_device, requires_grad=True)
+    obs, rew, kin_k, term, trunc = env.rollout_diff(torch.zeros((4, N, 1, 4), device=gpu_device), plant_scales=s)
+    assert obs.shape == (4, N, 1, 12)
+    obs[..., 2].sum().backward()
+    # hover RPMs: a heavier airframe sinks, a stronger rotor climbs; nothing turns, so the inertias do not matter
+    assert s.grad.shape == (9, N) and bool((s.grad[0] < 0).all()) and bool((s.grad[4] > 0).all()) and not s.grad[8].any()
+
+
+# ---- 8. the refusal ---------------------------------------------------------------------------------------------------------------
+def test_plant_scales_on_an_unsupported_configuration_raises_gpderror_with_the_librarys_message(gpu_device):
+    from gym_pybullet_drones_amd import _native, engine
+    core = engine.SimCore(num_envs=8, drones_per_env=1, act_code=1, task=engine.TASK_HOVER, target_pos=[[0.0, 0.0, 1.0]], device=gpu_device)
+    before = core.kin_store.clone()
+    s = torch.ones((9, 8), device=gpu_device, requires_grad=True)
+    with pytest.raises(_native.GpdError, match="gpd_rollout_tape_floats: the DSLPID action types are not differentiable"):
+        core.rollout_diff(torch.zeros((2, 8, 3), device=gpu_device), plant_scales=s)
+    assert torch.equal(before, core.kin_store) and core.plant_rows is None          # (nothing was touched)
+    with pytest.raises(ValueError, match="set_plant"):
+        _core(ref.config(), gpu_device).rollout_diff(torch.zeros((2, N, 4), device=gpu_device), plant_scales=torch.zeros((9, N), device=gpu_device))
+
+
+# ---- 9. identification -------------------------------------------------------------------------------------------------------------
+def test_hidden_mass_and_inertia_scales_are_recovered_from_the_recorded_flight(gpu_device):
+    """64 cf2x airframes, RPM actions, S = 1, K = 32, no task; hidden mass / Ixx / Iyy / Izz scales from U(0.75, 1.25); the record is
+    the device's own rollout with the true table.  Adam (lr 0.05) on the log-scales from nominal, 200 iterations, loss on obs12 with
+    the angular velocity weighted 0.1: every fitted scale within 1e-3 relative (the float64 and float32 restatements reach 6.5e-5)."""
+    n, K = 64, 32
+    cfg = ref.config("cf2x", "rpm", 1, False, "none")
+    core = _core(cfg, gpu_device, n=n, task="none")
+    rng = np.random.default_rng(0)
+    kin0 = core.kin_store.clone()
+    acts = torch.as_tensor(rng.uniform(-1.0, 1.0, (K, n, 4)), dtype=torch.float32, device=gpu_device)
+    true = torch.ones((9, n), device=gpu_device)
+    true[:4] = torch.as_tensor(rng.uniform(0.75, 1.25, (4, n)), dtype=torch.float32, device=gpu_device)
+    recorded = core.rollout_diff(acts, kin0, plant_scales=true)[0].detach()
+    log_s = torch.zeros((4, n), device=gpu_device, requires_grad=True)
+    opt = torch.optim.Adam([log_s], lr=0.05)
+    rest = torch.ones((5, n), device=gpu_device)
+    for _ in range(200):
+        opt.zero_grad()
+        obs = core.rollout_diff(acts, kin0, plant_scales=torch.cat([torch.exp(log_s), rest]))[0]
+        d2 = (obs - recorded) ** 2
+        (d2[..., :9].sum() + 0.1 * d2[..., 9:].sum()).backward()
+        opt.step()
+    err = (torch.exp(log_s.detach()) / true[:4] - 1.0).abs().max(dim=1).values.cpu().numpy()
+    print("MEASURED identification: worst relative error of mass / ixx / iyy / izz", " ".join(f"{e:.2e}" for e in err))
+    assert err.max() < 1e-3, err
+
+
+# ---- 10. the example ---------------------------------------------------------------------------------------------------------------
+def test_example_sysid_recovers_256_airframes(gpu_device):
+    spec = importlib.util.spec_from_file_location("example_sysid", os.path.join(REPO, "examples", "sysid.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    err, losses = m.run(num_envs=256, device=gpu_device, verbose=False)
+    print("MEASURED example: worst relative error per scale", " ".join(f"{e:.2e}" for e in err.max(axis=1)))
+    assert err.shape == (4, 256) and losses[-1] < losses[0]
+    assert err.max() < 1e-3, err.max(axis=1)
