@@ -53,6 +53,33 @@ def tape_floats(core, K: int) -> int:
     return out.value
 
 
+def tape_forward(core, K, actions, a_stride, obs, rew, term, trunc, tape):
+    """one `gpd_rollout_tape` launch on the core's params, state, cfg, target and plant rows (None: the nominal airframe): K steps of
+    `actions` (`a_stride` floats apart, 0: one shared block) into `obs [K,N,12]`, `rew`, `term`, `trunc [K,E]` and `tape`"""
+    _native.call("gpd_rollout_tape", core.device, core._stream(), core._params, core._state, core._cfg, K, actions, a_stride, core.target,
+                 obs, core.N * 12, rew, term, trunc, core.E, core.plant_rows, tape)
+
+
+#: `target` / `plant` of `sweep`: the core's own, as it stands now (None is an answer of its own: no target, the nominal airframe)
+OWN = object()
+
+
+def sweep(core, K, actions, a_stride, tape, g_obs, g_rew, g_kin, g_act, target=OWN, plant=OWN, g_rows=None):
+    """one reverse-sweep launch over `tape`: `gpd_rollout_vjp`, or -- with `g_rows [19, ld]` to receive the plant rows' cotangents --
+    `gpd_rollout_vjp_plant`.  `g_obs` / `g_rew`: None = zeros; `g_kin` is read and overwritten, `g_act [K,N,A]` written.  `target`
+    and `plant` default to the core's own; the backward passes the ones its forward flew (None included: a plant installed since
+    must not reach a tape that was recorded without one)."""
+    entry, rows = ("gpd_rollout_vjp", ()) if g_rows is None else ("gpd_rollout_vjp_plant", (g_rows,))
+    _native.call(entry, core.device, core._stream(), core._params, core._cfg, core.ld, K, actions, a_stride,
+                 core.target if target is OWN else target, core.plant_rows if plant is OWN else plant, tape, g_obs, core.N * 12, g_rew,
+                 core.E, g_kin, g_act, *rows)
+
+
+def derive_vjp(core, scales, g_rows, g_scales):
+    """`gpd_plant_derive_vjp`: the plant rows' cotangents `g_rows [19, ld]` at `scales [9, ld]` -> `g_scales [9, ld]` (drones 0 .. N-1)"""
+    _native.call("gpd_plant_derive_vjp", core.device, core._stream(), core._params, scales, g_rows, core.N, core.ld, g_scales)
+
+
 class RolloutDiff(torch.autograd.Function):
     """forward: `gpd_rollout_tape` from `kin0` (copied into the core's state first); backward: `gpd_rollout_vjp`, or -- when
     `plant_scales` (the scales `rollout_diff` has just installed with `set_plant`) asks for a gradient -- `gpd_rollout_vjp_plant`
@@ -70,8 +97,7 @@ class RolloutDiff(torch.autograd.Function):
         trunc = torch.empty((K, E), dtype=torch.bool, device=dev)
         tape = torch.empty((size,), dtype=torch.float32, device=dev)
         core.state_version += 1
-        _native.call("gpd_rollout_tape", dev, core._stream(), core._params, core._state, core._cfg, K, actions, a_stride, core.target,
-                     obs, N * 12, rew, term, trunc, E, core.plant_rows, tape)
+        tape_forward(core, K, actions, a_stride, obs, rew, term, trunc, tape)
         kin_k = core.kin_store.clone()
         core._publish_latest(obs, rew, term, trunc, K)          # (the core's latest-step tensors follow its state, as after rollout())
         ctx.core, ctx.K, ctx.a_stride, ctx.plant = core, K, a_stride, core.plant_rows
@@ -91,21 +117,18 @@ class RolloutDiff(torch.autograd.Function):
     def backward(ctx, g_obs, g_rew, g_kin, _g_term, _g_trunc):
         core, K = ctx.core, ctx.K
         actions, tape = ctx.saved_tensors
-        dev, N, E = core.device, core.N, core.E
+        dev, N = core.device, core.N
         g_obs = None if g_obs is None else g_obs.to(torch.float32).contiguous()
         g_rew = None if g_rew is None else g_rew.to(torch.float32).contiguous()
         g_kin = torch.zeros_like(core.kin_store) if g_kin is None else g_kin.to(torch.float32).clone(memory_format=torch.contiguous_format)
         g_act = torch.empty((K, N, core.A), dtype=torch.float32, device=dev)
+        with_scales = ctx.scales is not None and ctx.needs_input_grad[5]
+        g_rows = torch.empty((_native.PLANT_ROWS, core.ld), dtype=torch.float32, device=dev) if with_scales else None     # (both kernels write drones 0 .. N-1)
+        sweep(core, K, actions, ctx.a_stride, tape, g_obs, g_rew, g_kin, g_act, ctx.target, ctx.plant, g_rows)
         g_scales = None
-        if ctx.scales is None or not ctx.needs_input_grad[5]:
-            _native.call("gpd_rollout_vjp", dev, core._stream(), core._params, core._cfg, core.ld, K, actions, ctx.a_stride, ctx.target,
-                         ctx.plant, tape, g_obs, N * 12, g_rew, E, g_kin, g_act)
-        else:
-            g_rows = torch.empty((_native.PLANT_ROWS, core.ld), dtype=torch.float32, device=dev)     # (both kernels write drones 0 .. N-1)
+        if with_scales:
             g_table = torch.empty((len(_native.SCALE_FIELDS), core.ld), dtype=torch.float32, device=dev)
-            _native.call("gpd_rollout_vjp_plant", dev, core._stream(), core._params, core._cfg, core.ld, K, actions, ctx.a_stride,
-                         ctx.target, ctx.plant, tape, g_obs, N * 12, g_rew, E, g_kin, g_act, g_rows)
-            _native.call("gpd_plant_derive_vjp", dev, core._stream(), core._params, ctx.scales, g_rows, N, core.ld, g_table)
+            derive_vjp(core, ctx.scales, g_rows, g_table)
             g_scales = g_table[:, :N].reshape(ctx.scales_shape)
         if ctx.a_stride == 0:                                  # a shared action block: its gradient is the sum over the steps
             g_act = g_act.sum(dim=0)
@@ -122,24 +145,7 @@ def rollout_diff(core, actions, kin0=None, num_steps: int = None, plant_scales=N
     `plant_scales`: None (the core's plant, or none, as it stands: a constant) or the scale factors in any form `set_plant` accepts.
     They REPLACE the core's plant table (`set_plant(plant_scales.detach())`, with its validation), the forward then is the one above;
     a float tensor `[9, E]` / `[9, E, 1]` that requires grad receives its gradient in its own shape."""
-    per = core.N * core.A
-    if actions.device != core.device or actions.dtype != torch.float32:
-        actions = actions.to(device=core.device, dtype=torch.float32)
-    actions = actions.contiguous()
-    if num_steps is None:
-        if actions.numel() == 0 or actions.numel() % per != 0:
-            raise ValueError(f"actions has {actions.numel()} elements, expected K x {core.N}x{core.A}")
-        K, a_stride = actions.numel() // per, per
-    else:
-        K = int(num_steps)
-        if actions.numel() == per:
-            a_stride = 0
-        elif actions.numel() == K * per:
-            a_stride = per
-        else:
-            raise ValueError(f"actions has {actions.numel()} elements, expected {per} or {K}x{per}")
-    if K < 1:
-        raise ValueError("num_steps must be >= 1")
+    actions, K, a_stride = core._action_blocks(actions, num_steps)
     if kin0 is None:
         kin0 = core.kin_store.detach()
     else:

@@ -374,23 +374,7 @@ class SimCore:
         the next rollout of the same length overwrites -- or, with `last_only=True`, only the last step's
         values in the usual `step()` output tensors.  Bitwise identical to K calls of `step()`.
         """
-        per = self.N * self.A
-        if action_needs_fix(actions, self.device):
-            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
-        if num_steps is None:
-            if actions.numel() % per != 0 or actions.numel() == 0:
-                raise ValueError(f"actions has {actions.numel()} elements, expected K x {self.N}x{self.A}")
-            K, a_stride = actions.numel() // per, per
-        else:
-            K = int(num_steps)
-            if actions.numel() == per:
-                a_stride = 0
-            elif actions.numel() == K * per:
-                a_stride = per
-            else:
-                raise ValueError(f"actions has {actions.numel()} elements, expected {per} or {K}x{per}")
-        if K < 1:
-            raise ValueError("num_steps must be >= 1")
+        actions, K, a_stride = self._action_blocks(actions, num_steps)
         if last_only:
             obs, rew, term, trunc, tobs = self.obs12, self.reward, self.terminated, self.truncated, self.term_obs12
             o_stride = e_stride = 0
@@ -415,6 +399,29 @@ class SimCore:
             if tobs is not None and self.auto_reset:      # term_obs12 = what K single steps would have left
                 self._latest_terminal(tobs, term, trunc, K)
         return obs, rew, term, trunc
+
+    def _action_blocks(self, actions, num_steps):
+        """`(actions, num_steps)` of rollout() / rollout_diff() -> (actions, K, a_stride): K blocks of N x A floats, `a_stride` floats
+        apart (0: one block applied at every step).  A contiguous float32 tensor on the device passes through as it is -- no copy, no
+        dispatch: an eager loop of rollouts has this next to its critical path (`_launch_rollout`)."""
+        per = self.N * self.A
+        if action_needs_fix(actions, self.device):
+            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        if num_steps is None:
+            if actions.numel() % per != 0 or actions.numel() == 0:
+                raise ValueError(f"actions has {actions.numel()} elements, expected K x {self.N}x{self.A}")
+            K, a_stride = actions.numel() // per, per
+        else:
+            K = int(num_steps)
+            if actions.numel() == per:
+                a_stride = 0
+            elif actions.numel() == K * per:
+                a_stride = per
+            else:
+                raise ValueError(f"actions has {actions.numel()} elements, expected {per} or {K}x{per}")
+        if K < 1:
+            raise ValueError("num_steps must be >= 1")
+        return actions, K, a_stride
 
     def rollout_diff(self, actions: torch.Tensor, kin0: torch.Tensor = None, num_steps: int = None, plant_scales=None):
         """`rollout()` that `.backward()` goes through (`diff.rollout_diff`: `gpd_rollout_tape` forward, `gpd_rollout_vjp` backward).

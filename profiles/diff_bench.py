@@ -31,7 +31,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests", "helpers"))
 
 import diff_f64 as ref  # noqa: E402
-from gym_pybullet_drones_amd import _native, engine  # noqa: E402
+from gym_pybullet_drones_amd import _native, diff, engine  # noqa: E402
 from gym_pybullet_drones_amd.diff import tape_floats, unpack_kin  # noqa: E402
 
 N, K, MIN_SECONDS = 65536, 20, 0.25
@@ -65,12 +65,10 @@ def variants(S, dev, with_torch=True):
 
     def rollout_tape():
         core.kin_store.copy_(kin0)
-        _native.call("gpd_rollout_tape", dev, core._stream(), core._params, core._state, core._cfg, K, acts, N * 4, core.target, obs, N * 12,
-                     rew, flags[0], flags[1], N, None, tape)
+        diff.tape_forward(core, K, acts, N * 4, obs, rew, flags[0], flags[1], tape)
 
     def rollout_vjp():
-        _native.call("gpd_rollout_vjp", dev, core._stream(), core._params, core._cfg, core.ld, K, acts, N * 4, core.target, None, tape, g_obs,
-                     N * 12, g_rew, N, g_kin, g_act)
+        diff.sweep(core, K, acts, N * 4, tape, g_obs, g_rew, g_kin, g_act)
 
     cfg = ref.config("cf2x", "rpm", S, False, "hover")
     c = ref.consts(core.P, N, torch.float32, device=dev)
@@ -91,20 +89,18 @@ def variants(S, dev, with_torch=True):
     p_tape = torch.empty_like(tape)
     g_rows = torch.empty((_native.PLANT_ROWS, plant.ld), device=dev)
     g_scales = torch.empty((len(_native.SCALE_FIELDS), plant.ld), device=dev)
-    sweep = (plant._params, plant._cfg, plant.ld, K, acts, N * 4, plant.target, plant.plant_rows, p_tape, g_obs, N * 12, g_rew, N, g_kin, g_act)
 
     def vjp_table():
-        _native.call("gpd_rollout_vjp", dev, plant._stream(), *sweep)
+        diff.sweep(plant, K, acts, N * 4, p_tape, g_obs, g_rew, g_kin, g_act)
 
     def vjp_plant():
-        _native.call("gpd_rollout_vjp_plant", dev, plant._stream(), *sweep, g_rows)
+        diff.sweep(plant, K, acts, N * 4, p_tape, g_obs, g_rew, g_kin, g_act, g_rows=g_rows)
 
     def derive_vjp():
-        _native.call("gpd_plant_derive_vjp", dev, plant._stream(), plant._params, plant.plant_scales, g_rows, N, plant.ld, g_scales)
+        diff.derive_vjp(plant, plant.plant_scales, g_rows, g_scales)
 
     rollout_tape()                                             # (the reverse sweeps read these tapes)
-    _native.call("gpd_rollout_tape", dev, plant._stream(), plant._params, plant._state, plant._cfg, K, acts, N * 4, plant.target, obs, N * 12,
-                 rew, flags[0], flags[1], N, plant.plant_rows, p_tape)
+    diff.tape_forward(plant, K, acts, N * 4, obs, rew, flags[0], flags[1], p_tape)
     jobs = {"rollout": (rollout, 10), "rollout_tape": (rollout_tape, 10), "rollout_vjp": (rollout_vjp, 10), "vjp_table": (vjp_table, 10),
             "vjp_plant": (vjp_plant, 10), "derive_vjp": (derive_vjp, 10)}
     if with_torch:

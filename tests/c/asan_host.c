@@ -7,20 +7,7 @@
  * Device pointers are fake non-null addresses: host code must never dereference them (ASan would say so).  SURVEY.md section 5's
  * "-fsanitize=address host build"; run by tests/test_host_sanitizers.py.  Prints one line per check; exit code = failed checks.
  */
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include "gpd.h"
-
-int hipstub_launches(void);
-void hipstub_last(unsigned out[7]);
-const char* hipstub_last_kernel(void);
-#define KERNEL(piece) (strstr(hipstub_last_kernel(), piece) != NULL)
-
-static int failed;
-#define CHECK(cond, what) do { if (!(cond)) { ++failed; printf("FAIL %s (line %d): %s\n", what, __LINE__, gpd_last_error()); } else printf("ok   %s\n", what); } while (0)
-#define DEV(n) ((void*)(uintptr_t)(0x100000000ull + 0x1000000ull * (n)))      /* fake device addresses */
+#include "host_check.h"
 
 int main(void) {
     int32_t sz[3];

@@ -17,6 +17,8 @@ ACT_DIM = {"rpm": 4, "one_d_rpm": 1, "raw_rpm": 4, "direct_rpm": 4}
 ACT_CODE = {"rpm": 0, "one_d_rpm": 3, "raw_rpm": 5, "direct_rpm": 6}
 GIMBAL = 0.99999
 TURN_N2 = 1e-16
+#: the airframes of `config`, by their member of utils.enums.DroneModel
+MODELS = {"cf2x": "CF2X", "cf2p": "CF2P", "racer": "RACE"}
 #: order of the plant scale factors (include/gpd.h GPD_SCALE_*)
 SCALES = ("mass", "ixx", "iyy", "izz", "kf", "km", "drag_xy", "drag_z", "gnd_eff")
 
@@ -30,15 +32,16 @@ def config(model="cf2x", act="rpm", S=1, drag=False, task="hover", pyb_freq=240)
 def consts(C, n, dtype=torch.float64, device="cpu", scales=None):
     """Per-drone constants [n] from an object with the reference's attribute names (M, L, KF, KM, J, DRAG_COEFF, GRAVITY, HOVER_RPM,
     MAX_RPM: `DroneParams` or the oracle's `UrdfConstants`); `scales` [9, n]: the plant path's scale factors (the action mapping's
-    HOVER_RPM and the MAX_RPM clip stay nominal, include/gpd.h)."""
-    s = np.ones((9, n)) if scales is None else np.asarray(scales, dtype=np.float64)
+    HOVER_RPM and the MAX_RPM clip stay nominal, include/gpd.h), numpy or torch -- a tensor may be an autograd leaf: the products are
+    formed in torch float64, inside the graph, and each is cast to `dtype`."""
+    s = torch.ones((9, n), dtype=torch.float64) if scales is None else torch.as_tensor(scales, dtype=torch.float64)
     J = np.diag(np.asarray(C.J, dtype=np.float64))
     drag = np.asarray(C.DRAG_COEFF, dtype=np.float64)
-    t = lambda v: torch.as_tensor(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)).copy(), dtype=dtype, device=device)   # noqa: E731
+    t = lambda v: (v if isinstance(v, torch.Tensor) else torch.full((n,), float(v), dtype=torch.float64)).to(dtype=dtype, device=device)   # noqa: E731
     return SimpleNamespace(
-        M=t(C.M * s[0]), GRAVITY=t(C.G * C.M * s[0]), L=t(C.L), KF=t(C.KF * s[4]), KM=t(C.KM * s[5]),
-        J=torch.stack([t(J[0] * s[1]), t(J[1] * s[2]), t(J[2] * s[3])], dim=1),
-        DRAG=torch.stack([t(drag[0] * s[6]), t(drag[1] * s[6]), t(drag[2] * s[7])], dim=1),
+        M=t(float(C.M) * s[0]), GRAVITY=t(float(C.G * C.M) * s[0]), L=t(C.L), KF=t(float(C.KF) * s[4]), KM=t(float(C.KM) * s[5]),
+        J=torch.stack([t(float(J[0]) * s[1]), t(float(J[1]) * s[2]), t(float(J[2]) * s[3])], dim=1),
+        DRAG=torch.stack([t(float(drag[0]) * s[6]), t(float(drag[1]) * s[6]), t(float(drag[2]) * s[7])], dim=1),
         HOVER_RPM=t(C.HOVER_RPM), MAX_RPM=t(C.MAX_RPM))
 
 
@@ -198,21 +201,27 @@ def make_inputs(C, cfg, n, K, seed=0, at_rest=False, outside_clip=True):
 GROUPS = ("actions", "pos", "quat", "vel", "rates")
 
 
-def reference_grads(C, cfg, inp, dtype=torch.float64, scales=None, shared_action=False, stats=None, g_obs=True):
+def reference_grads(C, cfg, inp, dtype=torch.float64, scales=None, shared_action=False, stats=None, g_obs=True, wrt_scales=False):
     """Gradients of sum(cotangent * output) over every output with respect to the actions and the four groups of the initial state,
-    by torch autograd over the restatement: dict of numpy float64 arrays (GROUPS).  `shared_action`: actions[0] at every step."""
-    c = consts(C, inp.n, dtype, scales=scales)
+    by torch autograd over the restatement: dict of numpy float64 arrays (GROUPS).  `shared_action`: actions[0] at every step.
+    `wrt_scales`: the scales are a leaf too, and "scales" [9, n] (rows in SCALES order) their gradient; a scale the configuration
+    does not read gets zeros."""
     T = lambda v: torch.as_tensor(v, dtype=dtype)     # noqa: E731
     leaf = lambda v: T(v).clone().requires_grad_(True)     # noqa: E731
     kin0 = tuple(leaf(v) for v in (inp.pos, inp.quat, inp.vel, inp.rates))
     a = leaf(inp.actions[0:1] if shared_action else inp.actions)
+    leaves, names = (a,) + kin0, GROUPS
+    if wrt_scales:
+        scales = torch.as_tensor(scales, dtype=torch.float64).clone().requires_grad_(True)
+        leaves, names = leaves + (scales,), GROUPS + ("scales",)
+    c = consts(C, inp.n, dtype, scales=scales)
     acts = a.expand(inp.K, -1, -1) if shared_action else a
     obs, rew, kin_k = rollout(c, cfg, kin0, acts, T(inp.first_sum), T(inp.target), stats)
     loss = (T(inp.g_rew) * rew).sum() + sum((T(g) * k).sum() for g, k in zip((inp.g_pos, inp.g_quat, inp.g_vel, inp.g_rates), kin_k))
     if g_obs:
         loss = loss + (T(inp.g_obs) * obs).sum()
-    grads = torch.autograd.grad(loss, (a,) + kin0, allow_unused=True)
-    out = {k: (torch.zeros_like(x) if g is None else g).detach().to(torch.float64).numpy() for k, g, x in zip(GROUPS, grads, (a,) + kin0)}
+    grads = torch.autograd.grad(loss, leaves, allow_unused=True)
+    out = {k: (torch.zeros_like(x) if g is None else g).detach().to(torch.float64).numpy() for k, g, x in zip(names, grads, leaves)}
     out["forward"] = (obs.detach(), rew.detach(), tuple(k.detach() for k in kin_k))
     return out
 

@@ -1,12 +1,9 @@
-"""The yardstick of the gradients with respect to the plant scales (tests/test_host_sysid.py, tests/test_gpu_sysid.py): the torch
-restatement of tests/helpers/diff_f64.py with its per-drone constants restated as functions of the `[9, n]` scale factors (include/gpd.h
-GPD_SCALE_*), the scales being autograd leaves.  Run in float64 it is the reference `gpd_rollout_vjp_plant` + `gpd_plant_derive_vjp`
-are held against; the same file holds the numpy float64 statement of `gpd_plant_derive` and of the transpose of its Jacobian.
+"""What the tests of the gradients with respect to the plant scales (tests/test_host_sysid.py, tests/test_gpu_sysid.py) add to the
+yardstick of tests/helpers/diff_f64.py, whose `reference_grads(..., wrt_scales=True)` takes the `[9, n]` scale factors (include/gpd.h
+GPD_SCALE_*) as an autograd leaf -- run in float64 it is the reference `gpd_rollout_vjp_plant` + `gpd_plant_derive_vjp` are held
+against: the cases, the metric, and the numpy float64 statement of `gpd_plant_derive` and of the transpose of its Jacobian.
 Test infrastructure."""
-from types import SimpleNamespace
-
 import numpy as np
-import torch
 
 import diff_f64 as ref
 
@@ -29,33 +26,6 @@ def case(name, n=70, seed=1, ones=False):
     K = d.pop("K")
     scales = np.asarray(np.random.default_rng(seed + 100).uniform(0.8, 1.2, (9, n)), dtype=np.float32).astype(np.float64)
     return ref.config(**d), K, np.ones((9, n)) if ones else scales
-
-
-def consts(C, n, s, dtype=torch.float64):
-    """diff_f64.consts with `s` a torch tensor [9, n] (a leaf): the same products, inside the graph"""
-    J = np.diag(np.asarray(C.J, dtype=np.float64))
-    drag = np.asarray(C.DRAG_COEFF, dtype=np.float64)
-    t = lambda v: torch.full((n,), float(v), dtype=dtype)     # noqa: E731
-    return SimpleNamespace(
-        M=float(C.M) * s[0], GRAVITY=float(C.G * C.M) * s[0], L=t(C.L), KF=float(C.KF) * s[4], KM=float(C.KM) * s[5],
-        J=torch.stack([float(J[0]) * s[1], float(J[1]) * s[2], float(J[2]) * s[3]], dim=1),
-        DRAG=torch.stack([float(drag[0]) * s[6], float(drag[1]) * s[6], float(drag[2]) * s[7]], dim=1),
-        HOVER_RPM=t(C.HOVER_RPM), MAX_RPM=t(C.MAX_RPM))
-
-
-def scale_grads(C, cfg, inp, scales, dtype=torch.float64, g_obs=True):
-    """Gradient of sum(cotangent * output) over every output (diff_f64.reference_grads's loss) with respect to the scales:
-    numpy float64 [9, n], rows in SCALES order; a scale the configuration does not read gets zeros."""
-    T = lambda v: torch.as_tensor(v, dtype=dtype)     # noqa: E731
-    s = T(scales).clone().requires_grad_(True)
-    c = consts(C, inp.n, s, dtype)
-    kin0 = tuple(T(v) for v in (inp.pos, inp.quat, inp.vel, inp.rates))
-    obs, rew, kin_k = ref.rollout(c, cfg, kin0, T(inp.actions), T(inp.first_sum), T(inp.target))
-    loss = (T(inp.g_rew) * rew).sum() + sum((T(g) * k).sum() for g, k in zip((inp.g_pos, inp.g_quat, inp.g_vel, inp.g_rates), kin_k))
-    if g_obs:
-        loss = loss + (T(inp.g_obs) * obs).sum()
-    (g,) = torch.autograd.grad(loss, (s,), allow_unused=True)
-    return (torch.zeros_like(s) if g is None else g).detach().to(torch.float64).numpy()
 
 
 def scale_errors(got, want):

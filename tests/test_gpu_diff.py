@@ -15,39 +15,14 @@ from conftest import REPO
 
 sys.path.insert(0, os.path.join(REPO, "tests", "helpers"))
 import diff_f64 as ref  # noqa: E402
+from diff_gpu import N, core as _core, loss as _loss, set_state as _set, swept, taped  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-N = 70
-MODELS = {"cf2x": "CF2X", "cf2p": "CF2P", "racer": "RACE"}
-
-
-def _core(cfg, dev, n=N, task="hover", nan_guard=False):
-    from gym_pybullet_drones_amd import engine
-    from gym_pybullet_drones_amd.utils.enums import DroneModel
-    return engine.SimCore(drone_model=getattr(DroneModel, MODELS[cfg.model]), num_envs=n, drones_per_env=1, physics=2 if cfg.drag else 0,
-                          pyb_freq=240, ctrl_freq=240 // cfg.S, act_code=ref.ACT_CODE[cfg.act],
-                          task=engine.TASK_HOVER if task == "hover" else engine.TASK_NONE, target_pos=[[0.0, 0.0, 1.0]], auto_reset=False,
-                          track_rpm=True, nan_guard=nan_guard, device=dev)
-
-
-def _set(core, inp):
-    """the inputs' state into the core (the logical [13, n] rows; the RPMs the first drag term sees)"""
-    kin = np.concatenate([inp.pos, inp.quat, inp.vel, inp.rates], axis=1).T
-    core.set_state(kin=torch.as_tensor(kin, dtype=torch.float32), last_rpm=torch.as_tensor(inp.last_rpm.T, dtype=torch.float32),
-                   step_counter=torch.zeros(core.E, dtype=torch.int32))
 
 
 def _leaves(inp, dev):
     f = lambda v: torch.as_tensor(v, dtype=torch.float32, device=dev).requires_grad_(True)     # noqa: E731
     return [f(inp.pos), f(inp.quat), f(inp.vel), f(inp.rates)]
-
-
-def _loss(inp, dev, obs, rew, kin_k, n, with_obs=True):
-    from gym_pybullet_drones_amd.diff import unpack_kin
-    T = lambda v: torch.as_tensor(v, dtype=torch.float32, device=dev)     # noqa: E731
-    loss = (T(inp.g_rew) * rew).sum() + sum((T(g) * k).sum() for g, k in zip((inp.g_pos, inp.g_quat, inp.g_vel, inp.g_rates), unpack_kin(kin_k, n)))
-    return loss + (T(inp.g_obs) * obs).sum() if with_obs else loss
 
 
 def device_grads(core, inp, dev, shared_action=False, with_obs=True):
@@ -188,26 +163,14 @@ def test_at_rest_gradients_are_finite_and_match(gpu_device):
 
 # ---- 6. / 7. NULL cotangents, determinism ------------------------------------------------------------------------------------------
 def test_null_obs_cotangent_is_a_zero_tensor_and_two_sweeps_give_the_same_bits(gpu_device):
-    from gym_pybullet_drones_amd import _native
-    from gym_pybullet_drones_amd.diff import tape_floats
     cfg = ref.config("cf2x", "rpm", 8, True, "hover")
     core = _core(cfg, gpu_device)
     K = 5
     inp = ref.make_inputs(core.P, cfg, N, K, seed=8)
-    _set(core, inp)
     T = lambda v: torch.as_tensor(v, dtype=torch.float32, device=gpu_device).contiguous()     # noqa: E731
-    acts, tape = T(inp.actions), torch.empty(tape_floats(core, K), dtype=torch.float32, device=gpu_device)
-    obs, rew = torch.empty((K, N, 12), device=gpu_device), torch.empty((K, N), device=gpu_device)
-    flags = torch.empty((2, K, N), dtype=torch.bool, device=gpu_device)
-    _native.call("gpd_rollout_tape", gpu_device, core._stream(), core._params, core._state, core._cfg, K, acts, N * 4, core.target, obs,
-                 N * 12, rew, flags[0], flags[1], N, None, tape)
+    acts, tape = taped(core, inp, K)
     g_kin0 = torch.randn(13 * core.ld, device=gpu_device)
-
-    def sweep(g_obs, g_rew):
-        g_kin, g_act = g_kin0.clone(), torch.full((K, N, 4), float("nan"), device=gpu_device)
-        _native.call("gpd_rollout_vjp", gpu_device, core._stream(), core._params, core._cfg, core.ld, K, acts, N * 4, core.target, None, tape,
-                     g_obs, N * 12, g_rew, N, g_kin, g_act)
-        return g_kin, g_act
+    sweep = lambda g_obs, g_rew: swept(core, K, acts, tape, g_obs, g_rew, g_kin0)[:2]     # noqa: E731
 
     g_rew = T(inp.g_rew)
     null, zero = sweep(None, g_rew), sweep(torch.zeros((K, N, 12), device=gpu_device), g_rew)

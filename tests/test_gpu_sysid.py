@@ -1,6 +1,6 @@
 """Gradients with respect to the plant scales on the device (include/gpd.h `gpd_rollout_vjp_plant` / `gpd_plant_derive_vjp`,
 `rollout_diff(..., plant_scales=)` of gym_pybullet_drones_amd/diff.py): against float64 autograd over the restatement of
-tests/helpers/sysid_f64.py (which tests/test_host_sysid.py holds against finite differences), the sweep's other outputs bit for bit
+tests/helpers/diff_f64.py with the scales as leaves (which tests/test_host_sysid.py holds against finite differences), the sweep's other outputs bit for bit
 those of `gpd_rollout_vjp`, determinism, the scaling identity, the unchanged forward, chaining, the input's shapes, the refusal, and
 what the gradients are for: recovering hidden airframes from their recorded flight.  N = 70 drones (ld = 128: two waves, one ragged)
 unless stated otherwise."""
@@ -17,36 +17,9 @@ from conftest import REPO
 sys.path.insert(0, os.path.join(REPO, "tests", "helpers"))
 import diff_f64 as ref  # noqa: E402
 import sysid_f64 as sid  # noqa: E402
+from diff_gpu import N, core as _core, loss as _loss, set_state as _set, swept, taped  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-N = 70
-MODELS = {"cf2x": "CF2X", "cf2p": "CF2P", "racer": "RACE"}
-
-
-def _core(cfg, dev, n=N, task="hover"):
-    from gym_pybullet_drones_amd import engine
-    from gym_pybullet_drones_amd.utils.enums import DroneModel
-    return engine.SimCore(drone_model=getattr(DroneModel, MODELS[cfg.model]), num_envs=n, drones_per_env=1, physics=2 if cfg.drag else 0,
-                          pyb_freq=240, ctrl_freq=240 // cfg.S, act_code=ref.ACT_CODE[cfg.act],
-                          task=engine.TASK_HOVER if task == "hover" else engine.TASK_NONE, target_pos=[[0.0, 0.0, 1.0]], auto_reset=False,
-                          track_rpm=True, device=dev)
-
-
-def _set(core, inp):
-    """the inputs' state into the core (the logical [13, n] rows; the RPMs the first drag term sees)"""
-    kin = np.concatenate([inp.pos, inp.quat, inp.vel, inp.rates], axis=1).T
-    core.set_state(kin=torch.as_tensor(kin, dtype=torch.float32), last_rpm=torch.as_tensor(inp.last_rpm.T, dtype=torch.float32),
-                   step_counter=torch.zeros(core.E, dtype=torch.int32))
-
-
-def _loss(inp, dev, obs, rew, kin_k, n):
-    from gym_pybullet_drones_amd.diff import unpack_kin
-    T = lambda v: torch.as_tensor(v, dtype=torch.float32, device=dev)     # noqa: E731
-    loss = (T(inp.g_rew) * rew).sum() + (T(inp.g_obs) * obs).sum()
-    if kin_k is not None:
-        loss = loss + sum((T(g) * k).sum() for g, k in zip((inp.g_pos, inp.g_quat, inp.g_vel, inp.g_rates), unpack_kin(kin_k, n)))
-    return loss
 
 
 def device_scale_grads(core, inp, scales, dev, flat=False):
@@ -69,7 +42,7 @@ def runs(gpu_device):
         cfg, K, scales = sid.case(name, ones=ones)
         core = _core(cfg, gpu_device)
         inp = ref.make_inputs(core.P, cfg, N, K, seed=1)
-        g64 = sid.scale_grads(core.P, cfg, inp, scales, torch.float64)
+        g64 = ref.reference_grads(core.P, cfg, inp, torch.float64, scales, wrt_scales=True)["scales"]
         got = device_scale_grads(core, inp, scales, gpu_device).view(9, N).cpu().numpy().astype(np.float64)
         out[name, ones] = (cfg, scales, g64, got)
     return out
@@ -99,31 +72,15 @@ def test_sweep_writes_the_bits_of_gpd_rollout_vjp_and_two_sweeps_agree(gpu_devic
     """g_kin and g_actions of gpd_rollout_vjp_plant are bit for bit those of gpd_rollout_vjp on the same tape; two sweeps give the same
     bits, the rows' cotangents included; rows M, GND_EFF and HOVER_THRUST are exactly 0 and nothing past drone N - 1 is written"""
     from gym_pybullet_drones_amd import _native
-    from gym_pybullet_drones_amd.diff import tape_floats
     cfg, K, scales = sid.case(name)
     core = _core(cfg, gpu_device)
     core.set_plant(torch.as_tensor(scales, dtype=torch.float32, device=gpu_device).view(9, N, 1))
     inp = ref.make_inputs(core.P, cfg, N, K, seed=1)
-    _set(core, inp)
     T = lambda v: torch.as_tensor(v, dtype=torch.float32, device=gpu_device).contiguous()     # noqa: E731
-    A = inp.A
-    acts, tape = T(inp.actions), torch.empty(tape_floats(core, K), dtype=torch.float32, device=gpu_device)
-    obs, rew = torch.empty((K, N, 12), device=gpu_device), torch.empty((K, N), device=gpu_device)
-    flags = torch.empty((2, K, N), dtype=torch.bool, device=gpu_device)
-    _native.call("gpd_rollout_tape", gpu_device, core._stream(), core._params, core._state, core._cfg, K, acts, N * A, core.target, obs,
-                 N * 12, rew, flags[0], flags[1], N, core.plant_rows, tape)
+    acts, tape = taped(core, inp, K)
     g_kin0 = torch.randn(13 * core.ld, device=gpu_device)
     g_obs, g_rew = T(inp.g_obs), T(inp.g_rew)
-
-    def sweep(with_rows):
-        g_kin, g_act = g_kin0.clone(), torch.full((K, N, A), float("nan"), device=gpu_device)
-        g_rows = torch.full((_native.PLANT_ROWS, core.ld), 7.0, device=gpu_device)
-        args = (core._params, core._cfg, core.ld, K, acts, N * A, core.target, core.plant_rows, tape, g_obs, N * 12, g_rew, N, g_kin, g_act)
-        if with_rows:
-            _native.call("gpd_rollout_vjp_plant", gpu_device, core._stream(), *args, g_rows)
-        else:
-            _native.call("gpd_rollout_vjp", gpu_device, core._stream(), *args)
-        return g_kin, g_act, g_rows
+    sweep = lambda with_rows: swept(core, K, acts, tape, g_obs, g_rew, g_kin0, with_rows)     # noqa: E731
 
     plain, first, second = sweep(False), sweep(True), sweep(True)
     assert torch.equal(plain[0], first[0]) and torch.equal(plain[1], first[1]) and bool(torch.isfinite(first[1]).all())

@@ -4,8 +4,6 @@ host side of the three new entries (include/gpd.h `gpd_rollout_tape_floats` / `g
 every rejected configuration with its code and message, and tests/c/diff_host.c under AddressSanitizer + UBSan against the launch stub."""
 import ctypes
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -16,12 +14,8 @@ from conftest import REPO, urdf
 
 sys.path.insert(0, os.path.join(REPO, "tests", "helpers"))
 import diff_f64 as ref  # noqa: E402
-
-
-def _params(model):
-    from gym_pybullet_drones_amd.params import DroneParams
-    from gym_pybullet_drones_amd.utils.enums import DroneModel
-    return DroneParams({"cf2x": DroneModel.CF2X, "cf2p": DroneModel.CF2P, "racer": DroneModel.RACE}[model])
+import host_lib  # noqa: E402
+from host_lib import REJECTED, params as _params, step_cfg as _cfg  # noqa: E402
 
 
 @pytest.mark.parametrize("model", ["cf2x", "cf2p", "racer"])
@@ -138,15 +132,6 @@ def test_pack_and_unpack_kin_are_inverse_and_differentiable():
 
 
 # ---- the host side of the entries -------------------------------------------------------------------------------------------------
-def _cfg(**kw):
-    from gym_pybullet_drones_amd import _native
-    d = dict(num_envs=70, drones_per_env=1, act_type=0, substeps=8, physics_flags=0, pyb_dt=1 / 240, ctrl_dt=1 / 30, inv_ctrl_dt=30.0,
-             lanes_per_wave=64, task=1, xy_bound=1.5, z_bound=2.0, tilt_bound=0.4, term_dist=1e-4, trunc_counter=1920, target_per_env=0,
-             init_per_env=0, auto_reset=0)
-    d.update(kw)
-    return _native.GpdStepCfg(**d)
-
-
 def test_size_query_gives_thirteen_rows_per_step_and_one():
     from gym_pybullet_drones_amd import _native
     L = _native.lib()
@@ -157,12 +142,6 @@ def test_size_query_gives_thirteen_rows_per_step_and_one():
         assert out.value == (13 * K + 1) * ld
     assert L.gpd_rollout_tape_floats(ctypes.byref(_cfg()), 1, 64, ctypes.byref(out)) == _native.GPD_EINVAL        # ld < 70 drones
     assert L.gpd_rollout_tape_floats(ctypes.byref(_cfg()), 2 ** 31 - 1, 2 ** 32 - 1, ctypes.byref(out)) == _native.GPD_ERANGE
-
-
-REJECTED = [(dict(act_type=1), "DSLPID"), (dict(act_type=2), "DSLPID"), (dict(act_type=4), "DSLPID"),
-            (dict(physics_flags=1), "physics_flags"), (dict(physics_flags=4), "physics_flags"), (dict(physics_flags=8), "physics_flags"),
-            (dict(physics_flags=16), "physics_flags"), (dict(physics_flags=3), "physics_flags"),
-            (dict(drones_per_env=2, num_envs=35), "drones_per_env"), (dict(task=2), "task"), (dict(auto_reset=1), "auto_reset")]
 
 
 @pytest.mark.parametrize("change,reason", REJECTED)
@@ -224,40 +203,13 @@ def test_new_entries_are_bound_and_the_abi_version_stays():
     assert len(_native.UNITS) == 5 and "diff_kernels.inc" in _native.HEADERS
 
 
-def test_host_side_of_the_diff_entries_under_asan_and_ubsan(tmp_path):
-    """tests/c/diff_host.c linked to the host-only build of the five units and the launch stub under -fsanitize=address,undefined (built
-    the way tests/test_host_sanitizers.py builds its own): accepted and rejected arguments, and the kernel each accepted call launches"""
-    from gym_pybullet_drones_amd import _native
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    clang = "/opt/rocm/lib/llvm/bin/clang"
-    if not (os.path.exists(hipcc) and os.path.exists(clang)):
-        pytest.skip("no hipcc / clang")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1"]
-    objs, procs = [], []
-    for unit, _ in _native.UNITS:
-        obj = str(tmp_path / unit.replace(".hip", ".host.o"))
-        cmd = [hipcc, "-std=c++17", "--offload-arch=gfx950", "--cuda-host-only", "-fPIC"] + san + ["-I", _native.INCLUDE, "-c", os.path.join(_native.CSRC, unit), "-o", obj]
-        procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-        objs.append(obj)
-    for pr in procs:
-        out, _ = pr.communicate()
-        assert pr.returncode == 0, out[-3000:]
-    undefined = subprocess.run(["nm", "-u"] + objs, capture_output=True, text=True, check=True).stdout
-    fatbins = sorted(set(re.findall(r"__hip_fatbin_\w+", undefined)))
-    stub_c = str(tmp_path / "fatbin_stubs.c")
-    open(stub_c, "w").write("".join(f"const char {s}[16] = {{0}};\n" for s in fatbins))
-    lib = str(tmp_path / "libgpd_asan.so")
-    link = [clang + "++", "-shared", "-fPIC"] + san + objs + ["-x", "c", stub_c, os.path.join(REPO, "tests", "stubs", "hip_stub.c"), "-o", lib, "-ldl"]
-    res = subprocess.run(link, capture_output=True, text=True)
-    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
-    exe = str(tmp_path / "diff_host")
-    res = subprocess.run([clang] + san + ["-std=c11", "-I", _native.INCLUDE, os.path.join(REPO, "tests", "c", "diff_host.c"), lib, f"-Wl,-rpath,{tmp_path}", "-o", exe],
-                         capture_output=True, text=True)
-    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+def test_host_side_of_the_diff_entries_under_asan_and_ubsan():
+    """tests/c/diff_host.c linked to the host-only build of the five units and the launch stub under -fsanitize=address,undefined
+    (tests/helpers/host_lib.py; one run, shared with tests/test_host_sysid.py): accepted and rejected arguments, and the kernel each
+    accepted call launches"""
+    run, _ = host_lib.diff_host()
     print(run.stdout[-4000:])
     assert "AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-4000:]
     assert run.returncode == 0 and "\n0 checks failed" in run.stdout, run.stdout[-3000:] + run.stderr[-2000:]
-    assert run.stdout.count("\nok ") + run.stdout.startswith("ok ") >= 60
+    assert run.stdout.count("\nok ") + run.stdout.startswith("ok ") >= 60 + 50          # (this module's entries + the plant-gradient ones)
     assert "gpd_rollout_tape_kernel" in run.stdout and "gpd_rollout_vjp_kernel" in run.stdout          # (the kernels are named)

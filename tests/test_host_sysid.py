@@ -1,9 +1,9 @@
-"""Gradients with respect to the plant scales without a GPU: the float64 yardstick (tests/helpers/sysid_f64.py: the restatement of
-tests/helpers/diff_f64.py with the scales as autograd leaves) against finite differences, its float32 run against its float64 run on
-the GPU tests' inputs, the scaling identity, and the host side of the two entries (include/gpd.h `gpd_rollout_vjp_plant` /
-`gpd_plant_derive_vjp`): every refusal with its code and message, tests/c/sysid_host.c under AddressSanitizer + UBSan against the launch
-stub, the formulas of csrc/plant_derive_vjp.inc against a numerical Jacobian, and the compiler's word that no kernel of the sweep
-needs scratch memory."""
+"""Gradients with respect to the plant scales without a GPU: the float64 yardstick (tests/helpers/diff_f64.py with the scales as
+autograd leaves: `consts(scales=)`, `reference_grads(wrt_scales=True)`) against finite differences, its float32 run against its
+float64 run on the GPU tests' inputs, the scaling identity, and the host side of the two entries (include/gpd.h
+`gpd_rollout_vjp_plant` / `gpd_plant_derive_vjp`): every refusal with its code and message, tests/c/diff_host.c under AddressSanitizer
++ UBSan against the launch stub, the formulas of csrc/plant_derive_vjp.inc against a numerical Jacobian, and the compiler's word that
+no kernel of the sweep needs scratch memory."""
 import ctypes
 import os
 import re
@@ -19,13 +19,9 @@ from conftest import REPO
 
 sys.path.insert(0, os.path.join(REPO, "tests", "helpers"))
 import diff_f64 as ref  # noqa: E402
+import host_lib  # noqa: E402
+from host_lib import REJECTED, params as _params, step_cfg as _cfg  # noqa: E402
 import sysid_f64 as sid  # noqa: E402
-
-
-def _params(model):
-    from gym_pybullet_drones_amd.params import DroneParams
-    from gym_pybullet_drones_amd.utils.enums import DroneModel
-    return DroneParams({"cf2x": DroneModel.CF2X, "cf2p": DroneModel.CF2P, "racer": DroneModel.RACE}[model])
 
 
 # ---- the yardstick -----------------------------------------------------------------------------------------------------------------
@@ -39,7 +35,7 @@ def test_restatement_scale_gradients_pass_gradcheck(model, act, drag, S):
     kin0 = tuple(T(v) for v in (inp.pos, inp.quat, inp.vel, inp.rates))
 
     def f(s):
-        obs, rew, kin = ref.rollout(sid.consts(C, 2, s), cfg, kin0, T(inp.actions), T(inp.first_sum), T(inp.target))
+        obs, rew, kin = ref.rollout(ref.consts(C, 2, scales=s), cfg, kin0, T(inp.actions), T(inp.first_sum), T(inp.target))
         return torch.cat([obs.reshape(-1), rew.reshape(-1)] + [k.reshape(-1) for k in kin])
 
     s = T(np.random.default_rng(7).uniform(0.8, 1.2, (9, 2))).requires_grad_(True)
@@ -54,7 +50,8 @@ def runs():
         cfg, K, scales = sid.case(name, ones=ones)
         C = _params(cfg.model)
         inp = ref.make_inputs(C, cfg, 70, K, seed=1)
-        out[name, ones] = (cfg, scales, sid.scale_grads(C, cfg, inp, scales, torch.float64), sid.scale_grads(C, cfg, inp, scales, torch.float32))
+        g64, g32 = (ref.reference_grads(C, cfg, inp, dtype, scales, wrt_scales=True)["scales"] for dtype in (torch.float64, torch.float32))
+        out[name, ones] = (cfg, scales, g64, g32)
     return out
 
 
@@ -85,15 +82,6 @@ def test_scaling_identity_holds_in_float64(runs, name, ones):
 
 
 # ---- the host side of the entries -------------------------------------------------------------------------------------------------
-def _cfg(**kw):
-    from gym_pybullet_drones_amd import _native
-    d = dict(num_envs=70, drones_per_env=1, act_type=0, substeps=8, physics_flags=0, pyb_dt=1 / 240, ctrl_dt=1 / 30, inv_ctrl_dt=30.0,
-             lanes_per_wave=64, task=1, xy_bound=1.5, z_bound=2.0, tilt_bound=0.4, term_dist=1e-4, trunc_counter=1920, target_per_env=0,
-             init_per_env=0, auto_reset=0)
-    d.update(kw)
-    return _native.GpdStepCfg(**d)
-
-
 def test_new_entries_are_bound_and_the_abi_version_stays():
     from gym_pybullet_drones_amd import _native
     assert _native.ABI_VERSION == 9 and _native.lib().gpd_abi_version() == 9
@@ -101,17 +89,11 @@ def test_new_entries_are_bound_and_the_abi_version_stays():
     assert "plant_derive_vjp.inc" in _native.HEADERS
 
 
-REJECTED = [(dict(act_type=1), "DSLPID"), (dict(act_type=2), "DSLPID"), (dict(act_type=4), "DSLPID"),
-            (dict(physics_flags=1), "physics_flags"), (dict(physics_flags=4), "physics_flags"), (dict(physics_flags=8), "physics_flags"),
-            (dict(physics_flags=16), "physics_flags"), (dict(physics_flags=3), "physics_flags"),
-            (dict(drones_per_env=2, num_envs=35), "drones_per_env"), (dict(task=2), "task"), (dict(auto_reset=1), "auto_reset")]
-
-
 def test_every_refusal_returns_its_code_and_an_entry_named_message():
     """gpd_rollout_vjp_plant: gpd_rollout_vjp's refusals (GPD_ENOTSUP for what diff_cfg refuses, GPD_EINVAL for bad arguments) and its
     own (no plant table, no / a misaligned g_plant_rows); gpd_plant_derive_vjp: NULL pointers, n, ld.  The pointers are fake addresses
     of host memory: a call that got as far as a launch would not return a negative code on a machine without a device
-    (tests/c/sysid_host.c counts the launches against the stub: none)."""
+    (tests/c/diff_host.c counts the launches against the stub: none)."""
     from gym_pybullet_drones_amd import _native
     from gym_pybullet_drones_amd.utils.enums import DroneModel
     L = _native.lib()
@@ -150,41 +132,10 @@ def test_every_refusal_returns_its_code_and_an_entry_named_message():
 
 
 @pytest.fixture(scope="module")
-def host_program(tmp_path_factory):
-    """tests/c/sysid_host.c linked to the host-only build of the five units and the launch stub under -fsanitize=address,undefined,
-    built the way tests/test_host_diff.py builds tests/c/diff_host.c, and run once: (the finished process, the file of formula values)"""
-    from gym_pybullet_drones_amd import _native
-    tmp_path = tmp_path_factory.mktemp("sysid_host")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    clang = "/opt/rocm/lib/llvm/bin/clang"
-    if not (os.path.exists(hipcc) and os.path.exists(clang)):
-        pytest.skip("no hipcc / clang")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1"]
-    objs, procs = [], []
-    for unit, _ in _native.UNITS:
-        obj = str(tmp_path / unit.replace(".hip", ".host.o"))
-        cmd = [hipcc, "-std=c++17", "--offload-arch=gfx950", "--cuda-host-only", "-fPIC"] + san + ["-I", _native.INCLUDE, "-c", os.path.join(_native.CSRC, unit), "-o", obj]
-        procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-        objs.append(obj)
-    for pr in procs:
-        out, _ = pr.communicate()
-        assert pr.returncode == 0, out[-3000:]
-    undefined = subprocess.run(["nm", "-u"] + objs, capture_output=True, text=True, check=True).stdout
-    fatbins = sorted(set(re.findall(r"__hip_fatbin_\w+", undefined)))
-    stub_c = str(tmp_path / "fatbin_stubs.c")
-    open(stub_c, "w").write("".join(f"const char {s}[16] = {{0}};\n" for s in fatbins))
-    lib = str(tmp_path / "libgpd_asan.so")
-    link = [clang + "++", "-shared", "-fPIC"] + san + objs + ["-x", "c", stub_c, os.path.join(REPO, "tests", "stubs", "hip_stub.c"), "-o", lib, "-ldl"]
-    res = subprocess.run(link, capture_output=True, text=True)
-    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
-    exe = str(tmp_path / "sysid_host")
-    res = subprocess.run([clang] + san + ["-std=c11", "-I", _native.INCLUDE, "-I", _native.CSRC, os.path.join(REPO, "tests", "c", "sysid_host.c"), lib,
-                          f"-Wl,-rpath,{tmp_path}", "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    values = str(tmp_path / "formulas.txt")
-    run = subprocess.run([exe, values], capture_output=True, text=True, env=env, timeout=120)
-    return run, values
+def host_program():
+    """tests/c/diff_host.c linked to the host-only build of the five units and the launch stub under -fsanitize=address,undefined and
+    run once (tests/helpers/host_lib.py; shared with tests/test_host_diff.py): (the finished process, the file of formula values)"""
+    return host_lib.diff_host()
 
 
 def test_host_side_of_the_plant_gradient_entries_under_asan_and_ubsan(host_program):
@@ -193,7 +144,7 @@ def test_host_side_of_the_plant_gradient_entries_under_asan_and_ubsan(host_progr
     print(run.stdout[-6000:])
     assert "AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-4000:]
     assert run.returncode == 0 and "\n0 checks failed" in run.stdout, run.stdout[-3000:] + run.stderr[-2000:]
-    assert run.stdout.count("\nok ") + run.stdout.startswith("ok ") >= 50
+    assert run.stdout.count("\nok ") + run.stdout.startswith("ok ") >= 50 + 60          # (this module's entries + the three they extend)
     for inst in ("<EXT 0, AW 4, PLANT 1, GP 1>", "<EXT 0, AW 1, PLANT 1, GP 1>", "<EXT 1, AW 1, PLANT 1, GP 1>", "<EXT 1, AW 4, PLANT 1, GP 1>"):
         assert any(line.startswith("ok ") and inst in line for line in run.stdout.split("\n")), inst
     assert "ok   gpd_plant_derive_vjp launches its kernel once" in run.stdout
