@@ -30,7 +30,7 @@ ABI_VERSION = 9
 #                     slots of a rollout step)
 #   policy.hip        gpd_rollout_policy                 the default scheduler: 10 % faster on its MFMA + activation mix (round-2 A/B)
 #   swarm.hip         the one-world kernels              max-ilp, as in rounds 2-4
-#   abi.hip           small kernels, RCCL, library-level entries
+#   abi.hip           small kernels, RCCL, library-level entries; the differentiable rollout and gpd_obstacles (csrc/*.inc pulled in at its end)
 #   mrac.hip          gpd_mrac / gpd_mrac_reset / gpd_rollout_mrac: the adaptive controller and the rollout that carries it (max-ilp)
 #   -mllvm -amdgpu-kernarg-preload-count=14: the first 14 argument dwords of a kernel arrive in SGPRs with the wave (gfx942+ command
 #   processor) instead of through a scalar load -- gpd_step_kernel's argument list starts with what its load section needs
@@ -39,7 +39,7 @@ MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 HIPCC_FLAGS = COMMON_FLAGS + MAX_ILP + ["-shared"]        # (kept under this name for the ISA tests)
 UNITS = (("step_rollout.hip", MAX_ILP + KERNARG_PRELOAD), ("policy.hip", []), ("swarm.hip", MAX_ILP + KERNARG_PRELOAD), ("abi.hip", MAX_ILP), ("mrac.hip", MAX_ILP))
-HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc")
+HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc", "obstacle_math.inc", "obstacles.inc")
 
 
 class GpdError(RuntimeError):
@@ -174,6 +174,8 @@ _SIGNATURES = {
     "gpd_neighbors": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _P]),
+    "gpd_obstacles": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, _P, _P, _P,
+                                     _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _P, _P, _P]),
     "gpd_reset": (ctypes.c_int, [ctypes.POINTER(GpdState), _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32,
                                  ctypes.c_int32, _P, _P]),
     "gpd_pid": (ctypes.c_int, [ctypes.POINTER(GpdParams), _P, ctypes.c_int64, ctypes.c_float, _P, _P, _P, _P, _P, _P,

@@ -1,5 +1,6 @@
 // abi.hip -- the small kernels (masked reset, action-history rows, batched DSLPID, state vectors, clock probe), RCCL, and the library-level
-// entries of the C ABI (version, last error, struct sizes, debug status)
+// entries of the C ABI (version, last error, struct sizes, debug status); at its end the differentiable rollout (diff_kernels.inc) and the
+// obstacle queries (obstacles.inc)
 #include <chrono>
 #include "gpd_common.inc"
 
@@ -589,4 +590,7 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
 
 // the differentiable rollout: gpd_rollout_tape_floats / gpd_rollout_tape / gpd_rollout_vjp and their kernels
 #include "diff_kernels.inc"
+
+// obstacle fields: gpd_obstacles and its two kernels
+#include "obstacles.inc"
 

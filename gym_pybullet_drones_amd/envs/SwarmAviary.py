@@ -30,7 +30,7 @@ GPU.  `neighbors(radius, k)` / `collisions()` tell a drone who is near it (`gpd_
 import numpy as np
 import torch
 
-from .. import _native, engine, neighbors as _nb
+from .. import _native, engine, neighbors as _nb, obstacles as _ob
 from ..control.DSLPIDControl import DSLPIDControlBatch
 from ..params import DroneParams
 from ..utils.enums import ACT_DIRECT_RPM, ACT_RAW_RPM, ActionType, DroneModel, PHYS_DW, Physics, warn_if_pyb
@@ -668,6 +668,43 @@ class SwarmAviary:
         if min_dist is None:
             min_dist = 2.0 * self.COLLISION_R
         return self.neighbors(min_dist, k=1, rel=False).count > 0
+
+    # ---- obstacle fields (include/gpd.h gpd_obstacles): answers for this rank's drones ---------------------------------------------
+    def set_obstacles(self, field: "_ob.ObstacleField", collision_radius: float = None):
+        """The obstacles of the world (one shared `ObstacleField`; None removes them) for `clearance()` / `range_scan()` /
+        `obstacle_hits()`.  `collision_radius`: the drone as a sphere, default `COLLISION_R`."""
+        if field is None:
+            self._obstacles = None
+            return
+        if field.num_envs is not None:
+            raise ValueError("a swarm is one world: it takes one shared obstacle list, not one per aviary")
+        r = self.COLLISION_R if collision_radius is None else collision_radius
+        self._obstacles = _ob.FieldQuery(field, self.device, self.NUM_DRONES, 0, r)
+
+    def _obstacle_query(self):
+        """(the bound field, this rank's rows of pos4 for the current state)"""
+        q = getattr(self, "_obstacles", None)
+        if q is None:
+            raise ValueError("no obstacles: call set_obstacles(field) first")
+        first = self.RANK * self.slab
+        return q, self._current_pos4()[first:first + self.NUM_DRONES]
+
+    def clearance(self) -> "_ob.Clearance":
+        """For each of this rank's drones the nearest obstacle: `normal` (n, 3), `dist` (n,), `nearest` (n,), `hit` (n,)."""
+        q, pos4 = self._obstacle_query()
+        return q.clearance(pos4, self.core._stream())
+
+    def obstacle_hits(self) -> torch.Tensor:
+        """(n,) bool: this rank's drones closer to an obstacle than their collision radius"""
+        q, pos4 = self._obstacle_query()
+        return q.hits(pos4, self.core._stream())
+
+    def range_scan(self, dirs, max_range: float, frame: str = "body", want_ids: bool = False):
+        """(n, R) distances along the unit directions `dirs` [R, 3] to the first obstacle (`VectorAviary.range_scan`); the
+        attitudes are the core's quaternion plane."""
+        q, pos4 = self._obstacle_query()
+        ranges, ids = q.scan(pos4, self.core.kin_Q, dirs, max_range, frame, want_ids, self.core._stream())
+        return (ranges, ids) if want_ids else ranges
 
     # ---- checkpoint / resume (SURVEY.md section 5: absent upstream) ----------------------------------------------------------
     def get_state(self) -> dict:

@@ -17,7 +17,7 @@ import math
 import numpy as np
 import torch
 
-from .. import _native, engine, neighbors as _nb
+from .. import _native, engine, neighbors as _nb, obstacles as _ob
 from ..params import DroneParams
 from ..utils.enums import ACT_RAW_RPM, ActionType, DroneModel, ObservationType, Physics
 
@@ -229,6 +229,43 @@ class VectorAviary:
         """(E, D, D) uint8: `BaseAviary._getAdjacencyMatrix()` (envs/BaseAviary.py:658-675) of every aviary -- 1 on the diagonal
         and where two drones are closer than `radius` (None: `NEIGHBOURHOOD_RADIUS`)."""
         return self._neighbor_query(radius, 1, False, True)[1]
+
+    # ---- obstacle fields (include/gpd.h gpd_obstacles; the reference: BaseAviary._addObstacles, envs/BaseAviary.py:958-981) -----------
+    def set_obstacles(self, field: "_ob.ObstacleField", collision_radius: float = None):
+        """The obstacles `clearance()` / `range_scan()` / `obstacle_hits()` answer about: one `ObstacleField` shared by every aviary,
+        or one with a list per aviary (`ObstacleField(num_envs=E)`); None removes them.  `collision_radius`: the drone as a sphere
+        (default: the airframe's `COLLISION_R`).  Nothing acts on the integrator: combine `hit` into your own termination."""
+        if field is None:
+            self._obstacles = None
+            return
+        r = self.core.P.COLLISION_R if collision_radius is None else collision_radius
+        self._obstacles = _ob.FieldQuery(field, self.device, self.NUM_ENVS * self.NUM_DRONES, self.NUM_DRONES, r)
+
+    def _obstacle_query(self) -> "_ob.FieldQuery":
+        q = getattr(self, "_obstacles", None)
+        if q is None:
+            raise ValueError("no obstacles: call set_obstacles(field) first")
+        return q
+
+    def clearance(self) -> "_ob.Clearance":
+        """For every drone the nearest obstacle: `normal` (E, D, 3) pointing away from it, the signed `dist` (E, D), its record
+        `nearest` (E, D) and `hit` (E, D).  One launch, no host synchronisation; the tensors are reused by the next call."""
+        q, c, E, D = self._obstacle_query(), self.core, self.NUM_ENVS, self.NUM_DRONES
+        out = q.clearance(c.kin_P, c._stream())
+        return _ob.Clearance(out.normal.unflatten(0, (E, D)), out.dist.view(E, D), out.nearest.view(E, D), out.hit.view(E, D))
+
+    def obstacle_hits(self) -> torch.Tensor:
+        """(E, D) bool: the drones closer to an obstacle than their collision radius"""
+        q, c = self._obstacle_query(), self.core
+        return q.hits(c.kin_P, c._stream()).view(self.NUM_ENVS, self.NUM_DRONES)
+
+    def range_scan(self, dirs, max_range: float, frame: str = "body", want_ids: bool = False):
+        """(E, D, R) distances along the unit directions `dirs` [R, 3] (`obstacles.fan`; a float32 device tensor is used as it is) to
+        the first obstacle, `max_range` where there is none that close.  `frame`: "body" (the directions turn with the attitude),
+        "level" (with the yaw only) or "world".  `want_ids`: also the (E, D, R) int32 records that were hit, -1 for none."""
+        q, c, E, D = self._obstacle_query(), self.core, self.NUM_ENVS, self.NUM_DRONES
+        ranges, ids = q.scan(c.kin_P, c.kin_Q, dirs, max_range, frame, want_ids, c._stream())
+        return (ranges.view(E, D, -1), ids.view(E, D, -1)) if want_ids else ranges.view(E, D, -1)
 
     # ---- domain randomisation: the plant of every drone (include/gpd.h GPD_SCALE_*; SimCore.set_plant) ------------------------
     def set_physical_params(self, mask=None, **scales):

@@ -641,6 +641,59 @@ int gpd_neighbors(const float* pos4, int32_t n_rows, int32_t query_first, int32_
                   int32_t* nbr_idx, float* nbr_rel, uint8_t* adjacency, void* stream);
 
 /*
+ * Obstacle fields: for every drone the signed distance to the nearest obstacle and its direction, whether it collides, and what
+ * a fan of range sensors sees.  The reference puts bodies into the Bullet world (BaseAviary._addObstacles, envs/BaseAviary.py:
+ * 958-981; BaseRLAviary._addObstacles, envs/BaseRLAviary.py:99-128) and leaves every question about them to Bullet; here the
+ * world is a list of analytic shapes and the questions are answered on the device.  Nothing acts on the integrator: a consumer
+ * combines `hit` into its own termination, or steers by the normals.
+ *
+ * An obstacle is a record of GPD_OBST_FLOATS = 8 floats  cx, cy, cz, kind, ax, ay, az, 0  (kind: a GPD_OBST_* value stored
+ * exactly in a float):
+ *   GPD_OBST_NONE      skipped (lists of different lengths per aviary are padded with it)
+ *   GPD_OBST_SPHERE    centre c, radius ax
+ *   GPD_OBST_BOX       axis-aligned, centre c, half extents ax, ay, az
+ *   GPD_OBST_CYLINDER  vertical, centre c, radius ax, half height az
+ *   GPD_OBST_FLOOR     the half-space z <= cz
+ * The formulas are csrc/obstacle_math.inc: the exact signed distance (negative inside) with its unit gradient, and the first entry
+ * t >= 0 of a ray p + t d, |d| = 1 (t = 0 for an origin inside or on the obstacle, +inf for a miss).
+ *
+ *   pos4            [n][4] floats x, y, z, (ignored), 16-byte aligned: plane P of GpdState.kin, or GpdSwarm.pos4 (as gpd_neighbors)
+ *   quat4           [n][4] floats x, y, z, w, 16-byte aligned: plane Q of GpdState.kin; NULL when no ray needs it (ray_frame 0)
+ *   drones_per_env  D >= 1: row i belongs to aviary i / D (n is a multiple of D).  0: one world
+ *   obst, n_obst, obst_ld   float f of record m of aviary e is obst[(m * 8 + f) * obst_ld + e]:  obst_ld = 1 is ONE list of n_obst
+ *                   records ([n_obst][8], e = 0) shared by every drone; obst_ld >= n / D is one list per aviary, stored as field
+ *                   planes (needs D >= 1).  1 <= n_obst <= GPD_OBST_MAX
+ *   collision_radius   the drone as a SPHERE of this radius (COLLISION_R of the airframe): the URDF's collision body is a cylinder of
+ *                   that radius and of height COLLISION_H, which the sphere approximates -- it is exact sideways and generous by
+ *                   COLLISION_R - COLLISION_H / 2 above and below
+ *   clear4          [n][4] float out or NULL (16-byte aligned): (nx, ny, nz, d) -- d the minimum over the records of each one's own
+ *                   signed distance, n that record's unit gradient (away from the obstacle)
+ *   nearest         [n] int32 out or NULL: the minimising record; ties go to the lower m
+ *   hit             [n] uint8 out or NULL: 1 where d < collision_radius (strictly)
+ *                   Every record NONE, or a position that is not finite: (0, 0, 0, +inf), nearest -1, hit 0.
+ *   ray_dirs, n_rays   [n_rays][3] unit vectors shared by all drones, 1 <= n_rays <= GPD_OBST_MAX_RAYS (read only with `ranges`)
+ *   ray_frame       GPD_RAY_WORLD: the directions as they are.  GPD_RAY_LEVEL: rotated about z by the drone's yaw (the yaw of
+ *                   pybullet's Euler angles of the NORMALISED quaternion).  GPD_RAY_BODY: rotated by the attitude; |q| does not
+ *                   matter (DYN never renormalises q)
+ *   max_range       > 0, finite
+ *   ranges          [n][n_rays] float out or NULL (then every ray argument is ignored): the smallest entry distance over the records,
+ *                   capped at max_range; no hit is max_range
+ *   ray_hit         [n][n_rays] int32 out or NULL: the record that was hit (ties to the lower m), -1 for none within max_range
+ *                   A pose that is not finite (position; the quaternion where the frame uses it): max_range and -1.
+ * Everything is validated before the first device call.  GPD_EINVAL: NULL pos4 / obst, no output at all, alignment, n <= 0, n not a
+ * multiple of D, obst_ld, and with `ranges`: NULL ray_dirs, max_range, ray_frame, NULL quat4 for the frames that need it.
+ * GPD_ERANGE: n_obst, n_rays, n > 2^26.  Asynchronous on `stream`, no allocation, at most two launches (clearance; scan).
+ */
+enum { GPD_OBST_NONE = -1, GPD_OBST_SPHERE = 0, GPD_OBST_BOX = 1, GPD_OBST_CYLINDER = 2, GPD_OBST_FLOOR = 3 };
+enum { GPD_RAY_WORLD = 0, GPD_RAY_LEVEL = 1, GPD_RAY_BODY = 2 };
+#define GPD_OBST_FLOATS 8
+#define GPD_OBST_MAX 1024
+#define GPD_OBST_MAX_RAYS 64
+int gpd_obstacles(const float* pos4, const float* quat4, int32_t n, int32_t drones_per_env, const float* obst, int32_t n_obst,
+                  int64_t obst_ld, float collision_radius, float* clear4, int32_t* nearest, uint8_t* hit, const float* ray_dirs,
+                  int32_t n_rays, int32_t ray_frame, float max_range, float* ranges, int32_t* ray_hit, void* stream);
+
+/*
  * Masked reset.  Replaces BaseAviary.reset/_housekeeping (envs/BaseAviary.py:220-255, 451-477)
  * for the envs whose mask byte is non-zero (mask == NULL: all).  Sets pos/quat to init_pose,
  * vel, rpy_rates, last_rpm and step_counter to zero and writes the initial obs12 rows.  As in
