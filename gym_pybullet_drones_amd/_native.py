@@ -30,7 +30,8 @@ ABI_VERSION = 9
 #                     slots of a rollout step)
 #   policy.hip        gpd_rollout_policy                 the default scheduler: 10 % faster on its MFMA + activation mix (round-2 A/B)
 #   swarm.hip         the one-world kernels              max-ilp, as in rounds 2-4
-#   abi.hip           small kernels, RCCL, library-level entries; the differentiable rollout and gpd_obstacles (csrc/*.inc pulled in at its end)
+#   abi.hip           small kernels, RCCL, library-level entries; the differentiable rollout, gpd_obstacles and gpd_mppi (csrc/*.inc pulled in at
+#                     its end)
 #   mrac.hip          gpd_mrac / gpd_mrac_reset / gpd_rollout_mrac: the adaptive controller and the rollout that carries it (max-ilp)
 #   -mllvm -amdgpu-kernarg-preload-count=14: the first 14 argument dwords of a kernel arrive in SGPRs with the wave (gfx942+ command
 #   processor) instead of through a scalar load -- gpd_step_kernel's argument list starts with what its load section needs
@@ -39,7 +40,7 @@ MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 HIPCC_FLAGS = COMMON_FLAGS + MAX_ILP + ["-shared"]        # (kept under this name for the ISA tests)
 UNITS = (("step_rollout.hip", MAX_ILP + KERNARG_PRELOAD), ("policy.hip", []), ("swarm.hip", MAX_ILP + KERNARG_PRELOAD), ("abi.hip", MAX_ILP), ("mrac.hip", MAX_ILP))
-HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc", "obstacle_math.inc", "obstacles.inc")
+HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc", "obstacle_math.inc", "obstacles.inc", "mppi_math.inc", "mppi.inc")
 
 
 class GpdError(RuntimeError):
@@ -92,6 +93,15 @@ class GpdMrac(ctypes.Structure):
                 ("pwm2rpm_scale", ctypes.c_float), ("inv_pwm2rpm_scale", ctypes.c_float), ("pwm2rpm_const", ctypes.c_float),
                 ("min_pwm", ctypes.c_float), ("max_pwm", ctypes.c_float), ("pad_", ctypes.c_float * 3),
                 ("Kx0", ctypes.c_float * 48), ("Kr0", ctypes.c_float * 16)]
+
+
+class GpdMppi(ctypes.Structure):
+    """mirror of `struct GpdMppi` (gpd_mppi: the sampler, the cost's weights, the Philox key and the plan's counter word)"""
+    _fields_ = [("horizon", ctypes.c_int32), ("samples", ctypes.c_int32), ("sigma", ctypes.c_float * 4), ("act_lo", ctypes.c_float * 4),
+                ("act_hi", ctypes.c_float * 4), ("lam", ctypes.c_float), ("w_pos", ctypes.c_float), ("w_vel", ctypes.c_float),
+                ("w_tilt", ctypes.c_float), ("w_rate", ctypes.c_float), ("w_term", ctypes.c_float), ("w_obs", ctypes.c_float),
+                ("obst_margin", ctypes.c_float), ("collision_radius", ctypes.c_float), ("seed", ctypes.c_uint32 * 2),
+                ("iteration", ctypes.c_uint32)]
 
 
 #: floats of MRAC state per controller (GPD_MRAC_STATE): Kx [12][4] | Kr [4][4] | Xm [12]
@@ -176,6 +186,8 @@ _SIGNATURES = {
                                      _P, _P, _P, _P]),
     "gpd_obstacles": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, _P, _P, _P,
                                      _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _P, _P, _P]),
+    "gpd_mppi": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg), ctypes.POINTER(GpdMppi), _P,
+                                ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int32, ctypes.c_int64, _P, _P, _P, _P]),
     "gpd_reset": (ctypes.c_int, [ctypes.POINTER(GpdState), _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32,
                                  ctypes.c_int32, _P, _P]),
     "gpd_pid": (ctypes.c_int, [ctypes.POINTER(GpdParams), _P, ctypes.c_int64, ctypes.c_float, _P, _P, _P, _P, _P, _P,

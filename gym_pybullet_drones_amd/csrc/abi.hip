@@ -1,6 +1,6 @@
 // abi.hip -- the small kernels (masked reset, action-history rows, batched DSLPID, state vectors, clock probe), RCCL, and the library-level
-// entries of the C ABI (version, last error, struct sizes, debug status); at its end the differentiable rollout (diff_kernels.inc) and the
-// obstacle queries (obstacles.inc)
+// entries of the C ABI (version, last error, struct sizes, debug status); at its end the differentiable rollout (diff_kernels.inc), the
+// obstacle queries (obstacles.inc) and the sampling-based planner (mppi.inc)
 #include <chrono>
 #include "gpd_common.inc"
 
@@ -593,4 +593,7 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
 
 // obstacle fields: gpd_obstacles and its two kernels
 #include "obstacles.inc"
+
+// sampling-based MPC: gpd_mppi and its kernel
+#include "mppi.inc"
 

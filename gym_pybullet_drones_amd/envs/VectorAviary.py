@@ -17,7 +17,7 @@ import math
 import numpy as np
 import torch
 
-from .. import _native, engine, neighbors as _nb, obstacles as _ob
+from .. import _native, engine, mppi as _mppi, neighbors as _nb, obstacles as _ob
 from ..params import DroneParams
 from ..utils.enums import ACT_RAW_RPM, ActionType, DroneModel, ObservationType, Physics
 
@@ -266,6 +266,16 @@ class VectorAviary:
         q, c, E, D = self._obstacle_query(), self.core, self.NUM_ENVS, self.NUM_DRONES
         ranges, ids = q.scan(c.kin_P, c.kin_Q, dirs, max_range, frame, want_ids, c._stream())
         return (ranges.view(E, D, -1), ids.view(E, D, -1)) if want_ids else ranges.view(E, D, -1)
+
+    # ---- sampling-based MPC (include/gpd.h gpd_mppi; the reference has no planner) ---------------------------------------------------
+    def mppi(self, horizon: int, samples: int, sigma, lam: float, cost: "_mppi.MPPICost" = None, seed: int = 0, act_lo=None,
+             act_hi=None) -> "_mppi.MPPI":
+        """An `mppi.MPPI` planner bound to this batch (single drones, RPM or VEL actions) and to the field given to `set_obstacles()`,
+        if any: `plan(goal)` returns the next action `(E, 4)` from the current state, `advance()` shifts the nominal after it was
+        flown.  The default bounds are [-1, 1]^4 for RPM and [-1, 1]^3 x [0, 1] for VEL.  The planning model is the flag-less DYN
+        integrator, whatever `physics` this batch was built with."""
+        return _mppi.MPPI(self.core, horizon, samples, sigma, lam, cost=cost, seed=seed, field=getattr(self, "_obstacles", None),
+                          act_lo=act_lo, act_hi=act_hi)
 
     # ---- domain randomisation: the plant of every drone (include/gpd.h GPD_SCALE_*; SimCore.set_plant) ------------------------
     def set_physical_params(self, mask=None, **scales):

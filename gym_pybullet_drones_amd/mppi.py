@@ -1,0 +1,133 @@
+"""Sampling-based model-predictive control on the device: the binding of `gpd_mppi` (include/gpd.h).
+
+Per drone, M perturbed action sequences around a nominal one are rolled H env steps through the in-register physics, scored, and the
+nominal is replaced by their cost-weighted average (MPPI, Williams et al.): one launch per plan, no trajectory in memory.  The
+reference has no planner; its examples steer by hand-written DSLPID set-points.
+
+THE PLANNING MODEL IS THE FLAG-LESS DYN INTEGRATOR of a single drone: `physics_flags` is 0 whatever the environment's is (no drag,
+ground effect, downwash, ground plane or damping), the plant is the nominal airframe, and there are no episode ends.  The environment
+the plan is flown in may have all of these; the plan is then a plan under a simpler model, as in any MPC.
+"""
+import ctypes
+import dataclasses
+import math
+
+import torch
+
+from . import _native
+from . import obstacles as _ob
+
+ACT_RPM, ACT_VEL = 0, 2
+#: the default bounds of a sample's action: [-1, 1]^4 for RPM; a direction in [-1, 1]^3 and a speed fraction in [0, 1] for VEL
+DEFAULT_BOUNDS = {ACT_RPM: ((-1.0,) * 4, (1.0,) * 4), ACT_VEL: ((-1.0, -1.0, -1.0, 0.0), (1.0, 1.0, 1.0, 1.0))}
+
+
+@dataclasses.dataclass
+class MPPICost:
+    """The running cost of the state after each step (include/gpd.h):
+    `w_pos |p - goal|^2` (times `w_term` on the last step) `+ w_vel |v|^2 + w_tilt (1 - R22) + w_rate |omega_body|^2
+    + w_obs max(0, obst_margin - (d - collision_radius))^2`; `collision_radius` None: the airframe's `COLLISION_R`."""
+    w_pos: float = 1.0
+    w_vel: float = 0.05
+    w_tilt: float = 0.5
+    w_rate: float = 0.01
+    w_term: float = 5.0
+    w_obs: float = 100.0
+    obst_margin: float = 0.3
+    collision_radius: float = None
+
+
+class MPPI:
+    """A planner bound to a `SimCore` of single drones with RPM or VEL actions: the nominal sequence `[H, N, 4]`, the samples' `costs`
+    `[N, M]` and `stats` `[N, 4]` (min cost, weighted mean cost, effective sample size, finite samples) are tensors allocated once;
+    every launch goes to the core's stream.  `field`: an `obstacles.ObstacleField` (or the `FieldQuery` an aviary built from one)."""
+
+    def __init__(self, core, horizon: int, samples: int, sigma, lam: float, cost: MPPICost = None, seed: int = 0, field=None,
+                 act_lo=None, act_hi=None):
+        if core.D != 1:
+            raise ValueError("MPPI plans for aviaries of one drone (drones_per_env must be 1)")
+        if core.act_code not in DEFAULT_BOUNDS:
+            raise ValueError("MPPI plans over RPM or VEL actions (ActionType.RPM / ActionType.VEL)")
+        self.core, self.device, self.N = core, core.device, core.N
+        self.H, self.M = int(horizon), int(samples)
+        if self.H < 1 or self.M % 64 != 0 or not 64 <= self.M <= 1024:
+            raise ValueError("horizon must be >= 1 and samples a multiple of 64 in 64..1024")
+        if not (lam > 0.0 and math.isfinite(lam)):
+            raise ValueError("lam must be positive and finite")
+        cost = MPPICost() if cost is None else cost
+        lo, hi = DEFAULT_BOUNDS[core.act_code]
+        lo, hi = (lo if act_lo is None else tuple(act_lo)), (hi if act_hi is None else tuple(act_hi))
+        sigma = (float(sigma),) * 4 if isinstance(sigma, (int, float)) else tuple(float(s) for s in sigma)
+        if len(sigma) != 4 or len(lo) != 4 or len(hi) != 4:
+            raise ValueError("sigma, act_lo and act_hi have 4 components")
+        radius = core.P.COLLISION_R if cost.collision_radius is None else cost.collision_radius
+        seed = int(seed)
+        F4 = ctypes.c_float * 4
+        self._q = _native.GpdMppi(horizon=self.H, samples=self.M, sigma=F4(*sigma), act_lo=F4(*lo), act_hi=F4(*hi), lam=lam, w_pos=cost.w_pos,
+                                  w_vel=cost.w_vel, w_tilt=cost.w_tilt, w_rate=cost.w_rate, w_term=cost.w_term, w_obs=cost.w_obs,
+                                  obst_margin=cost.obst_margin, collision_radius=radius,
+                                  seed=(ctypes.c_uint32 * 2)(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF), iteration=0)
+        # the model's configuration: the core's rates and action type, nothing else of it
+        c = core._cfg
+        self._cfg = _native.GpdStepCfg(num_envs=core.E, drones_per_env=1, act_type=core.act_code, substeps=core.S, physics_flags=0,
+                                       pyb_dt=c.pyb_dt, ctrl_dt=c.ctrl_dt, inv_ctrl_dt=c.inv_ctrl_dt, lanes_per_wave=c.lanes_per_wave,
+                                       task=0, auto_reset=0)
+        if isinstance(field, _ob.ObstacleField):
+            field = _ob.FieldQuery(field, self.device, self.N, 1, radius)
+        # (gpd_obstacles names the shared list by a pitch of 1, gpd_mppi by 0; one aviary's own list at pitch 1 is the same bytes)
+        self._obst = (None, 0, 0) if field is None else (field.obst, field.n_obst, 0 if field.obst_ld == 1 else field.obst_ld)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self._u = [torch.zeros((self.H, self.N, 4), **f32), torch.zeros((self.H, self.N, 4), **f32)]
+        self._goal = torch.zeros((self.N, 4), **f32)
+        self.costs, self.stats = torch.zeros((self.N, self.M), **f32), torch.zeros((self.N, 4), **f32)
+        self.iteration = 0
+        self.reset()
+
+    @property
+    def nominal(self) -> torch.Tensor:
+        """the nominal action sequence `[H, N, 4]` (the tensor the next plan starts from)"""
+        return self._u[0]
+
+    def reset(self, rows=None, value=None):
+        """Set the nominal of the drones `rows` (index or mask tensor; None: all) to `value` (4 numbers or `[.., 4]`; None: hover --
+        zeros for RPM, a zero speed along +x for VEL, which commands a stop)."""
+        if value is None:
+            value = (0.0, 0.0, 0.0, 0.0) if self.core.act_code == ACT_RPM else (1.0, 0.0, 0.0, 0.0)
+        v = torch.as_tensor(value, dtype=torch.float32, device=self.device)
+        if rows is None:
+            self._u[0][:] = v
+        else:
+            self._u[0][:, rows] = v
+
+    def _launch(self, goal, goal_stride):
+        self._q.iteration = self.iteration & 0xFFFFFFFF
+        obst, n_obst, ld = self._obst
+        c = self.core
+        _native.call("gpd_mppi", self.device, c._stream(), c._params, c._state, self._cfg, self._q, self._u[0], self.N * 4, goal, goal_stride,
+                     obst, n_obst, ld, self._u[1], self.costs, self.stats)
+        self._u.reverse()
+        self.iteration += 1
+
+    def plan(self, goal, iterations: int = 1) -> torch.Tensor:
+        """Run `iterations` updates of the nominal from the core's CURRENT state towards `goal` -- `[N, 3]` (one goal per drone for the
+        whole horizon), `[3]` (the same for all), or a float32 device tensor `[H, N, 4]` of xyz-padded goals per step, used as it is --
+        and return the first action of the nominal, `[N, 4]`.  The state is not touched; no host synchronisation."""
+        g = goal if isinstance(goal, torch.Tensor) else torch.as_tensor(goal, dtype=torch.float32)
+        if g.ndim == 3:
+            if tuple(g.shape) != (self.H, self.N, 4) or g.dtype != torch.float32 or g.device != self.device or not g.is_contiguous():
+                raise ValueError(f"a goal per step is a contiguous float32 device tensor [{self.H}, {self.N}, 4]")
+            buf, stride = g, self.N * 4
+        else:
+            self._goal[:, :3] = g.to(self.device, torch.float32)
+            buf, stride = self._goal, 0
+        for _ in range(int(iterations)):
+            self._launch(buf, stride)
+        return self._u[0][0]
+
+    def advance(self):
+        """The warm start of the next plan: shift the nominal one step, repeating its last row."""
+        u, v = self._u
+        if self.H > 1:
+            v[:-1] = u[1:]
+        v[-1] = u[-1]
+        self._u.reverse()

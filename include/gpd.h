@@ -694,6 +694,62 @@ int gpd_obstacles(const float* pos4, const float* quat4, int32_t n, int32_t dron
                   int32_t n_rays, int32_t ray_frame, float max_range, float* ranges, int32_t* ray_hit, void* stream);
 
 /*
+ * Sampling-based model-predictive control (MPPI, Williams et al., "Information theoretic MPC for model-based reinforcement
+ * learning", ICRA 2017): per drone, M perturbed action sequences around a nominal one are rolled H env steps through the physics,
+ * scored, and the nominal is replaced by their cost-weighted average.  The reference has no planner; the nearest it comes is the
+ * hand-written DSLPID set-points of its examples.  One launch; the state is READ ONLY -- the call leaves every byte of GpdState as
+ * it found it -- and the M x H trajectories never reach memory.
+ *
+ * For drone n, sample m, step h:
+ *   z     the four standard normals of (n, m, h, iteration): Philox4x32-10 with key `seed` on the counter (n, m, h, iteration), its
+ *         four words as the float32 uniforms ((x >> 8) + 0.5) 2^-24 in (0, 1], two Box-Muller pairs (csrc/mppi_math.inc)
+ *   a     clamp(u_in[h][n] + sigma o z, act_lo, act_hi), per component
+ *   step  one env step exactly as gpd_rollout takes it for the action a (the action mapping with DSLPID and its members for
+ *         GPD_ACT_VEL, `substeps` sub-steps, the rpy refresh); controller members and kinematic state are per-sample copies
+ *   c_h   of the state AFTER the step:  w_pos |p - goal_h|^2 (x w_term at h = H - 1) + w_vel |v|^2 + w_tilt (1 - R22)
+ *         + w_rate |omega_body|^2 + w_obs max(0, obst_margin - (d - collision_radius))^2,  d the minimum of the records' signed
+ *         distances (csrc/obstacle_math.inc; the term is absent without a list), R22 of the quaternion as it is.  Every term is
+ *         continuous in the state.
+ * S_m = sum_h c_h;  w_m = exp(-(S_m - min S) / lambda), minimum and sums over the FINITE S_m only, a sample whose cost is not finite
+ * has weight 0;  u_out[h] = u_in[h] + sum_m w_m (a_mh - u_in[h]) / sum_m w_m, clamped once more against rounding.  No finite sample
+ * at all: u_out = clamp(u_in), stats4 = (+inf, +inf, 0, 0).
+ *
+ *   cfg             drones_per_env = 1, physics_flags 0 (the planning model is the flag-less explicit integrator), task GPD_TASK_NONE,
+ *                   no auto-reset, act_type GPD_ACT_RPM or GPD_ACT_VEL; any sub-step count
+ *   u_in, u_step_stride     [H][N][4] nominal actions, 16-byte aligned, the stride in floats (a multiple of 4, >= 4 N)
+ *   goal, goal_step_stride  [N][4] x, y, z, (ignored), 16-byte aligned; stride 0: one goal per drone for every step, else [H][N][4]
+ *   obst, n_obst, obst_ld   the records of gpd_obstacles; NULL or n_obst 0: no list.  obst_ld 0: ONE list [n_obst][8] shared by every
+ *                   drone; obst_ld >= N: one list per aviary as field planes, float f of record r of aviary e at
+ *                   obst[(r * 8 + f) * obst_ld + e]
+ *   u_out           [H][N][4] out, the stride of u_in; must not be u_in
+ *   costs           [N][M] out, REQUIRED: S_m per sample -- also the kernel's workspace between its two passes
+ *   stats4          [N][4] out, 16-byte aligned: min S, the weighted mean sum w S / sum w, the effective sample size
+ *                   (sum w)^2 / sum w^2, the number of samples with a finite cost
+ * Refused before any device work.  GPD_EINVAL: a NULL pointer (obst excepted), the state's layout, samples not a multiple of 64 in
+ * 64 .. 1024, horizon < 1, lambda not positive and finite, a sigma that is negative or not finite, act_lo > act_hi, u_out == u_in,
+ * alignment, the strides, n_obst outside 0 .. GPD_OBST_MAX, obst_ld neither 0 nor >= N, GPD_ACT_VEL without state.pid.
+ * GPD_ENOTSUP: drones_per_env != 1, any physics flag, a task or auto_reset, any other action type, GPD_ACT_VEL on an airframe
+ * without DSLPID.  GPD_ERANGE: N > 2^26.  Asynchronous on `stream`, no allocation, one launch; two calls with the same arguments
+ * give the same bits.
+ */
+typedef struct GpdMppi {
+    int32_t horizon;        /* H >= 1 env steps */
+    int32_t samples;        /* M: a multiple of 64, 64 .. 1024 */
+    float sigma[4];         /* std of the noise per action component (>= 0) */
+    float act_lo[4], act_hi[4];   /* a = clamp(u + sigma*z, lo, hi) per component */
+    float lambda;           /* temperature > 0 */
+    float w_pos, w_vel, w_tilt, w_rate;   /* running cost */
+    float w_term;           /* the position term of the LAST step is multiplied by this */
+    float w_obs, obst_margin;             /* hinge on the clearance */
+    float collision_radius;
+    uint32_t seed[2];       /* Philox key */
+    uint32_t iteration;     /* fourth counter word: the caller bumps it per plan */
+} GpdMppi;
+int gpd_mppi(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, const GpdMppi* mppi, const float* u_in,
+             int64_t u_step_stride, const float* goal, int64_t goal_step_stride, const float* obst, int32_t n_obst, int64_t obst_ld,
+             float* u_out, float* costs, float* stats4, void* stream);
+
+/*
  * Masked reset.  Replaces BaseAviary.reset/_housekeeping (envs/BaseAviary.py:220-255, 451-477)
  * for the envs whose mask byte is non-zero (mask == NULL: all).  Sets pos/quat to init_pose,
  * vel, rpy_rates, last_rpm and step_counter to zero and writes the initial obs12 rows.  As in
