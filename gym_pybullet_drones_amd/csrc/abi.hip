@@ -1,6 +1,6 @@
 // abi.hip -- the small kernels (masked reset, action-history rows, batched DSLPID, state vectors, clock probe), RCCL, and the library-level
-// entries of the C ABI (version, last error, struct sizes, debug status); at its end the differentiable rollout (diff_kernels.inc), the
-// obstacle queries (obstacles.inc) and the sampling-based planner (mppi.inc)
+// entries of the C ABI (version, last error, struct sizes, debug status); at its end the differentiable rollout (diff_kernels.inc; through the
+// DSLPID loop: diff_pid_kernels.inc), the obstacle queries (obstacles.inc) and the sampling-based planner (mppi.inc)
 #include <chrono>
 #include "gpd_common.inc"
 
@@ -590,6 +590,9 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
 
 // the differentiable rollout: gpd_rollout_tape_floats / gpd_rollout_tape / gpd_rollout_vjp and their kernels
 #include "diff_kernels.inc"
+
+// ... through the DSLPID loop: gpd_rollout_tape_pid_floats / gpd_rollout_tape_pid / gpd_rollout_vjp_pid and their kernels
+#include "diff_pid_kernels.inc"
 
 // obstacle fields: gpd_obstacles and its two kernels
 #include "obstacles.inc"

@@ -17,6 +17,14 @@ without a plant table, no auto-reset; everything else raises `GpdError` with the
 With `plant_scales=` the per-drone plant (`SimCore.set_plant`) is the third differentiable input: the call installs the scales as the
 core's plant table, and the backward is `gpd_rollout_vjp_plant` (the same sweep, which also sums the cotangents of the plant rows it
 reads) followed by `gpd_plant_derive_vjp` (rows -> scale factors).  System identification and calibration: examples/sysid.py.
+
+    obs12, reward, kin_K, pid_K, *_ = core.rollout_diff_pid(actions, pid_gains=gains)     # a PID / VEL / ONE_D_PID core; gains [6, 3]
+    loss(obs12).backward()                                                                # actions.grad, gains.grad
+
+The three action types that close the loop in the kernel go through `rollout_diff_pid` (`gpd_rollout_tape_pid` /
+`gpd_rollout_vjp_pid`): the nine controller members (`pack_pid` / `unpack_pid`) are a differentiable input
+and output next to the kinematic state, and the 18 gains of the cascaded PID receive a gradient.  Tuning the controller by
+back-propagation through the flight: examples/tune_pid.py.
 """
 import ctypes
 
@@ -162,3 +170,151 @@ def rollout_diff(core, actions, kin0=None, num_steps: int = None, plant_scales=N
         core.set_plant(plant_scales)
         plant_scales = None
     return RolloutDiff.apply(core, kin0, actions, K, a_stride, plant_scales, True)
+
+
+# ---- through the DSLPID loop (include/gpd.h `gpd_rollout_tape_pid` / `gpd_rollout_vjp_pid`, csrc/diff_pid_kernels.inc) ----------------
+#: the rows of `pid_gains` [6, 3], in the order of `g_gains [18][ld]` and of the fields of GpdParams
+GAIN_FIELDS = ("p_for", "i_for", "d_for", "p_tor", "i_tor", "d_tor")
+
+
+def pack_pid(int_pos_e, last_rpy, int_rpy_e, ld: int = None):
+    """(integral position error [N,3], last rpy [N,3], integral rpy error [N,3]) -> the `[9, ld]` rows of `GpdState.pid` (ld: N rounded
+    up to 64 by default; the padding is zero).  Differentiable torch code."""
+    n = int_pos_e.shape[0]
+    ld = (n + 63) // 64 * 64 if ld is None else int(ld)
+    rows = torch.cat([int_pos_e, last_rpy, int_rpy_e], dim=1).t()
+    return torch.cat([rows, rows.new_zeros((9, ld - n))], dim=1)
+
+
+def unpack_pid(pid, n: int = None):
+    """the `[9, ld]` rows -> (integral position error [n,3], last rpy [n,3], integral rpy error [n,3]) (n: ld by default).
+    Differentiable."""
+    pid = pid.view(9, -1)
+    n = pid.shape[1] if n is None else int(n)
+    rows = pid[:, :n].t()
+    return rows[:, 0:3], rows[:, 3:6], rows[:, 6:9]
+
+
+def gains_of(params):
+    """the 18 gains of a `GpdParams` as a float32 CPU tensor `[6, 3]` (rows: GAIN_FIELDS)"""
+    return torch.tensor([list(getattr(params, f)) for f in GAIN_FIELDS], dtype=torch.float32)
+
+
+def params_with_gains(params, gains):
+    """a copy of the by-value `GpdParams` whose 18 gains are `gains` ([6, 3], rows: GAIN_FIELDS).  Reads the tensor to the host:
+    a synchronisation when it lives on the device."""
+    host = gains.detach().to(device="cpu", dtype=torch.float32).reshape(6, 3).tolist()
+    out = type(params).from_buffer_copy(params)
+    for f, row in zip(GAIN_FIELDS, host):
+        setattr(out, f, (ctypes.c_float * 3)(*row))
+    return out
+
+
+def tape_floats_pid(core, K: int) -> int:
+    """floats of the tape of a K-step call on `core` (`gpd_rollout_tape_pid_floats`); raises GpdError for an unsupported configuration"""
+    out = ctypes.c_int64(0)
+    _native.call("gpd_rollout_tape_pid_floats", None, _native.NO_STREAM, core._cfg, int(K), core.ld, ctypes.byref(out))
+    return out.value
+
+
+def tape_forward_pid(core, params, K, actions, a_stride, obs, rew, term, trunc, tape):
+    """one `gpd_rollout_tape_pid` launch on the core's state, cfg and target with `params` (the core's own, or a copy with other gains)"""
+    _native.call("gpd_rollout_tape_pid", core.device, core._stream(), params, core._state, core._cfg, K, actions, a_stride, core.target,
+                 obs, core.N * 12, rew, term, trunc, core.E, tape)
+
+
+def sweep_pid(core, params, K, actions, a_stride, tape, g_obs, g_rew, g_kin, g_pid, g_act, g_gains=None, target=OWN):
+    """one `gpd_rollout_vjp_pid` launch over `tape`: `g_obs` / `g_rew`: None = zeros; `g_kin [13*ld]` and `g_pid [9, ld]` are read and
+    overwritten, `g_act [K,N,A]` written, `g_gains [18, ld]` (None: not asked for) written per drone"""
+    _native.call("gpd_rollout_vjp_pid", core.device, core._stream(), params, core._cfg, core.ld, K, actions, a_stride,
+                 core.target if target is OWN else target, tape, g_obs, core.N * 12, g_rew, core.E, g_kin, g_pid, g_act, g_gains)
+
+
+class RolloutDiffPid(torch.autograd.Function):
+    """forward: `gpd_rollout_tape_pid` from `kin0` / `pid0` (copied into the core's state first); backward: `gpd_rollout_vjp_pid`"""
+
+    @staticmethod
+    def forward(ctx, core, kin0, pid0, actions, K, a_stride, pid_gains=None):
+        dev, N, E = core.device, core.N, core.E
+        size = tape_floats_pid(core, K)                        # (also the configuration check, before anything is touched)
+        params = core._params if pid_gains is None else params_with_gains(core._params, pid_gains)
+        if kin0.data_ptr() != core.kin_store.data_ptr():
+            core.kin_store.copy_(kin0)
+        if pid0.data_ptr() != core.pid.data_ptr():
+            core.pid.copy_(pid0.view(9, core.ld))
+        obs = torch.empty((K, N, 12), dtype=torch.float32, device=dev)
+        rew = torch.empty((K, E), dtype=torch.float32, device=dev)
+        term = torch.empty((K, E), dtype=torch.bool, device=dev)
+        trunc = torch.empty((K, E), dtype=torch.bool, device=dev)
+        tape = torch.empty((size,), dtype=torch.float32, device=dev)
+        core.state_version += 1
+        tape_forward_pid(core, params, K, actions, a_stride, obs, rew, term, trunc, tape)
+        kin_k, pid_k = core.kin_store.clone(), core.pid.clone()
+        core._publish_latest(obs, rew, term, trunc, K)
+        ctx.core, ctx.K, ctx.a_stride, ctx.params, ctx.target = core, K, a_stride, params, core.target
+        ctx.with_gains = pid_gains is not None and pid_gains.requires_grad
+        ctx.gains_like = None if pid_gains is None else (pid_gains.shape, pid_gains.dtype, pid_gains.device)
+        ctx.save_for_backward(actions, tape)
+        ctx.mark_non_differentiable(term, trunc)
+        ctx.set_materialize_grads(False)                       # (an output nobody differentiates arrives as None: NULL = zeros)
+        return obs, rew, kin_k, pid_k, term, trunc
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_obs, g_rew, g_kin, g_pid, _g_term, _g_trunc):
+        core, K = ctx.core, ctx.K
+        actions, tape = ctx.saved_tensors
+        dev, N = core.device, core.N
+        g_obs = None if g_obs is None else g_obs.to(torch.float32).contiguous()
+        g_rew = None if g_rew is None else g_rew.to(torch.float32).contiguous()
+        g_kin = torch.zeros_like(core.kin_store) if g_kin is None else g_kin.to(torch.float32).clone(memory_format=torch.contiguous_format)
+        g_pid = torch.zeros_like(core.pid) if g_pid is None else g_pid.to(torch.float32).clone(memory_format=torch.contiguous_format)
+        g_act = torch.empty((K, N, core.A), dtype=torch.float32, device=dev)
+        with_gains = ctx.with_gains and ctx.needs_input_grad[6]
+        g_rows = torch.zeros((18, core.ld), dtype=torch.float32, device=dev) if with_gains else None     # (the kernel writes drones 0 .. N-1)
+        sweep_pid(core, ctx.params, K, actions, ctx.a_stride, tape, g_obs, g_rew, g_kin, g_pid, g_act, g_rows, ctx.target)
+        g_gains = None
+        if with_gains:         # the forward's gains are shared: the sum over drones, in float64 (N terms), in the caller's shape and place
+            shape, dtype, device = ctx.gains_like
+            g_gains = g_rows[:, :N].sum(dim=1, dtype=torch.float64).reshape(6, 3).to(device=device, dtype=dtype).reshape(shape)
+        if ctx.a_stride == 0:                                  # a shared action block: its gradient is the sum over the steps
+            g_act = g_act.sum(dim=0)
+        return None, g_kin, g_pid, g_act.view(actions.shape), None, None, g_gains
+
+
+def rollout_diff_pid(core, actions, kin0=None, pid0=None, num_steps: int = None, pid_gains=None):
+    """`SimCore.rollout_diff_pid`: K env steps of a PID / VEL / ONE_D_PID core in one launch, differentiable with respect to `actions`,
+    `kin0`, `pid0` and `pid_gains`.
+
+    `actions` and `kin0` as in `rollout_diff`.  `pid0`: None (the core's own controller members) or a `[9, ld]` tensor (`pack_pid`),
+    copied into the state first.  Returns fresh tensors `(obs12 [K,N,12], reward [K,E], kin_K [13*ld], pid_K [9, ld], terminated [K,E],
+    truncated [K,E])`; the first four carry gradients, and `kin_K` / `pid_K` of one call given as `kin0` / `pid0` of the next chain the
+    graph.  `pid_gains`: None (the core's gains: constants, no gain gradient) or a `[6, 3]` tensor, rows `GAIN_FIELDS`; it REPLACES
+    the gains of the by-value parameter block for this call (the core keeps its own), and -- when it requires grad -- receives the
+    gradient summed over drones.  Reading its 18 floats to the host is a SYNCHRONISATION when it lives on the device."""
+    actions, K, a_stride = core._action_blocks(actions, num_steps)
+    tape_floats_pid(core, K)                                   # (the configuration check, with the library's message, before anything else)
+    if core.plant_rows is not None:
+        raise _native.GpdError("rollout_diff_pid: the DSLPID sweep flies the nominal airframe only; a per-drone plant table is set "
+                               "(set_plant(None) removes it)")
+    # what the size query cannot see and gpd_rollout_tape_pid would refuse only after kin0 / pid0 have been copied into the core's state
+    if core.pid is None or core._params.pid_kf <= 0.0:
+        raise _native.GpdError("rollout_diff_pid: this core has no DSLPID controller (no controller members, or an airframe without one)")
+    if core._state.dw_force:
+        raise _native.GpdError("rollout_diff_pid: downwash computed outside the kernel (state.dw_force) is not differentiable")
+    if kin0 is None:
+        kin0 = core.kin_store.detach()
+    else:
+        if kin0.numel() != 13 * core.ld:
+            raise ValueError(f"kin0 has {kin0.numel()} elements, expected 13 x ld = {13 * core.ld} (the plane layout: pack_kin)")
+        kin0 = kin0.to(device=core.device, dtype=torch.float32).reshape(-1).contiguous()
+    if pid0 is None:
+        pid0 = core.pid.detach()
+    else:
+        if pid0.numel() != 9 * core.ld:
+            raise ValueError(f"pid0 has {pid0.numel()} elements, expected 9 x ld = {9 * core.ld} (the rows of the controller members: pack_pid)")
+        pid0 = pid0.to(device=core.device, dtype=torch.float32).reshape(9, core.ld).contiguous()
+    if pid_gains is not None:
+        if not isinstance(pid_gains, torch.Tensor) or pid_gains.numel() != 18:
+            raise ValueError("pid_gains must be a tensor of 6 x 3 gains (rows: p_for, i_for, d_for, p_tor, i_tor, d_tor)")
+    return RolloutDiffPid.apply(core, kin0, pid0, actions, K, a_stride, pid_gains)

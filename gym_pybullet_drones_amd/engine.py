@@ -435,6 +435,19 @@ class SimCore:
         from . import diff
         return diff.rollout_diff(self, actions, kin0, num_steps, plant_scales)
 
+    def rollout_diff_pid(self, actions: torch.Tensor, kin0: torch.Tensor = None, pid0: torch.Tensor = None, num_steps: int = None,
+                         pid_gains: torch.Tensor = None):
+        """`rollout_diff()` for the action types that close the loop in the kernel -- PID, VEL, ONE_D_PID -- (`diff.rollout_diff_pid`:
+        `gpd_rollout_tape_pid` forward, `gpd_rollout_vjp_pid` backward).  Returns fresh tensors `(obs12 [K,N,12], reward [K,E],
+        kin_K [13*ld], pid_K [9,ld], terminated [K,E], truncated [K,E])`; the first four carry gradients with respect to `actions`,
+        `kin0`, `pid0` (None: the core's own; `kin_K` / `pid_K` of one call as `kin0` / `pid0` of the next chains the graph) and
+        `pid_gains`: a `[6, 3]` tensor (rows p_for, i_for, d_for, p_tor, i_tor, d_tor) that replaces the controller's gains for this
+        call and receives the gradient summed over drones; None: the core's gains, no gain gradient.  Reading the 18 gains to the
+        host is a synchronisation when the tensor lives on the device.  Single-drone aviaries, CF2X / CF2P, no add-on physics or
+        drag, no plant table, no auto-reset: GpdError otherwise."""
+        from . import diff
+        return diff.rollout_diff_pid(self, actions, kin0, pid0, num_steps, pid_gains)
+
     def _fixed_args(self):
         """the arguments of gpd_step / gpd_rollout* that never change between two calls, as ctypes objects (set_target() drops them)"""
         self._step_args = tuple(_native.as_c(x) for x in (self._params, self._state, self._cfg, self.target, self.init_pose, self.obs12,

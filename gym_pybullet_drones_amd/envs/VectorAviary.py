@@ -181,6 +181,16 @@ class VectorAviary:
         obs, reward, kin_k, terminated, truncated = self.core.rollout_diff(actions, kin0, plant_scales=plant_scales)
         return obs.view(-1, self.NUM_ENVS, self.NUM_DRONES, 12), reward, kin_k, terminated, truncated
 
+    def rollout_diff_pid(self, actions: torch.Tensor, kin0: torch.Tensor = None, pid0: torch.Tensor = None, num_steps: int = None,
+                         pid_gains: torch.Tensor = None):
+        """The differentiable rollout through the DSLPID loop (`SimCore.rollout_diff_pid`; PID, VEL and ONE_D_PID aviaries): actions
+        (K, E, 1, A) -> (obs12 (K,E,1,12), reward (K,E), kin_K [13*ld], pid_K [9,ld], terminated (K,E), truncated (K,E)); the first four
+        carry gradients with respect to `actions`, `kin0`, `pid0` (the controller members, `diff.pack_pid`; None: the current ones)
+        and `pid_gains` ([6, 3]: replaces the controller's gains for this call -- reading it to the host synchronises -- and receives
+        the gradient summed over drones)."""
+        obs, reward, kin_k, pid_k, terminated, truncated = self.core.rollout_diff_pid(actions, kin0, pid0, num_steps, pid_gains)
+        return obs.view(-1, self.NUM_ENVS, self.NUM_DRONES, 12), reward, kin_k, pid_k, terminated, truncated
+
     def rollout_policy(self, policy, num_steps: int, noise: torch.Tensor = None, action_std=None, mean_out: torch.Tensor = None):
         """K env steps in ONE launch with the policy in the loop (`policy.MlpPolicy`; the loop of
         `examples/learn.py:157-192`).  The policy's input is the (12,) kinematic row, or -- `full_obs` True / "lazy" and

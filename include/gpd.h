@@ -1021,6 +1021,63 @@ int gpd_rollout_vjp_plant(const GpdParams* params, const GpdStepCfg* cfg, int64_
 int gpd_plant_derive_vjp(const GpdParams* nominal, const float* scales, const float* g_rows, int32_t n, int64_t ld, float* g_scales,
                          void* stream);
 
+/*
+ * The differentiable rollout through the DSLPID loop (additions to ABI 9): the three entries above for the action types that close the
+ * loop in the kernel -- GPD_ACT_PID, GPD_ACT_VEL, GPD_ACT_ONE_D_PID -- with the nine controller members (GpdState.pid: integral
+ * position error | last rpy | integral rpy error) as a differentiable input and output, and the cotangents of the 18 controller gains.
+ * Policy gradients for set-point policies, waypoint optimisation with the controller in the loop, tuning the controller by
+ * back-propagation through the flight.  The reference has no counterpart.  gpd_rollout_tape / gpd_rollout_vjp keep refusing these
+ * action types.
+ *
+ * gpd_rollout_tape_pid is gpd_rollout for these action types plus a record of what the sweep needs.  Whatever it leaves behind --
+ * state, state.pid, last_rpm, step_counter, bad, obs12, reward and flags -- is bit for bit what gpd_rollout leaves on the same inputs
+ * (the same load_carry / map_action / env_step / store_carry code).  The tape is opaque, 16-byte aligned,
+ * gpd_rollout_tape_pid_floats(cfg, num_steps, state.ld) floats: the 13 kinematic floats and the nine members every env step starts
+ * from, 22 floats = 88 B per drone-step.  The cached roll / pitch / yaw the controller reads are not taped: they are the Euler
+ * extraction of the step's start quaternion in every kernel, and the sweep recomputes them with the same instructions.
+ *
+ * gpd_rollout_vjp_pid is the vector-Jacobian product of (kin_0, pid_0, a_0 .. a_K-1, the 18 gains) -> (kin_K, pid_K, obs12_0 ..,
+ * reward_0 ..) of that call:
+ *   ld, num_steps, actions, action_step_stride, target_pos   what the taped call was given (ld = state.ld)
+ *   g_obs12, g_reward   cotangents of the outputs, laid out like them; NULL = zeros
+ *   g_kin               [13*ld], the four-plane layout of GpdState.kin, IN PLACE: the final state's cotangent on entry, the initial
+ *                       state's on return.  16-byte aligned
+ *   g_pid               [9][ld], the rows of GpdState.pid, IN PLACE in the same way.  16-byte aligned
+ *   g_actions           [K][N][A] out (A = 3, 4, 1), ALWAYS one block per step, also for a shared action block.  16-byte aligned for
+ *                       GPD_ACT_VEL (its rows are stored as float4)
+ *   g_gains             NULL, or [18][ld] out, 16-byte aligned, drones 0 .. N-1 of every row overwritten: PER DRONE, the cotangents of
+ *                       p_for[3] | i_for[3] | d_for[3] | p_tor[3] | i_tor[3] | d_tor[3] of GpdParams, summed over the steps in
+ *                       registers and stored once after the loop (the forward's gains are shared: the caller sums over drones).
+ *                       g_kin, g_pid and g_actions do not depend by a bit on whether it is given
+ * One lane per drone, steps K-1 .. 0, the 13 + 9 cotangents in registers; the sub-steps are undone as in gpd_rollout_vjp.  No atomics:
+ * two calls give the same bits.  The adjoint is that of the function as executed -- a select differentiates the branch taken, a clamp
+ * passes its cotangent on lo <= x <= hi and nothing outside:
+ *   the target mappings   PID: inside the 1 m approach limit the target is the action, outside it p + d/|d| (Jacobian (I - dd^T)/|d|
+ *                         towards the action, I minus that towards the position); VEL: speed_limit |a_w| a_xyz/|a_xyz| (exactly zero
+ *                         at a_xyz = 0), target yaw = the current yaw; ONE_D_PID: 0.1 a + p_z
+ *   the position loop     the errors, the three integrators with their clamps (z nested), max(0, .) of the thrust along body z with
+ *                         the square root's derivative selected to 0 there, the two normalisations, the cross products, sincos(yaw)
+ *   the attitude loop     e_R of R(q) and R*, the finite difference of the Euler angles (it reaches this step's rpy and the last
+ *                         rpy, i.e. the previous step), the rate integrators with their clamps, the +-3200 torque clamps, the mixer,
+ *                         the PWM clamp, pwm -> rpm, the rotor thrusts
+ *   R(q) and rpy(q)       of the step's start state, into the quaternion's cotangent
+ * Targets of the task, the mixer, the PWM constants and the target rpy and rates are constants of the sweep.
+ *
+ * Supported: drones_per_env == 1; the three DSLPID action types; CF2X and CF2P; GPD_TASK_NONE and GPD_TASK_HOVER; physics_flags == 0;
+ * auto_reset == 0; no plant table.  GPD_ENOTSUP, before any device work and with a message that names the entry and the reason: the RPM
+ * action types (gpd_rollout_tape / gpd_rollout_vjp serve them), any physics flag (drag included), D > 1, GPD_TASK_MULTIHOVER,
+ * auto_reset, state.dw_force, an airframe without DSLPID (pid_kf <= 0).  GPD_EINVAL: NULL pointers, a missing state.pid, misaligned
+ * kin / g_kin / g_pid / g_gains / tape (and g_actions under GPD_ACT_VEL), bad strides or sizes.  GPD_ERANGE: more than 2^26 drones.
+ */
+int gpd_rollout_tape_pid_floats(const GpdStepCfg* cfg, int32_t num_steps, int64_t ld, int64_t* floats_out);
+int gpd_rollout_tape_pid(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, int32_t num_steps, const float* actions,
+                         int64_t action_step_stride, const float* target_pos, float* obs12, int64_t obs_step_stride, float* reward,
+                         uint8_t* terminated, uint8_t* truncated, int64_t env_step_stride, float* tape, void* stream);
+int gpd_rollout_vjp_pid(const GpdParams* params, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, const float* actions,
+                        int64_t action_step_stride, const float* target_pos, const float* tape, const float* g_obs12,
+                        int64_t obs_step_stride, const float* g_reward, int64_t env_step_stride, float* g_kin, float* g_pid,
+                        float* g_actions, float* g_gains, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

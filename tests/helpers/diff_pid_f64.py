@@ -1,0 +1,295 @@
+"""The yardstick of the differentiable rollout through the DSLPID loop (tests/test_host_diff_pid.py, tests/test_gpu_diff_pid.py): a torch
+restatement of the three target mappings (envs/BaseRLAviary.py:196-239, envs/BaseAviary.py:1132-1150) and of
+`DSLPIDControl.computeControl` (control/DSLPIDControl.py:82-259) on top of `diff_f64`'s `substep` / `euler` /
+`rotation`.  Dtype-generic; in float64 under autograd it is the reference the device gradients are held against, and its forward is held
+against `oracle.batched_oracle` (1e-12).  Every clip is `torch.clamp` (the gradient passes on lo <= x <= hi), every select is NaN-safe
+(the operands of an untaken branch are replaced by harmless ones first).  The nine controller members -- integral position error, last
+rpy, integral rpy error -- are carried from step to step.
+
+`stats` (a dict) records, over every drone-step of a run, the smallest RELATIVE distance to each select threshold of the controller and
+the mappings (`near[...]`), and how many drone-steps sat on either side of the two clamps the saturated cases are about.
+
+The same file holds the input generator and the cases of the GPU tests.  Test infrastructure."""
+import math
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+import diff_f64 as ref
+
+ACT_DIM = {"pid": 3, "vel": 4, "one_d_pid": 1}
+ACT_CODE = {"pid": 1, "vel": 2, "one_d_pid": 4}
+#: rows of the gains tensor [6, 3], the order of `g_gains` (include/gpd.h gpd_rollout_vjp_pid)
+GAINS = ("p_for", "i_for", "d_for", "p_tor", "i_tor", "d_tor")
+DEFAULT_GAINS = np.array([[.4, .4, 1.25], [.05, .05, .05], [.2, .2, .5], [70000., 70000., 60000.], [.0, .0, 500.], [20000., 20000., 12000.]])
+#: the RL aviaries fly the CF2X controller whatever the airframe (envs/BaseRLAviary.py:75-76)
+MIXER_CF2X = np.array([[-.5, -.5, -1], [-.5, .5, 1], [.5, .5, -1], [.5, -.5, 1]])
+PWM2RPM_SCALE, PWM2RPM_CONST, MIN_PWM, MAX_PWM = 0.2685, 4070.3, 20000.0, 65535.0
+KIN_GROUPS = ("pos", "quat", "vel", "rates")
+PID_GROUPS = ("int_pos", "last_rpy", "int_rpy")
+GROUPS = ("actions",) + KIN_GROUPS + PID_GROUPS + GAINS
+
+
+def pid_consts(gravity, kf, speed_limit, gains=None, dtype=torch.float64):
+    """the controller's constants: `gravity` = g M and `kf` of the CONTROLLER's airframe, the VEL mapping's speed limit, the gains
+    [6, 3] (default: the reference's; a tensor may be an autograd leaf -- it is cast to `dtype` inside the graph)"""
+    g = torch.as_tensor(DEFAULT_GAINS if gains is None else gains)
+    return SimpleNamespace(gravity=float(gravity), kf=float(kf), speed_limit=float(speed_limit), gains=g.to(dtype),
+                           mixer=torch.as_tensor(MIXER_CF2X, dtype=dtype))
+
+
+def pid_consts_of(C, gains=None, dtype=torch.float64):
+    """... of an airframe `C` (`DroneParams`) flown by the CF2X controller, as `SimCore` builds it"""
+    from gym_pybullet_drones_amd.params import DroneParams
+    from gym_pybullet_drones_amd.utils.enums import DroneModel
+    cp = C if C.DRONE_MODEL == DroneModel.CF2X else DroneParams(DroneModel.CF2X)
+    return pid_consts(9.8 * cp.M, cp.KF, C.SPEED_LIMIT, gains, dtype)
+
+
+def _near(stats, key, dist):
+    if stats is not None:
+        near = stats.setdefault("near", {})
+        near[key] = min(near.get(key, math.inf), float(dist.detach().min()))
+
+
+def _count(stats, key, mask):
+    if stats is not None:
+        stats[key] = stats.get(key, 0) + int(mask.sum())
+
+
+def controller(pc, dt, e_p, vel, R, rpy, tyaw, tvel, mem, stats=None):
+    """one call of computeControl from the position error `e_p` = target - position [n, 3]: R = rows-of-columns list R[i][j] of [n]
+    (ref.rotation), rpy [n, 3] the cached Euler angles, `mem` = (integral position error, last rpy, integral rpy error) each [n, 3]
+    -> (rpm [n, 4], the members after the call)"""
+    ip, lrpy, ir = mem
+    P_FOR, I_FOR, D_FOR, P_TOR, I_TOR, D_TOR = pc.gains.unbind(0)
+    e_v = tvel - vel
+    u = ip + e_p * dt
+    acc = torch.clamp(u, -2.0, 2.0)
+    accz = torch.clamp(acc[:, 2], -0.15, 0.15)
+    _near(stats, "int_pos_2", (u.abs() - 2.0).abs() / 2.0)
+    _near(stats, "int_pos_z_0.15", (u[:, 2].abs() - 0.15).abs() / 0.15)
+    _count(stats, "int_z_saturated", u[:, 2].abs() > 0.15)
+    _count(stats, "int_z_free", u[:, 2].abs() <= 0.15)
+    ip = torch.stack([acc[:, 0], acc[:, 1], accz], dim=-1)
+    f = P_FOR * e_p + I_FOR * ip + D_FOR * e_v
+    f = torch.stack([f[:, 0], f[:, 1], f[:, 2] + pc.gravity], dim=-1)
+    dot = f[:, 0] * R[0][2] + f[:, 1] * R[1][2] + f[:, 2] * R[2][2]
+    fnorm = torch.sqrt((f * f).sum(-1))
+    _near(stats, "along_0", dot.abs() / fnorm)
+    up = dot > 0
+    sq = torch.where(up, torch.sqrt(torch.where(up, dot, torch.ones_like(dot)) / (4 * pc.kf)), torch.zeros_like(dot))
+    base_pwm = (sq - PWM2RPM_CONST) / PWM2RPM_SCALE
+    zb = f / fnorm[:, None]
+    heading = torch.stack([torch.cos(tyaw), torch.sin(tyaw), torch.zeros_like(tyaw)], dim=-1)
+    yb = torch.cross(zb, heading, dim=-1)
+    yb = yb / torch.sqrt((yb * yb).sum(-1))[:, None]
+    xb = torch.cross(yb, zb, dim=-1)
+    Rd = (xb, yb, zb)                                               # columns
+    col = lambda j: torch.stack([R[0][j], R[1][j], R[2][j]], dim=-1)     # noqa: E731
+    m = lambda i, j: (Rd[i] * col(j)).sum(-1)     # noqa: E731           (Rd^T R)_ij
+    e_R = torch.stack([m(2, 1) - m(1, 2), m(0, 2) - m(2, 0), m(1, 0) - m(0, 1)], dim=-1)
+    e_w = -(rpy - lrpy) / dt                                        # (target rpy rates: zero)
+    w = ir - e_R * dt
+    acc_r = torch.clamp(w, -1500.0, 1500.0)
+    acc_xy = torch.clamp(acc_r[:, 0:2], -1.0, 1.0)
+    _near(stats, "int_rpy_1500", (w.abs() - 1500.0).abs() / 1500.0)
+    _near(stats, "int_rpy_xy_1", (w[:, 0:2].abs() - 1.0).abs())
+    ir = torch.cat([acc_xy, acc_r[:, 2:3]], dim=-1)
+    tau_raw = -P_TOR * e_R + D_TOR * e_w + I_TOR * ir
+    _near(stats, "torque_3200", (tau_raw.abs() - 3200.0).abs() / 3200.0)
+    tau = torch.clamp(tau_raw, -3200.0, 3200.0)
+    pwm_raw = base_pwm[:, None] + tau @ pc.mixer.t()
+    _near(stats, "pwm_limits", torch.minimum((pwm_raw - MIN_PWM).abs() / MIN_PWM, (pwm_raw - MAX_PWM).abs() / MAX_PWM))
+    _count(stats, "pwm_saturated", (pwm_raw < MIN_PWM) | (pwm_raw > MAX_PWM))
+    _count(stats, "pwm_free", (pwm_raw >= MIN_PWM) & (pwm_raw <= MAX_PWM))
+    if stats is not None:
+        stats["all_pwm_clipped"] = stats.get("all_pwm_clipped", 0) + int(((pwm_raw < MIN_PWM) | (pwm_raw > MAX_PWM)).all(-1).sum())
+    pwm = torch.clamp(pwm_raw, MIN_PWM, MAX_PWM)
+    return PWM2RPM_SCALE * pwm + PWM2RPM_CONST, (ip, rpy, ir)
+
+
+def targets(pc, cfg, pos, yaw, act, stats=None):
+    """the action type's mapping: -> (position error = target position - position [n, 3], target yaw [n], target velocity [n, 3]).
+    The error is formed directly: the VEL and ONE_D_PID targets ARE the position (plus 0.1 a in z), so the error does not depend on
+    it -- written as `(pos + x) - pos` the two cotangents cancel only up to the rounding of whatever else the position's gradient
+    holds, which costs a float32 run of this restatement four digits of a small gradient and says nothing about the function."""
+    zero = torch.zeros_like(pos)
+    if cfg.act == "pid":                        # a waypoint, approached in steps of at most 1 m
+        d = act - pos
+        n2 = (d * d).sum(-1)
+        far = n2 > 1.0
+        n = torch.sqrt(torch.where(far, n2, torch.ones_like(n2)))
+        _near(stats, "approach_1m", (torch.sqrt(n2) - 1.0).abs())
+        _count(stats, "beyond_1m", far)
+        _count(stats, "within_1m", ~far)
+        return torch.where(far[:, None], d / n[:, None], d), torch.zeros_like(yaw), zero
+    if cfg.act == "vel":                        # a direction and a fraction of the speed limit; the yaw is kept, the position is the target
+        a3 = act[:, 0:3]
+        n2 = (a3 * a3).sum(-1)
+        moving = n2 != 0
+        n = torch.sqrt(torch.where(moving, n2, torch.ones_like(n2)))
+        unit = torch.where(moving[:, None], a3 / n[:, None], zero)
+        return zero, yaw, pc.speed_limit * act[:, 3:4].abs() * unit
+    z = torch.zeros_like(act[:, 0])             # one_d_pid: 0.1 a above the position
+    return torch.stack([z, z, 0.1 * act[:, 0]], dim=-1), torch.zeros_like(yaw), zero
+
+
+def step(c, pc, cfg, kin, mem, act, target=None, stats=None):
+    """one env step: -> kin', the members after it, obs12 [n, 12], reward [n]"""
+    pos, quat, vel, _ = kin
+    R = ref.rotation(quat)
+    rpy = ref.euler(quat, stats)                # the cached Euler angles: those of the step's start state
+    e_p, tyaw, tvel = targets(pc, cfg, pos, rpy[:, 2], act, stats)
+    rpm, mem = controller(pc, cfg.S * cfg.h, e_p, vel, R, rpy, tyaw, tvel, mem, stats)
+    ang_v = None
+    nothing = torch.zeros_like(pos[:, 0])
+    for _s in range(cfg.S):
+        kin, ang_v = ref.substep(c, cfg, kin, rpm, nothing, stats)
+    pos, quat, vel, _ = kin
+    obs = torch.cat([pos, ref.euler(quat, stats), vel, ang_v], dim=-1)
+    if cfg.task == "hover":
+        d2 = ((target - pos) ** 2).sum(-1)
+        arg = 2.0 - d2 * d2
+        if stats is not None:
+            stats["reward_arg_min"] = min(stats.get("reward_arg_min", math.inf), float(arg.detach().min()))
+        reward = torch.where(arg > 0, arg, torch.zeros_like(arg))
+    else:
+        reward = -torch.ones_like(pos[:, 0])
+    return kin, mem, obs, reward
+
+
+def rollout(c, pc, cfg, kin0, mem0, actions, target=None, stats=None):
+    """K steps: actions [K, n, A] -> obs12 [K, n, 12], reward [K, n], kin_K, the members after the last step"""
+    kin, mem, obs, rew = kin0, mem0, [], []
+    for t in range(actions.shape[0]):
+        kin, mem, o, r = step(c, pc, cfg, kin, mem, actions[t], target, stats)
+        obs.append(o)
+        rew.append(r)
+    return torch.stack(obs), torch.stack(rew), kin, mem
+
+
+# ---- the inputs of the GPU tests --------------------------------------------------------------------------------------------------
+#: the gradient cases of tests/test_gpu_diff_pid.py: 70 drones (ld = 128), task hover.  `kind` selects the targets (`make_inputs`).
+GPU_CASES = {
+    "vel_k8_s5": dict(model="cf2x", act="vel", S=5, K=8, kind="plain", seed=1),
+    "pid_k8_s5": dict(model="cf2x", act="pid", S=5, K=8, kind="plain", seed=175),
+    "one_d_k6_s8": dict(model="cf2x", act="one_d_pid", S=8, K=6, kind="plain", seed=534),
+    "cf2p_vel_k6_s5": dict(model="cf2p", act="vel", S=5, K=6, kind="plain", seed=7),
+    "sat_int_k10_s5": dict(model="cf2x", act="pid", S=5, K=10, kind="sat_int", seed=472),
+    "sat_pwm_k4_s5": dict(model="cf2x", act="vel", S=5, K=4, kind="sat_pwm", seed=59),
+}
+# The seeds were chosen on the CPU, by this file alone: among the generator's draws, one whose float32 run of the restatement stays
+# within 1e-5 of its float64 run in every group and whose drone-steps all keep 1e-3 (relative) from every select threshold
+# (tests/test_host_diff_pid.py asserts both).  With 70 drones, up to 10 steps and a dozen thresholds -- the +-3200 torque clamps are
+# crossed all the time in ordinary flight -- about one draw in five to fifty does.  Among those, the two long cases at a low control rate
+# (one_d_k6_s8, sat_int_k10_s5) take the draw whose float32 FORWARD stays closest to the float64 one: the observed angular velocity of the
+# closed loop carries the rounding of the Euler-angle difference times d_tor x the control rate, and a plain float32 run of this
+# restatement is 5e-5 .. 6e-4 (absolute, rad/s) from the float64 run after 6 .. 10 steps, whatever evaluates it.
+
+
+#: the shared-action test flies the first block of "vel_k8_s5"'s generator at every step; its seed was chosen by the same two rules
+SHARED_SEED = 5
+
+
+def case(name):
+    """(cfg, K, kind, seed) of a GPU case"""
+    d = dict(GPU_CASES[name])
+    K, kind, seed = d.pop("K"), d.pop("kind"), d.pop("seed")
+    return ref.config(d["model"], d["act"], d["S"], False, "hover"), K, kind, seed
+
+
+def make_inputs(C, cfg, n, K, seed=0, kind="plain"):
+    """Every value representable in float32 (both precisions start from the same numbers).  A drone near hover whose controller is in
+    its linear range: positions within +-0.15 m of (0, 0, 1), attitudes within +-0.01 rad, velocities +-0.1 m/s, body rates +-0.05 rad/s,
+    the last rpy within 2e-4 rad of the attitude, integral position errors +-0.05, integral rpy errors +-0.3; random cotangents for every
+    output.  Actions by action type and `kind`:
+      pid        waypoints at 0.05 .. 0.3 m from the drone, and for every third drone 1.2 .. 2 m (beyond the 1 m approach limit)
+      vel        a random direction, speed fraction +-(0.1 .. 0.5)
+      one_d_pid  U(-1, 1)
+      "sat_int"  pid waypoints whose z error makes the +-0.15 clamp of the z integrator engage for every fourth drone (integral z
+                 error 0.13 .. 0.148 carried in and a waypoint 0.15 .. 0.2 m above: the clamp engages within a few steps and stays
+                 engaged); the others carry 0.02 .. 0.08 and cannot reach it (z errors of +-0.2 m move the integral by 0.04 in 10 steps)
+      "sat_pwm"  vel commands upwards at full speed fraction to a drone that descends at 0.2 .. 1 m/s: the thrust the velocity error
+                 asks for (d_for_z = 0.5 N per m/s against a hover thrust of 0.26 N and a ceiling of 2.25 times that) pushes the
+                 rotors of part of the drones to MAX_PWM"""
+    rng = np.random.default_rng(seed)
+    f32 = lambda x: np.asarray(x, dtype=np.float32).astype(np.float64)     # noqa: E731
+    A = ACT_DIM[cfg.act]
+    pos = f32(np.array([0.0, 0.0, 1.0]) + rng.uniform(-0.15, 0.15, (n, 3)))
+    rpy0 = rng.uniform(-0.01, 0.01, (n, 3))
+    vel = f32(rng.uniform(-0.1, 0.1, (n, 3)))
+    rates = f32(rng.uniform(-0.05, 0.05, (n, 3)))
+    int_pos = f32(rng.uniform(-0.05, 0.05, (n, 3)))
+    int_rpy = f32(rng.uniform(-0.3, 0.3, (n, 3)))
+    if kind == "sat_pwm":
+        vel[:, 2] = f32(-rng.uniform(0.2, 1.0, n))
+    quat = f32(ref.quat_from_rpy(rpy0))
+    last_rpy = f32(rpy0 + rng.uniform(-2e-4, 2e-4, (n, 3)))
+    if cfg.act == "pid":
+        direction = rng.standard_normal((K, n, 3))
+        direction /= np.linalg.norm(direction, axis=-1, keepdims=True)
+        dist = rng.uniform(0.05, 0.3, (K, n, 1))
+        dist[:, ::3] = rng.uniform(1.2, 2.0, (K, (n + 2) // 3, 1))
+        a = pos[None] + direction * dist
+        if kind == "sat_int":
+            ez = rng.uniform(-0.2, 0.2, (1, n, 1))
+            int_pos[:, 2] = f32(rng.uniform(0.02, 0.08, n))
+            int_pos[::4, 2] = f32(rng.uniform(0.13, 0.148, (n + 3) // 4))
+            ez[:, ::4] = rng.uniform(0.15, 0.2, (1, (n + 3) // 4, 1))
+            a = pos[None] + np.concatenate([rng.uniform(-0.05, 0.05, (K, n, 2)), np.broadcast_to(ez, (K, n, 1))], axis=-1)
+    elif cfg.act == "vel":
+        direction = rng.standard_normal((K, n, 3))
+        direction /= np.linalg.norm(direction, axis=-1, keepdims=True)
+        frac = rng.uniform(0.1, 0.5, (K, n, 1)) * rng.choice([-1.0, 1.0], (K, n, 1))
+        if kind == "sat_pwm":
+            frac = rng.uniform(0.9, 1.0, (K, n, 1))
+            direction[..., 2] = np.abs(direction[..., 2])
+        a = np.concatenate([direction, frac], axis=-1)
+    else:
+        a = rng.uniform(-1.0, 1.0, (K, n, 1))
+    return SimpleNamespace(n=n, K=K, A=A, pos=pos, quat=quat, vel=vel, rates=rates, int_pos=int_pos, last_rpy=last_rpy, int_rpy=int_rpy,
+                           actions=f32(a), last_rpm=np.zeros((n, 4)), target=np.tile(np.array([0.0, 0.0, 1.0]), (n, 1)),
+                           g_obs=f32(rng.standard_normal((K, n, 12))), g_rew=f32(rng.standard_normal((K, n))),
+                           g_pos=f32(rng.standard_normal((n, 3))), g_quat=f32(rng.standard_normal((n, 4))),
+                           g_vel=f32(rng.standard_normal((n, 3))), g_rates=f32(rng.standard_normal((n, 3))),
+                           g_int_pos=f32(rng.standard_normal((n, 3))), g_last_rpy=f32(rng.standard_normal((n, 3))),
+                           g_int_rpy=f32(rng.standard_normal((n, 3))))
+
+
+def loss_of(inp, T, obs, rew, kin_k, mem_k, g_obs=True):
+    """sum(cotangent * output) over reward, the final state, the final members and -- `g_obs` -- the observations"""
+    total = (T(inp.g_rew) * rew).sum()
+    total = total + sum((T(g) * k).sum() for g, k in zip((inp.g_pos, inp.g_quat, inp.g_vel, inp.g_rates), kin_k))
+    total = total + sum((T(g) * k).sum() for g, k in zip((inp.g_int_pos, inp.g_last_rpy, inp.g_int_rpy), mem_k))
+    return total + (T(inp.g_obs) * obs).sum() if g_obs else total
+
+
+def reference_grads(C, cfg, inp, dtype=torch.float64, shared_action=False, stats=None, gains=None):
+    """Gradients of `loss_of` with respect to the actions, the four groups of the initial state, the three groups of the initial
+    members and the six gain vectors, by torch autograd over the restatement: dict of numpy float64 arrays (GROUPS).  `shared_action`:
+    actions[0] at every step.  `gains` [6, 3]: default the reference's."""
+    T = lambda v: torch.as_tensor(v, dtype=dtype)     # noqa: E731
+    leaf = lambda v: T(v).clone().requires_grad_(True)     # noqa: E731
+    kin0 = tuple(leaf(v) for v in (inp.pos, inp.quat, inp.vel, inp.rates))
+    mem0 = tuple(leaf(v) for v in (inp.int_pos, inp.last_rpy, inp.int_rpy))
+    a = leaf(inp.actions[0:1] if shared_action else inp.actions)
+    g = torch.as_tensor(DEFAULT_GAINS if gains is None else gains, dtype=torch.float64).clone().requires_grad_(True)
+    c = ref.consts(C, inp.n, dtype)
+    pc = pid_consts_of(C, g, dtype)
+    acts = a.expand(inp.K, -1, -1) if shared_action else a
+    obs, rew, kin_k, mem_k = rollout(c, pc, cfg, kin0, mem0, acts, T(inp.target), stats)
+    grads = torch.autograd.grad(loss_of(inp, T, obs, rew, kin_k, mem_k), (a,) + kin0 + mem0 + (g,), allow_unused=True)
+    leaves = (a,) + kin0 + mem0
+    out = {k: (torch.zeros_like(x) if gr is None else gr).detach().to(torch.float64).numpy() for k, gr, x in zip(GROUPS[:8], grads[:8], leaves)}
+    gg = (torch.zeros_like(g) if grads[8] is None else grads[8]).detach().numpy()
+    for i, name in enumerate(GAINS):
+        out[name] = gg[i]
+    out["forward"] = (obs.detach(), rew.detach(), tuple(k.detach() for k in kin_k), tuple(m.detach() for m in mem_k))
+    return out
+
+
+def group_errors(got, want):
+    """max |g - g64| / max |g64| per group (the metric of the tests)"""
+    return {k: float(np.abs(np.asarray(got[k], dtype=np.float64) - want[k]).max() / max(float(np.abs(want[k]).max()), 1e-300)) for k in GROUPS}
