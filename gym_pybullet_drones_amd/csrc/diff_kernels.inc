@@ -14,6 +14,8 @@
 // The adjoint is that of the function AS EXECUTED: a select differentiates the branch taken (the `turn` test of the quaternion update,
 // the gimbal fix-up of quat_to_rpy, the clip of GPD_ACT_RAW_RPM, max(0, .) of the reward).  The cos / sinc polynomials of the quaternion
 // exponential are differentiated as the polynomials they are (the exact path beyond |t| = 1 rad as cos / sinc).
+// The DSLPID sweep (diff_pid_kernels.inc) stands on the same core, which lives here once: the plane and member-row traffic, the taped
+// forwards' lane and stores, rpy_vjp / mat_vjp, outputs_vjp, and the entries' checks and prologues.
 #include "plant_derive_vjp.inc"
 
 namespace {
@@ -21,29 +23,72 @@ namespace {
 __device__ __forceinline__ float norm_thrust_of(const GpdParams& P) { return P.hover_thrust; }
 __device__ __forceinline__ float norm_thrust_of(const PlantParams& P) { return P.norm_thrust; }
 
-// one drone's 13 floats from / to a block in the plane layout (GpdState.kin, a tape step, the cotangent block)
-__device__ __forceinline__ Kin planes_load(const float* __restrict__ base, int64_t ld, uint32_t n) {
+// One drone's 13 floats from / to three planes of float4[ld] (P | Q | V, as in GpdState.kin) and the row of body rate z: a block in the
+// plane layout (kin_load / kin_store: GpdState.kin, a step of the RPM tape, the cotangent block) or the planes of the DSLPID tape.
+__device__ __forceinline__ Kin planes_load(const float* __restrict__ P, const float* __restrict__ Q, const float* __restrict__ V,
+                                           const float* __restrict__ wz, uint32_t n) {
     const uint32_t off16 = n * 16u;
-    const f4v p = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(base) + off16);
-    const f4v q = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(base + 4 * ld) + off16);
-    const f4v v = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(base + 8 * ld) + off16);
+    const f4v p = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(P) + off16);
+    const f4v q = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(Q) + off16);
+    const f4v v = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(V) + off16);
     Kin k;
     k.px = p.x; k.py = p.y; k.pz = p.z; k.wx = p.w;
     k.qx = q.x; k.qy = q.y; k.qz = q.z; k.qw = q.w;
     k.vx = v.x; k.vy = v.y; k.vz = v.z; k.wy = v.w;
-    k.wz = ld_row(base, ld, 12, n * 4u);
+    k.wz = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(wz) + n * 4u);
     return k;
 }
-__device__ __forceinline__ void planes_store(float* __restrict__ base, int64_t ld, uint32_t n, const Kin& k) {
+__device__ __forceinline__ void planes_store(float* __restrict__ P, float* __restrict__ Q, float* __restrict__ V, float* __restrict__ wz,
+                                             uint32_t n, const Kin& k) {
     const uint32_t off16 = n * 16u;
     // (opaque copies, as in store_carry: the field reads must not be combined into vector loads of the struct)
     float e0 = k.px, e1 = k.py, e2 = k.pz, e3 = k.wx, e4 = k.qx, e5 = k.qy, e6 = k.qz, e7 = k.qw, e8 = k.vx, e9 = k.vy, e10 = k.vz, e11 = k.wy;
     asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3), "+v"(e4), "+v"(e5), "+v"(e6), "+v"(e7), "+v"(e8), "+v"(e9), "+v"(e10), "+v"(e11));
     const f4v p = {e0, e1, e2, e3}, q = {e4, e5, e6, e7}, v = {e8, e9, e10, e11};
-    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(base) + off16) = p;
-    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(base + 4 * ld) + off16) = q;
-    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(base + 8 * ld) + off16) = v;
-    st_row(base, ld, 12, n * 4u, k.wz);
+    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(P) + off16) = p;
+    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(Q) + off16) = q;
+    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(V) + off16) = v;
+    *reinterpret_cast<float*>(reinterpret_cast<char*>(wz) + n * 4u) = k.wz;
+}
+__device__ __forceinline__ Kin kin_load(const float* __restrict__ base, int64_t ld, uint32_t n) {
+    return planes_load(base, base + 4 * ld, base + 8 * ld, base + 12 * ld, n);
+}
+__device__ __forceinline__ void kin_store(float* __restrict__ base, int64_t ld, uint32_t n, const Kin& k) {
+    planes_store(base, base + 4 * ld, base + 8 * ld, base + 12 * ld, n, k);
+}
+// The nine controller members from / to nine rows of float[ld], by name: Pid (GpdState.pid, the DSLPID tape) and GpdDslOutCot (g_pid)
+// spell them alike.
+template <class M>
+__device__ __forceinline__ void members_load(const float* __restrict__ rows, int64_t ld, uint32_t off4, M& s) {
+    s.ipx = ld_row(rows, ld, 0, off4); s.ipy = ld_row(rows, ld, 1, off4); s.ipz = ld_row(rows, ld, 2, off4);
+    s.lr = ld_row(rows, ld, 3, off4); s.lp = ld_row(rows, ld, 4, off4); s.ly = ld_row(rows, ld, 5, off4);
+    s.irx = ld_row(rows, ld, 6, off4); s.iry = ld_row(rows, ld, 7, off4); s.irz = ld_row(rows, ld, 8, off4);
+}
+template <class M>
+__device__ __forceinline__ void members_store(float* __restrict__ rows, int64_t ld, uint32_t off4, const M& s) {
+    st_row(rows, ld, 0, off4, s.ipx); st_row(rows, ld, 1, off4, s.ipy); st_row(rows, ld, 2, off4, s.ipz);
+    st_row(rows, ld, 3, off4, s.lr); st_row(rows, ld, 4, off4, s.lp); st_row(rows, ld, 5, off4, s.ly);
+    st_row(rows, ld, 6, off4, s.irx); st_row(rows, ld, 7, off4, s.iry); st_row(rows, ld, 8, off4, s.irz);
+}
+
+// What the two taped forwards share around their loops: the lane of a one-drone aviary, and one step's stores
+__device__ __forceinline__ Lane tape_lane(uint32_t N) {
+    const uint32_t n_raw = blockIdx.x * kBlock + threadIdx.x;
+    Lane L;
+    L.tid = threadIdx.x;
+    L.active = n_raw < N;
+    L.n = L.active ? n_raw : 0u;          // (a lane without a drone computes on drone 0 and stores nothing)
+    L.env = L.n; L.le = L.tid; L.d = 0; L.base = L.tid; L.shfl = false;
+    return L;
+}
+__device__ __forceinline__ void tape_step_store(const Lane& L, const StepOut& out, float* __restrict__ obs12, float* __restrict__ reward,
+                                                uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated) {
+    if (!L.active) return;
+    store_obs12(obs12, L.n, out.o[0], out.o[1], out.o[2], out.o[3], out.o[4], out.o[5], out.o[6], out.o[7],
+                out.o[8], out.o[9], out.o[10], out.o[11]);
+    reward[L.env] = out.rew;
+    terminated[L.env] = static_cast<uint8_t>(out.term ? 1 : 0);
+    truncated[L.env] = static_cast<uint8_t>(out.trunc ? 1 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -56,13 +101,7 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_tape_kernel(const GpdParam
                                                                   float* __restrict__ obs12, float* __restrict__ reward,
                                                                   uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated,
                                                                   const float* __restrict__ plant, float* __restrict__ tape) {
-    const uint32_t N = static_cast<uint32_t>(C.num_envs);
-    const uint32_t n_raw = blockIdx.x * kBlock + threadIdx.x;
-    Lane L;
-    L.tid = threadIdx.x;
-    L.active = n_raw < N;
-    L.n = L.active ? n_raw : 0u;          // (a lane without a drone computes on drone 0 and stores nothing)
-    L.env = L.n; L.le = L.tid; L.d = 0; L.base = L.tid; L.shfl = false;
+    const Lane L = tape_lane(static_cast<uint32_t>(C.num_envs));
     const uint32_t flags = EXT ? C.physics_flags : 0u;
     const int64_t ld = S.ld;
     Carry c;
@@ -75,17 +114,11 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_tape_kernel(const GpdParam
     for (int t = 0; t < K; ++t, actions += a_stride, obs12 += o_stride, reward += e_stride, terminated += e_stride, truncated += e_stride,
                             tape += 13 * ld) {
         const float4 act = load_action<AW>(actions, L.n);
-        if (L.active) planes_store(tape, ld, L.n, c.k);
+        if (L.active) kin_store(tape, ld, L.n, c.k);
         StepOut out;
         env_step<false, EXT, false, AW>(Q, C, flags, 1, L, act, tgx, tgy, tgz, false, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f,
                                         nullptr, nullptr, c, out);
-        if (L.active) {
-            store_obs12(obs12, L.n, out.o[0], out.o[1], out.o[2], out.o[3], out.o[4], out.o[5], out.o[6], out.o[7],
-                        out.o[8], out.o[9], out.o[10], out.o[11]);
-            reward[L.env] = out.rew;
-            terminated[L.env] = static_cast<uint8_t>(out.term ? 1 : 0);
-            truncated[L.env] = static_cast<uint8_t>(out.trunc ? 1 : 0);
-        }
+        tape_step_store(L, out, obs12, reward, terminated, truncated);
     }
     if (L.active) store_carry<false>(S, L, c);
 }
@@ -117,6 +150,22 @@ __device__ __forceinline__ void rpy_vjp(float x, float y, float z, float w, floa
     ay = gimbal ? inv * x : ry;
     az = gimbal ? 0.0f : rz;
     aw = gimbal ? 0.0f : rw;
+}
+
+// Adjoint of quat_to_mat at (x, y, z, w): the nine cotangents of R -> += the quaternion's.  R = I + s B(q), s = 2 / |q|^2.
+__device__ __forceinline__ void mat_vjp(float x, float y, float z, float w, float r00, float r01, float r02, float r10, float r11, float r12,
+                                        float r20, float r21, float r22, float& ax, float& ay, float& az, float& aw) {
+    const float d = fmaf(x, x, fmaf(y, y, fmaf(z, z, w * w)));
+    const float s = 2.0f / d;
+    const float a_s = -(r00 * fmaf(y, y, z * z) + r11 * fmaf(x, x, z * z) + r22 * fmaf(x, x, y * y))
+                      + r01 * fmaf(x, y, -(w * z)) + r02 * fmaf(x, z, w * y) + r10 * fmaf(x, y, w * z)
+                      + r12 * fmaf(y, z, -(w * x)) + r20 * fmaf(x, z, -(w * y)) + r21 * fmaf(y, z, w * x);
+    const float a_d2 = -2.0f * (s / d) * a_s;                   // d s / d q_i = -(s / d) 2 q_i
+    const float b00 = s * r00, b01 = s * r01, b02 = s * r02, b10 = s * r10, b11 = s * r11, b12 = s * r12, b20 = s * r20, b21 = s * r21, b22 = s * r22;
+    ax += fmaf(a_d2, x, (b01 + b10) * y + (b02 + b20) * z + (b21 - b12) * w - 2.0f * (b11 + b22) * x);
+    ay += fmaf(a_d2, y, (b01 + b10) * x + (b12 + b21) * z + (b02 - b20) * w - 2.0f * (b00 + b22) * y);
+    az += fmaf(a_d2, z, (b02 + b20) * x + (b12 + b21) * y + (b10 - b01) * w - 2.0f * (b00 + b11) * z);
+    aw += fmaf(a_d2, w, (b10 - b01) * z + (b02 - b20) * y + (b21 - b12) * x);
 }
 
 // Cotangents of the plant rows the sweep reads (gpd_rollout_vjp_plant), one drone's, in registers for all K steps: the 16 rows of
@@ -259,19 +308,8 @@ __device__ __forceinline__ void substep_vjp(const GpdParams& P, const float h, c
     const float r02 = fmaf(afx, T, AV ? bx * wz : 0.0f), r12 = fmaf(afy, T, AV ? by * wz : 0.0f), r22 = fmaf(afz, T, AV ? bz * wz : 0.0f);
     const float r00 = AV ? bx * wx : 0.0f, r01 = AV ? bx * wy : 0.0f, r10 = AV ? by * wx : 0.0f, r11 = AV ? by * wy : 0.0f;
     const float r20 = AV ? bz * wx : 0.0f, r21 = AV ? bz * wy : 0.0f;
-    // R = I + s B(q), s = 2 / |q|^2 (quat_to_mat)
-    const float x = k.qx, y = k.qy, z = k.qz, w = k.qw;
-    const float d = fmaf(x, x, fmaf(y, y, fmaf(z, z, w * w)));
-    const float s = 2.0f / d;
-    const float a_s = -(r00 * fmaf(y, y, z * z) + r11 * fmaf(x, x, z * z) + r22 * fmaf(x, x, y * y))
-                      + r01 * fmaf(x, y, -(w * z)) + r02 * fmaf(x, z, w * y) + r10 * fmaf(x, y, w * z)
-                      + r12 * fmaf(y, z, -(w * x)) + r20 * fmaf(x, z, -(w * y)) + r21 * fmaf(y, z, w * x);
-    const float a_d2 = -2.0f * (s / d) * a_s;                   // d s / d q_i = -(s / d) 2 q_i
-    const float b00 = s * r00, b01 = s * r01, b02 = s * r02, b10 = s * r10, b11 = s * r11, b12 = s * r12, b20 = s * r20, b21 = s * r21, b22 = s * r22;
-    a.qx = aqx + fmaf(a_d2, x, (b01 + b10) * y + (b02 + b20) * z + (b21 - b12) * w - 2.0f * (b11 + b22) * x);
-    a.qy = aqy + fmaf(a_d2, y, (b01 + b10) * x + (b12 + b21) * z + (b02 - b20) * w - 2.0f * (b00 + b22) * y);
-    a.qz = aqz + fmaf(a_d2, z, (b02 + b20) * x + (b12 + b21) * y + (b10 - b01) * w - 2.0f * (b00 + b11) * z);
-    a.qw = aqw + fmaf(a_d2, w, (b10 - b01) * z + (b02 - b20) * y + (b21 - b12) * x);
+    a.qx = aqx; a.qy = aqy; a.qz = aqz; a.qw = aqw;
+    mat_vjp(k.qx, k.qy, k.qz, k.qw, r00, r01, r02, r10, r11, r12, r20, r21, r22, a.qx, a.qy, a.qz, a.qw);
 }
 
 // Adjoint of map_action<false, AW> (the four RPM action types): out[AW] = cotangent of the raw action row
@@ -319,6 +357,24 @@ __device__ __forceinline__ void action_vjp(const PP& P, const GpdStepCfg& C, con
     }
 }
 
+// The step's outputs are functions of the state kp its LAST sub-step leaves: obs12 = pos | rpy | vel | ang_v, the reward.  A += the
+// cotangents of pos, rpy, vel (go[0..8]) and of the reward (grew); that of ang_v (go[9..11]) goes through substep_vjp<.., AV = true>.
+__device__ __forceinline__ void outputs_vjp(const Kin& kp, const float go[12], const float grew, const float tgx, const float tgy,
+                                            const float tgz, Kin& A) {
+    A.px += go[0]; A.py += go[1]; A.pz += go[2];
+    A.vx += go[6]; A.vy += go[7]; A.vz += go[8];
+    float rqx, rqy, rqz, rqw;
+    rpy_vjp(kp.qx, kp.qy, kp.qz, kp.qw, go[3], go[4], go[5], rqx, rqy, rqz, rqw);
+    A.qx += rqx; A.qy += rqy; A.qz += rqz; A.qw += rqw;
+    {   // reward = max(0, 2 - |target - p|^4), task_single's expressions
+        const float ex = tgx - kp.px, ey = tgy - kp.py, ez = tgz - kp.pz;
+        const float dist = fast_sqrt(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
+        const float dd = dist * dist;
+        const float gr = fmaf(-dd, dd, 2.0f) > 0.0f ? 4.0f * dd * grew : 0.0f;
+        A.px = fmaf(gr, ex, A.px); A.py = fmaf(gr, ey, A.py); A.pz = fmaf(gr, ez, A.pz);
+    }
+}
+
 // GP (only with PLANT): the lane also accumulates the cotangents of its drone's plant rows over the whole sweep and stores them once,
 // after the loop, into g_plant [GPD_PLANT_ROWS][ld] -- rows no supported configuration reads as exactly 0.  g_plant is NULL otherwise.
 template <bool EXT, int AW, bool PLANT, bool GP = false>
@@ -341,12 +397,12 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_kernel(const GpdParams
     const float tgx = tp[0], tgy = tp[1], tgz = tp[2];
     const float h = C.pyb_dt;
     const int S = C.substeps;
-    Kin A = planes_load(g_kin, ld, n);                         // cotangent of the state after the step in hand
+    Kin A = kin_load(g_kin, ld, n);                         // cotangent of the state after the step in hand
     float a_next = 0.0f;                                       // cotangent of this step's rpm sum from the NEXT step's first drag term
     plant_cot_t<GP> G;                                         // GP: cotangents of the plant rows, summed over the sweep
     const float first_sum = drag ? tape[static_cast<int64_t>(K) * 13 * ld + n] : 0.0f;
     for (int t = K - 1; t >= 0; --t) {
-        const Kin k0 = planes_load(tape + static_cast<int64_t>(t) * 13 * ld, ld, n);
+        const Kin k0 = kin_load(tape + static_cast<int64_t>(t) * 13 * ld, ld, n);
         const float4 act = load_action<AW>(actions + t * a_stride, n);
         Carry c{};
         c.k = k0;
@@ -362,6 +418,8 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_kernel(const GpdParams
                 prev_sum = ((rp[0] + rp[1]) + rp[2]) + rp[3];
             }
         }
+        // (This load and the loop over the sub-steps below stand in gpd_rollout_vjp_pid_kernel too: shared, the load in three forms cost
+        // 1 - 4 % of the sweeps' time, the loop 1 - 6 VGPRs as one function and 1.3 % at S = 8 with its body alone shared.)
         float go[12];
         if (g_obs12) {
             const f4u* row = reinterpret_cast<const f4u*>(g_obs12 + t * o_stride + static_cast<size_t>(n) * 12);
@@ -385,18 +443,7 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_kernel(const GpdParams
                 // the step's outputs are functions of the state its LAST sub-step leaves: obs12 = pos | rpy | vel | ang_v, the reward
                 Kin kp = k;
                 substep<EXT, false>(Q, h, flags, g, ds, 0.0f, kp, d0, d1, d2);
-                A.px += go[0]; A.py += go[1]; A.pz += go[2];
-                A.vx += go[6]; A.vy += go[7]; A.vz += go[8];
-                float rqx, rqy, rqz, rqw;
-                rpy_vjp(kp.qx, kp.qy, kp.qz, kp.qw, go[3], go[4], go[5], rqx, rqy, rqz, rqw);
-                A.qx += rqx; A.qy += rqy; A.qz += rqz; A.qw += rqw;
-                {   // reward = max(0, 2 - |target - p|^4), task_single's expressions
-                    const float ex = tgx - kp.px, ey = tgy - kp.py, ez = tgz - kp.pz;
-                    const float dist = fast_sqrt(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
-                    const float dd = dist * dist;
-                    const float gr = fmaf(-dd, dd, 2.0f) > 0.0f ? 4.0f * dd * grew : 0.0f;
-                    A.px = fmaf(gr, ex, A.px); A.py = fmaf(gr, ey, A.py); A.pz = fmaf(gr, ez, A.pz);
-                }
+                outputs_vjp(kp, go, grew, tgx, tgy, tgz, A);
                 substep_vjp<EXT, true, GP>(Q, h, flags, g, ds, k, A, go[9], go[10], go[11], ag, a_drag, G);
             } else {
                 substep_vjp<EXT, false, GP>(Q, h, flags, g, ds, k, A, 0.0f, 0.0f, 0.0f, ag, a_drag, G);
@@ -411,7 +458,7 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_kernel(const GpdParams
         else dst[0] = ga[0];
         a_next = a_prev;
     }
-    planes_store(g_kin, ld, n, A);
+    kin_store(g_kin, ld, n, A);
     if constexpr (GP) {
         const float rows[GPD_PLANT_ROWS] = {0.0f /* M */, G.inv_m, G.kf, G.gravity, G.j0, G.j1, G.j2, G.ji0, G.ji1, G.ji2, G.km_over_kf,
                                             0.0f /* GND_EFF */, G.d0, G.d1, G.d2, 0.0f /* HOVER_THRUST */, G.resid, G.norm_thrust, G.norm_gap};
@@ -440,8 +487,11 @@ __global__ __launch_bounds__(256) void gpd_plant_derive_vjp_kernel(const GpdPara
 }
 
 // What the entries of the rollout check of the configuration and refuse of it, before any device work: the span and the sizes, then what is
-// not differentiable.  `ld` comes without the state in two of them.
-int diff_cfg(Refuse bad, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, int64_t stride0 = 0, int64_t stride1 = 0, int64_t stride2 = 0) {
+// not differentiable in the family the entry serves (the RPM action types of this file, or the DSLPID ones of diff_pid_kernels.inc).
+// `ld` comes without the state in two entries of each family.
+enum class DiffFamily { RPM, PID };
+int diff_cfg(Refuse bad, DiffFamily family, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, int64_t stride0 = 0, int64_t stride1 = 0,
+             int64_t stride2 = 0) {
     if (int rc = check_steps(bad, num_steps, stride0, stride1, stride2)) return rc;
     if (int rc = check_ranges(bad, cfg)) return rc;
     if (int rc = check_positive(bad, cfg)) return rc;
@@ -450,11 +500,60 @@ int diff_cfg(Refuse bad, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, i
     if (int rc = check_extent(bad, static_cast<int64_t>(cfg->num_envs) * cfg->drones_per_env, ld, "ld")) return rc;
     if (cfg->drones_per_env != 1) return bad(GPD_ENOTSUP, "aviaries of more than one drone are not differentiable (drones_per_env must be 1)");
     if (cfg->task != GPD_TASK_NONE && cfg->task != GPD_TASK_HOVER) return bad(GPD_ENOTSUP, "task must be GPD_TASK_NONE or GPD_TASK_HOVER");
-    if (cfg->act_type != GPD_ACT_RPM && cfg->act_type != GPD_ACT_ONE_D_RPM && cfg->act_type != GPD_ACT_RAW_RPM && cfg->act_type != GPD_ACT_DIRECT_RPM)
-        return bad(GPD_ENOTSUP, "the DSLPID action types are not differentiable (RPM, ONE_D_RPM, RAW_RPM and DIRECT_RPM are)");
-    if (cfg->physics_flags & ~static_cast<uint32_t>(GPD_PHYS_DRAG))
-        return bad(GPD_ENOTSUP, "physics_flags other than GPD_PHYS_DRAG are not differentiable (ground effect, downwash, ground plane, damping)");
+    if (family == DiffFamily::RPM) {
+        if (cfg->act_type != GPD_ACT_RPM && cfg->act_type != GPD_ACT_ONE_D_RPM && cfg->act_type != GPD_ACT_RAW_RPM && cfg->act_type != GPD_ACT_DIRECT_RPM)
+            return bad(GPD_ENOTSUP, "the DSLPID action types are not differentiable (RPM, ONE_D_RPM, RAW_RPM and DIRECT_RPM are)");
+        if (cfg->physics_flags & ~static_cast<uint32_t>(GPD_PHYS_DRAG))
+            return bad(GPD_ENOTSUP, "physics_flags other than GPD_PHYS_DRAG are not differentiable (ground effect, downwash, ground plane, damping)");
+    } else {
+        if (cfg->act_type != GPD_ACT_PID && cfg->act_type != GPD_ACT_VEL && cfg->act_type != GPD_ACT_ONE_D_PID)
+            return bad(GPD_ENOTSUP, "the RPM action types go through gpd_rollout_tape / gpd_rollout_vjp (this entry: PID, VEL and ONE_D_PID)");
+        if (cfg->physics_flags)
+            return bad(GPD_ENOTSUP, "physics_flags are not differentiable together with DSLPID (drag, ground effect, downwash, ground plane, damping)");
+    }
     if (cfg->auto_reset) return bad(GPD_ENOTSUP, "auto_reset inside a differentiated call is not supported");
+    return 0;
+}
+
+// The size query of a family's tape: per_step x num_steps + extra rows of ld floats
+int tape_floats_impl(Refuse bad, DiffFamily family, const GpdStepCfg* cfg, int32_t num_steps, int64_t ld, int per_step, int extra, int64_t* floats_out) {
+    if (!cfg || !floats_out) return bad(GPD_EINVAL, "NULL cfg/floats_out");
+    if (int rc = diff_cfg(bad, family, cfg, ld, num_steps)) return rc;
+    const int64_t rows = per_step * static_cast<int64_t>(num_steps) + extra;
+    if (rows > INT64_MAX / ld) return bad(GPD_ERANGE, "the tape does not fit 2^63 floats");
+    *floats_out = rows * ld;
+    return 0;
+}
+
+// The argument checks of a taped forward (gpd_rollout_tape, gpd_rollout_tape_pid) up to the tape's alignment, then the copies the kernel
+// gets: `c` with a readable dummy target where there is no task, `s` without the action ring.
+int tape_prologue(Refuse bad, DiffFamily family, const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, int32_t num_steps,
+                  const float* actions, int64_t action_step_stride, const float*& target_pos, const float* obs12, int64_t obs_step_stride,
+                  const float* reward, const uint8_t* terminated, const uint8_t* truncated, int64_t env_step_stride, const float* tape,
+                  GpdStepCfg& c, GpdState& s) {
+    if (!params || !state || !cfg) return bad(GPD_EINVAL, "NULL params/state/cfg");
+    if (int rc = check_state(bad, state)) return rc;
+    if (!actions || !obs12 || !reward || !terminated || !truncated || !tape)
+        return bad(GPD_EINVAL, "NULL actions/obs12/reward/terminated/truncated/tape");
+    if (int rc = diff_cfg(bad, family, cfg, state->ld, num_steps, action_step_stride, obs_step_stride, env_step_stride)) return rc;
+    if (state->dw_force) return bad(GPD_ENOTSUP, "state.dw_force (downwash computed outside the kernel) is not differentiable");
+    if (int rc = check_needs(bad, params, state, cfg, target_pos, nullptr)) return rc;
+    if (misaligned16(tape)) return bad(GPD_EINVAL, "tape must be 16-byte aligned");
+    c = *cfg;
+    s = *state;
+    s.act_ring = nullptr;                                      // (a rollout never pushes into the action ring itself)
+    dummy_target(c, target_pos, state->kin);
+    return 0;
+}
+
+// The checks the reverse sweeps (gpd_rollout_vjp / _plant, gpd_rollout_vjp_pid) share after their own NULL lists: the configuration, what
+// it needs, the alignment of the two blocks both read as float4.  Each entry goes on with the alignment of its own arguments.
+int sweep_prologue(Refuse bad, DiffFamily family, const GpdParams* params, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps,
+                   int64_t action_step_stride, int64_t obs_step_stride, int64_t env_step_stride, const float* target_pos,
+                   const float* tape, const float* g_kin) {
+    if (int rc = diff_cfg(bad, family, cfg, ld, num_steps, action_step_stride, obs_step_stride, env_step_stride)) return rc;
+    if (int rc = check_needs(bad, params, nullptr, cfg, target_pos, nullptr)) return rc;
+    if (misaligned16(tape) || misaligned16(g_kin)) return bad(GPD_EINVAL, "tape and g_kin must be 16-byte aligned");
     return 0;
 }
 
@@ -473,9 +572,9 @@ int vjp_impl(Refuse bad, const GpdParams* params, const GpdStepCfg* cfg, int64_t
              void* stream) {
     if (!params || !cfg) return bad(GPD_EINVAL, "NULL params/cfg");
     if (!actions || !tape || !g_kin || !g_actions) return bad(GPD_EINVAL, "NULL actions/tape/g_kin/g_actions");
-    if (int rc = diff_cfg(bad, cfg, ld, num_steps, action_step_stride, obs_step_stride, env_step_stride)) return rc;
-    if (int rc = check_needs(bad, params, nullptr, cfg, target_pos, nullptr)) return rc;
-    if (misaligned16(tape) || misaligned16(g_kin)) return bad(GPD_EINVAL, "tape and g_kin must be 16-byte aligned");
+    if (int rc = sweep_prologue(bad, DiffFamily::RPM, params, cfg, ld, num_steps, action_step_stride, obs_step_stride, env_step_stride,
+                                target_pos, tape, g_kin))
+        return rc;
     if (misaligned16(plant_rows)) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
     if (misaligned16(g_actions)) return bad(GPD_EINVAL, "g_actions must be 16-byte aligned");
     GpdStepCfg c = *cfg;
@@ -502,32 +601,20 @@ int vjp_impl(Refuse bad, const GpdParams* params, const GpdStepCfg* cfg, int64_t
 extern "C" {
 
 int gpd_rollout_tape_floats(const GpdStepCfg* cfg, int32_t num_steps, int64_t ld, int64_t* floats_out) {
-    const Refuse bad{"gpd_rollout_tape_floats"};
-    if (!cfg || !floats_out) return bad(GPD_EINVAL, "NULL cfg/floats_out");
-    if (int rc = diff_cfg(bad, cfg, ld, num_steps)) return rc;
-    const int64_t rows = 13 * static_cast<int64_t>(num_steps) + 1;           // 13 per env step + the first drag term's rpm sum
-    if (rows > INT64_MAX / ld) return bad(GPD_ERANGE, "the tape does not fit 2^63 floats");
-    *floats_out = rows * ld;
-    return 0;
+    // 13 per env step + the first drag term's rpm sum
+    return tape_floats_impl(Refuse{"gpd_rollout_tape_floats"}, DiffFamily::RPM, cfg, num_steps, ld, 13, 1, floats_out);
 }
 
 int gpd_rollout_tape(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, int32_t num_steps, const float* actions,
                      int64_t action_step_stride, const float* target_pos, float* obs12, int64_t obs_step_stride, float* reward,
                      uint8_t* terminated, uint8_t* truncated, int64_t env_step_stride, const float* plant_rows, float* tape, void* stream) {
     const Refuse bad{"gpd_rollout_tape"};
-    if (!params || !state || !cfg) return bad(GPD_EINVAL, "NULL params/state/cfg");
-    if (int rc = check_state(bad, state)) return rc;
-    if (!actions || !obs12 || !reward || !terminated || !truncated || !tape)
-        return bad(GPD_EINVAL, "NULL actions/obs12/reward/terminated/truncated/tape");
-    if (int rc = diff_cfg(bad, cfg, state->ld, num_steps, action_step_stride, obs_step_stride, env_step_stride)) return rc;
-    if (state->dw_force) return bad(GPD_ENOTSUP, "state.dw_force (downwash computed outside the kernel) is not differentiable");
-    if (int rc = check_needs(bad, params, state, cfg, target_pos, nullptr)) return rc;
-    if (misaligned16(tape)) return bad(GPD_EINVAL, "tape must be 16-byte aligned");
+    GpdStepCfg c;
+    GpdState s;
+    if (int rc = tape_prologue(bad, DiffFamily::RPM, params, state, cfg, num_steps, actions, action_step_stride, target_pos, obs12,
+                               obs_step_stride, reward, terminated, truncated, env_step_stride, tape, c, s))
+        return rc;
     if (misaligned16(plant_rows)) return bad(GPD_EINVAL, "plant_rows must be 16-byte aligned");
-    GpdStepCfg c = *cfg;
-    GpdState s = *state;
-    s.act_ring = nullptr;                                      // (a rollout never pushes into the action ring itself)
-    dummy_target(c, target_pos, state->kin);
     const dim3 grid(blocks_for(c.num_envs, kBlock));
     diff_dispatch(c, plant_rows != nullptr, [&](auto ext, auto aw, auto pl) {
         hipLaunchKernelGGL((gpd_rollout_tape_kernel<decltype(ext)::value, decltype(aw)::value, decltype(pl)::value>), grid, dim3(kBlock), 0,

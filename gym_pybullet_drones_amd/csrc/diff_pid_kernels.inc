@@ -21,33 +21,18 @@ namespace {
 
 constexpr int kTapePidRows = 22;       // floats per drone-step
 
+// drone n's step t of the tape: the three planes through planes_store / planes_load, the ten rows through the member-row helpers
 __device__ __forceinline__ void tape_pid_store(float* __restrict__ tape, int64_t ld, int K, int t, uint32_t n, const Kin& k, const Pid& s) {
-    const uint32_t off16 = n * 16u, off4 = n * 4u;
-    float e0 = k.px, e1 = k.py, e2 = k.pz, e3 = k.wx, e4 = k.qx, e5 = k.qy, e6 = k.qz, e7 = k.qw, e8 = k.vx, e9 = k.vy, e10 = k.vz, e11 = k.wy;
-    asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3), "+v"(e4), "+v"(e5), "+v"(e6), "+v"(e7), "+v"(e8), "+v"(e9), "+v"(e10), "+v"(e11));
-    const f4v p = {e0, e1, e2, e3}, q = {e4, e5, e6, e7}, v = {e8, e9, e10, e11};
-    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(tape + (4 * static_cast<int64_t>(t)) * ld) + off16) = p;
-    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(tape + (4 * (static_cast<int64_t>(K) + t)) * ld) + off16) = q;
-    *reinterpret_cast<f4v*>(reinterpret_cast<char*>(tape + (4 * (2 * static_cast<int64_t>(K) + t)) * ld) + off16) = v;
     float* rows = tape + (12 * static_cast<int64_t>(K) + 10 * static_cast<int64_t>(t)) * ld;
-    st_row(rows, ld, 0, off4, k.wz);
-    st_row(rows, ld, 1, off4, s.ipx); st_row(rows, ld, 2, off4, s.ipy); st_row(rows, ld, 3, off4, s.ipz);
-    st_row(rows, ld, 4, off4, s.lr); st_row(rows, ld, 5, off4, s.lp); st_row(rows, ld, 6, off4, s.ly);
-    st_row(rows, ld, 7, off4, s.irx); st_row(rows, ld, 8, off4, s.iry); st_row(rows, ld, 9, off4, s.irz);
+    planes_store(tape + (4 * static_cast<int64_t>(t)) * ld, tape + (4 * (static_cast<int64_t>(K) + t)) * ld,
+                 tape + (4 * (2 * static_cast<int64_t>(K) + t)) * ld, rows, n, k);
+    members_store(rows + ld, ld, n * 4u, s);
 }
 __device__ __forceinline__ void tape_pid_load(const float* __restrict__ tape, int64_t ld, int K, int t, uint32_t n, Kin& k, Pid& s) {
-    const uint32_t off16 = n * 16u, off4 = n * 4u;
-    const f4v p = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(tape + (4 * static_cast<int64_t>(t)) * ld) + off16);
-    const f4v q = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(tape + (4 * (static_cast<int64_t>(K) + t)) * ld) + off16);
-    const f4v v = *reinterpret_cast<const f4v*>(reinterpret_cast<const char*>(tape + (4 * (2 * static_cast<int64_t>(K) + t)) * ld) + off16);
     const float* rows = tape + (12 * static_cast<int64_t>(K) + 10 * static_cast<int64_t>(t)) * ld;
-    k.px = p.x; k.py = p.y; k.pz = p.z; k.wx = p.w;
-    k.qx = q.x; k.qy = q.y; k.qz = q.z; k.qw = q.w;
-    k.vx = v.x; k.vy = v.y; k.vz = v.z; k.wy = v.w;
-    k.wz = ld_row(rows, ld, 0, off4);
-    s.ipx = ld_row(rows, ld, 1, off4); s.ipy = ld_row(rows, ld, 2, off4); s.ipz = ld_row(rows, ld, 3, off4);
-    s.lr = ld_row(rows, ld, 4, off4); s.lp = ld_row(rows, ld, 5, off4); s.ly = ld_row(rows, ld, 6, off4);
-    s.irx = ld_row(rows, ld, 7, off4); s.iry = ld_row(rows, ld, 8, off4); s.irz = ld_row(rows, ld, 9, off4);
+    k = planes_load(tape + (4 * static_cast<int64_t>(t)) * ld, tape + (4 * (static_cast<int64_t>(K) + t)) * ld,
+                    tape + (4 * (2 * static_cast<int64_t>(K) + t)) * ld, rows, n);
+    members_load(rows + ld, ld, n * 4u, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -60,13 +45,7 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_tape_pid_kernel(const GpdP
                                                                       float* __restrict__ obs12, float* __restrict__ reward,
                                                                       uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated,
                                                                       float* __restrict__ tape) {
-    const uint32_t N = static_cast<uint32_t>(C.num_envs);
-    const uint32_t n_raw = blockIdx.x * kBlock + threadIdx.x;
-    Lane L;
-    L.tid = threadIdx.x;
-    L.active = n_raw < N;
-    L.n = L.active ? n_raw : 0u;          // (a lane without a drone computes on drone 0 and stores nothing)
-    L.env = L.n; L.le = L.tid; L.d = 0; L.base = L.tid; L.shfl = false;
+    const Lane L = tape_lane(static_cast<uint32_t>(C.num_envs));
     const int64_t ld = S.ld;
     Carry c;
     float tgx, tgy, tgz;
@@ -78,13 +57,7 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_tape_pid_kernel(const GpdP
         StepOut out;
         env_step<true, false, false, AW>(P, C, 0u, 1, L, act, tgx, tgy, tgz, false, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f,
                                          nullptr, nullptr, c, out);
-        if (L.active) {
-            store_obs12(obs12, L.n, out.o[0], out.o[1], out.o[2], out.o[3], out.o[4], out.o[5], out.o[6], out.o[7],
-                        out.o[8], out.o[9], out.o[10], out.o[11]);
-            reward[L.env] = out.rew;
-            terminated[L.env] = static_cast<uint8_t>(out.term ? 1 : 0);
-            truncated[L.env] = static_cast<uint8_t>(out.trunc ? 1 : 0);
-        }
+        tape_step_store(L, out, obs12, reward, terminated, truncated);
     }
     if (L.active) store_carry<true>(S, L, c);
 }
@@ -92,23 +65,6 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_tape_pid_kernel(const GpdP
 // ------------------------------------------------------------------------------------------------
 // the reverse sweep
 // ------------------------------------------------------------------------------------------------
-// Adjoint of quat_to_mat at (x, y, z, w): the nine cotangents of R -> += the quaternion's.  R = I + s B(q), s = 2 / |q|^2 (the lines
-// substep_vjp ends with, for a full matrix).
-__device__ __forceinline__ void mat_vjp(float x, float y, float z, float w, float r00, float r01, float r02, float r10, float r11, float r12,
-                                        float r20, float r21, float r22, float& ax, float& ay, float& az, float& aw) {
-    const float d = fmaf(x, x, fmaf(y, y, fmaf(z, z, w * w)));
-    const float s = 2.0f / d;
-    const float a_s = -(r00 * fmaf(y, y, z * z) + r11 * fmaf(x, x, z * z) + r22 * fmaf(x, x, y * y))
-                      + r01 * fmaf(x, y, -(w * z)) + r02 * fmaf(x, z, w * y) + r10 * fmaf(x, y, w * z)
-                      + r12 * fmaf(y, z, -(w * x)) + r20 * fmaf(x, z, -(w * y)) + r21 * fmaf(y, z, w * x);
-    const float a_d2 = -2.0f * (s / d) * a_s;
-    const float b00 = s * r00, b01 = s * r01, b02 = s * r02, b10 = s * r10, b11 = s * r11, b12 = s * r12, b20 = s * r20, b21 = s * r21, b22 = s * r22;
-    ax += fmaf(a_d2, x, (b01 + b10) * y + (b02 + b20) * z + (b21 - b12) * w - 2.0f * (b11 + b22) * x);
-    ay += fmaf(a_d2, y, (b01 + b10) * x + (b12 + b21) * z + (b02 - b20) * w - 2.0f * (b00 + b22) * y);
-    az += fmaf(a_d2, z, (b02 + b20) * x + (b12 + b21) * y + (b10 - b01) * w - 2.0f * (b00 + b11) * z);
-    aw += fmaf(a_d2, w, (b10 - b01) * z + (b02 - b20) * y + (b21 - b12) * x);
-}
-
 struct NoGains {};
 template <bool GG> using gain_cot_t = std::conditional_t<GG, GpdDslGainCot, NoGains>;
 
@@ -129,11 +85,9 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_pid_kernel(const GpdPa
     const float tgx = tp[0], tgy = tp[1], tgz = tp[2];
     const float h = C.pyb_dt;
     const int S = C.substeps;
-    Kin A = planes_load(g_kin, ld, n);                         // cotangent of the state after the step in hand
+    Kin A = kin_load(g_kin, ld, n);                            // cotangent of the state after the step in hand
     GpdDslOutCot o;                                            // ... and of the members after it (the RPMs' slots: per step)
-    o.ipx = ld_row(g_pid, ld, 0, off4); o.ipy = ld_row(g_pid, ld, 1, off4); o.ipz = ld_row(g_pid, ld, 2, off4);
-    o.lr = ld_row(g_pid, ld, 3, off4); o.lp = ld_row(g_pid, ld, 4, off4); o.ly = ld_row(g_pid, ld, 5, off4);
-    o.irx = ld_row(g_pid, ld, 6, off4); o.iry = ld_row(g_pid, ld, 7, off4); o.irz = ld_row(g_pid, ld, 8, off4);
+    members_load(g_pid, ld, off4, o);
     gain_cot_t<GG> G{};                                        // GG: cotangents of the 18 gains, summed over the sweep
     NoCot no_plant;
     for (int t = K - 1; t >= 0; --t) {
@@ -167,18 +121,7 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_pid_kernel(const GpdPa
             if (j == S - 1) {
                 Kin kp = k;
                 substep<false, false>(P, h, 0u, g, 0.0f, 0.0f, kp, d0, d1, d2);
-                A.px += go[0]; A.py += go[1]; A.pz += go[2];
-                A.vx += go[6]; A.vy += go[7]; A.vz += go[8];
-                float rqx, rqy, rqz, rqw;
-                rpy_vjp(kp.qx, kp.qy, kp.qz, kp.qw, go[3], go[4], go[5], rqx, rqy, rqz, rqw);
-                A.qx += rqx; A.qy += rqy; A.qz += rqz; A.qw += rqw;
-                {   // reward = max(0, 2 - |target - p|^4), task_single's expressions
-                    const float ex = tgx - kp.px, ey = tgy - kp.py, ez = tgz - kp.pz;
-                    const float dist = fast_sqrt(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
-                    const float dd = dist * dist;
-                    const float gr = fmaf(-dd, dd, 2.0f) > 0.0f ? 4.0f * dd * grew : 0.0f;
-                    A.px = fmaf(gr, ex, A.px); A.py = fmaf(gr, ey, A.py); A.pz = fmaf(gr, ez, A.pz);
-                }
+                outputs_vjp(kp, go, grew, tgx, tgy, tgz, A);
                 substep_vjp<false, true>(P, h, 0u, g, 0.0f, k, A, go[9], go[10], go[11], ag, a_drag, no_plant);
             } else {
                 substep_vjp<false, false>(P, h, 0u, g, 0.0f, k, A, 0.0f, 0.0f, 0.0f, ag, a_drag, no_plant);
@@ -253,10 +196,8 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_pid_kernel(const GpdPa
         else if (AW == 3) { dst[0] = ga0; dst[1] = ga1; dst[2] = ga2; }
         else dst[0] = ga0;
     }
-    planes_store(g_kin, ld, n, A);
-    st_row(g_pid, ld, 0, off4, o.ipx); st_row(g_pid, ld, 1, off4, o.ipy); st_row(g_pid, ld, 2, off4, o.ipz);
-    st_row(g_pid, ld, 3, off4, o.lr); st_row(g_pid, ld, 4, off4, o.lp); st_row(g_pid, ld, 5, off4, o.ly);
-    st_row(g_pid, ld, 6, off4, o.irx); st_row(g_pid, ld, 7, off4, o.iry); st_row(g_pid, ld, 8, off4, o.irz);
+    kin_store(g_kin, ld, n, A);
+    members_store(g_pid, ld, off4, o);
     if constexpr (GG) {
         st_row(g_gains, ld, 0, off4, G.pf0); st_row(g_gains, ld, 1, off4, G.pf1); st_row(g_gains, ld, 2, off4, G.pf2);
         st_row(g_gains, ld, 3, off4, G.if0); st_row(g_gains, ld, 4, off4, G.if1); st_row(g_gains, ld, 5, off4, G.if2);
@@ -267,25 +208,6 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_vjp_pid_kernel(const GpdPa
     } else {
         (void)g_gains;
     }
-}
-
-// What the three entries check of the configuration and refuse of it, before any device work (diff_cfg's order; `ld` comes without the
-// state in two of them).
-int diff_pid_cfg(Refuse bad, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, int64_t stride0 = 0, int64_t stride1 = 0, int64_t stride2 = 0) {
-    if (int rc = check_steps(bad, num_steps, stride0, stride1, stride2)) return rc;
-    if (int rc = check_ranges(bad, cfg)) return rc;
-    if (int rc = check_positive(bad, cfg)) return rc;
-    if (int rc = check_flags(bad, cfg)) return rc;
-    if (ld <= 0 || ld > 0xffffffffLL) return bad(GPD_EINVAL, "ld must be in 1 .. 2^32 - 1 (floats)");
-    if (int rc = check_extent(bad, static_cast<int64_t>(cfg->num_envs) * cfg->drones_per_env, ld, "ld")) return rc;
-    if (cfg->drones_per_env != 1) return bad(GPD_ENOTSUP, "aviaries of more than one drone are not differentiable (drones_per_env must be 1)");
-    if (cfg->task != GPD_TASK_NONE && cfg->task != GPD_TASK_HOVER) return bad(GPD_ENOTSUP, "task must be GPD_TASK_NONE or GPD_TASK_HOVER");
-    if (cfg->act_type != GPD_ACT_PID && cfg->act_type != GPD_ACT_VEL && cfg->act_type != GPD_ACT_ONE_D_PID)
-        return bad(GPD_ENOTSUP, "the RPM action types go through gpd_rollout_tape / gpd_rollout_vjp (this entry: PID, VEL and ONE_D_PID)");
-    if (cfg->physics_flags)
-        return bad(GPD_ENOTSUP, "physics_flags are not differentiable together with DSLPID (drag, ground effect, downwash, ground plane, damping)");
-    if (cfg->auto_reset) return bad(GPD_ENOTSUP, "auto_reset inside a differentiated call is not supported");
-    return 0;
 }
 
 // act_type -> the action row's width: both kernels of this file are launched as launch(aw)
@@ -301,31 +223,19 @@ void diff_pid_dispatch(const GpdStepCfg& c, F&& launch) {
 extern "C" {
 
 int gpd_rollout_tape_pid_floats(const GpdStepCfg* cfg, int32_t num_steps, int64_t ld, int64_t* floats_out) {
-    const Refuse bad{"gpd_rollout_tape_pid_floats"};
-    if (!cfg || !floats_out) return bad(GPD_EINVAL, "NULL cfg/floats_out");
-    if (int rc = diff_pid_cfg(bad, cfg, ld, num_steps)) return rc;
-    const int64_t rows = kTapePidRows * static_cast<int64_t>(num_steps);          // 13 kinematic floats + 9 members per env step
-    if (rows > INT64_MAX / ld) return bad(GPD_ERANGE, "the tape does not fit 2^63 floats");
-    *floats_out = rows * ld;
-    return 0;
+    // 13 kinematic floats + 9 members per env step
+    return tape_floats_impl(Refuse{"gpd_rollout_tape_pid_floats"}, DiffFamily::PID, cfg, num_steps, ld, kTapePidRows, 0, floats_out);
 }
 
 int gpd_rollout_tape_pid(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, int32_t num_steps, const float* actions,
                          int64_t action_step_stride, const float* target_pos, float* obs12, int64_t obs_step_stride, float* reward,
                          uint8_t* terminated, uint8_t* truncated, int64_t env_step_stride, float* tape, void* stream) {
     const Refuse bad{"gpd_rollout_tape_pid"};
-    if (!params || !state || !cfg) return bad(GPD_EINVAL, "NULL params/state/cfg");
-    if (int rc = check_state(bad, state)) return rc;
-    if (!actions || !obs12 || !reward || !terminated || !truncated || !tape)
-        return bad(GPD_EINVAL, "NULL actions/obs12/reward/terminated/truncated/tape");
-    if (int rc = diff_pid_cfg(bad, cfg, state->ld, num_steps, action_step_stride, obs_step_stride, env_step_stride)) return rc;
-    if (state->dw_force) return bad(GPD_ENOTSUP, "state.dw_force (downwash computed outside the kernel) is not differentiable");
-    if (int rc = check_needs(bad, params, state, cfg, target_pos, nullptr)) return rc;
-    if (misaligned16(tape)) return bad(GPD_EINVAL, "tape must be 16-byte aligned");
-    GpdStepCfg c = *cfg;
-    GpdState s = *state;
-    s.act_ring = nullptr;                                      // (a rollout never pushes into the action ring itself)
-    dummy_target(c, target_pos, state->kin);
+    GpdStepCfg c;
+    GpdState s;
+    if (int rc = tape_prologue(bad, DiffFamily::PID, params, state, cfg, num_steps, actions, action_step_stride, target_pos, obs12,
+                               obs_step_stride, reward, terminated, truncated, env_step_stride, tape, c, s))
+        return rc;
     const dim3 grid(blocks_for(c.num_envs, kBlock));
     diff_pid_dispatch(c, [&](auto aw) {
         hipLaunchKernelGGL((gpd_rollout_tape_pid_kernel<decltype(aw)::value>), grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), *params, s, c,
@@ -342,9 +252,9 @@ int gpd_rollout_vjp_pid(const GpdParams* params, const GpdStepCfg* cfg, int64_t 
     const Refuse bad{"gpd_rollout_vjp_pid"};
     if (!params || !cfg) return bad(GPD_EINVAL, "NULL params/cfg");
     if (!actions || !tape || !g_kin || !g_pid || !g_actions) return bad(GPD_EINVAL, "NULL actions/tape/g_kin/g_pid/g_actions");
-    if (int rc = diff_pid_cfg(bad, cfg, ld, num_steps, action_step_stride, obs_step_stride, env_step_stride)) return rc;
-    if (int rc = check_needs(bad, params, nullptr, cfg, target_pos, nullptr)) return rc;
-    if (misaligned16(tape) || misaligned16(g_kin)) return bad(GPD_EINVAL, "tape and g_kin must be 16-byte aligned");
+    if (int rc = sweep_prologue(bad, DiffFamily::PID, params, cfg, ld, num_steps, action_step_stride, obs_step_stride, env_step_stride,
+                                target_pos, tape, g_kin))
+        return rc;
     if (misaligned16(g_pid) || misaligned16(g_gains)) return bad(GPD_EINVAL, "g_pid and g_gains must be 16-byte aligned");
     if (cfg->act_type == GPD_ACT_VEL && misaligned16(g_actions)) return bad(GPD_EINVAL, "g_actions must be 16-byte aligned (GPD_ACT_VEL rows are stored as float4)");
     GpdStepCfg c = *cfg;

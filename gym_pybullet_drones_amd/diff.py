@@ -88,6 +88,38 @@ def derive_vjp(core, scales, g_rows, g_scales):
     _native.call("gpd_plant_derive_vjp", core.device, core._stream(), core._params, scales, g_rows, core.N, core.ld, g_scales)
 
 
+# ---- what the two autograd functions (RolloutDiff, RolloutDiffPid) share ---------------------------------------------------------------
+def _state0(core, x, own, name, layout):
+    """`kin0` / `pid0` of a call: None (the core's `own` block, `rows x ld`) or a tensor of as many elements, as float32 in its shape"""
+    if x is None:
+        return own.detach()
+    rows = own.numel() // core.ld
+    if x.numel() != own.numel():
+        raise ValueError(f"{name} has {x.numel()} elements, expected {rows} x ld = {rows * core.ld} ({layout})")
+    return x.to(device=core.device, dtype=torch.float32).reshape(own.shape).contiguous()
+
+
+def _outputs(core, K, size):
+    """fresh `(obs [K,N,12], rew [K,E], term [K,E], trunc [K,E], tape [size])` for a taped forward of K steps"""
+    dev, E = core.device, core.E
+    return (torch.empty((K, core.N, 12), dtype=torch.float32, device=dev), torch.empty((K, E), dtype=torch.float32, device=dev),
+            torch.empty((K, E), dtype=torch.bool, device=dev), torch.empty((K, E), dtype=torch.bool, device=dev),
+            torch.empty((size,), dtype=torch.float32, device=dev))
+
+
+def _cot(g, like=None):
+    """a cotangent as the sweeps take it: float32 and contiguous.  Of obs12 / reward (`like` None): None stays None, NULL = zeros; of a
+    state block: a COPY (the sweep overwrites it), None = zeros like `like`"""
+    if like is None:
+        return None if g is None else g.to(torch.float32).contiguous()
+    return torch.zeros_like(like) if g is None else g.to(torch.float32).clone(memory_format=torch.contiguous_format)
+
+
+def _action_grad(g_act, a_stride, actions):
+    """`g_act [K,N,A]` in the shape of `actions`; a shared action block's gradient is the sum over the steps"""
+    return (g_act.sum(dim=0) if a_stride == 0 else g_act).view(actions.shape)
+
+
 class RolloutDiff(torch.autograd.Function):
     """forward: `gpd_rollout_tape` from `kin0` (copied into the core's state first); backward: `gpd_rollout_vjp`, or -- when
     `plant_scales` (the scales `rollout_diff` has just installed with `set_plant`) asks for a gradient -- `gpd_rollout_vjp_plant`
@@ -95,15 +127,10 @@ class RolloutDiff(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, core, kin0, actions, K, a_stride, plant_scales=None, own_plant=False):
-        dev, N, E = core.device, core.N, core.E
         size = tape_floats(core, K)                            # (also the configuration check, before anything is touched)
         if kin0.data_ptr() != core.kin_store.data_ptr():
             core.kin_store.copy_(kin0)
-        obs = torch.empty((K, N, 12), dtype=torch.float32, device=dev)
-        rew = torch.empty((K, E), dtype=torch.float32, device=dev)
-        term = torch.empty((K, E), dtype=torch.bool, device=dev)
-        trunc = torch.empty((K, E), dtype=torch.bool, device=dev)
-        tape = torch.empty((size,), dtype=torch.float32, device=dev)
+        obs, rew, term, trunc, tape = _outputs(core, K, size)
         core.state_version += 1
         tape_forward(core, K, actions, a_stride, obs, rew, term, trunc, tape)
         kin_k = core.kin_store.clone()
@@ -126,21 +153,17 @@ class RolloutDiff(torch.autograd.Function):
         core, K = ctx.core, ctx.K
         actions, tape = ctx.saved_tensors
         dev, N = core.device, core.N
-        g_obs = None if g_obs is None else g_obs.to(torch.float32).contiguous()
-        g_rew = None if g_rew is None else g_rew.to(torch.float32).contiguous()
-        g_kin = torch.zeros_like(core.kin_store) if g_kin is None else g_kin.to(torch.float32).clone(memory_format=torch.contiguous_format)
+        g_kin = _cot(g_kin, core.kin_store)
         g_act = torch.empty((K, N, core.A), dtype=torch.float32, device=dev)
         with_scales = ctx.scales is not None and ctx.needs_input_grad[5]
         g_rows = torch.empty((_native.PLANT_ROWS, core.ld), dtype=torch.float32, device=dev) if with_scales else None     # (both kernels write drones 0 .. N-1)
-        sweep(core, K, actions, ctx.a_stride, tape, g_obs, g_rew, g_kin, g_act, ctx.target, ctx.plant, g_rows)
+        sweep(core, K, actions, ctx.a_stride, tape, _cot(g_obs), _cot(g_rew), g_kin, g_act, ctx.target, ctx.plant, g_rows)
         g_scales = None
         if with_scales:
             g_table = torch.empty((len(_native.SCALE_FIELDS), core.ld), dtype=torch.float32, device=dev)
             derive_vjp(core, ctx.scales, g_rows, g_table)
             g_scales = g_table[:, :N].reshape(ctx.scales_shape)
-        if ctx.a_stride == 0:                                  # a shared action block: its gradient is the sum over the steps
-            g_act = g_act.sum(dim=0)
-        return None, g_kin, g_act.view(actions.shape), None, None, g_scales, None
+        return None, g_kin, _action_grad(g_act, ctx.a_stride, actions), None, None, g_scales, None
 
 
 def rollout_diff(core, actions, kin0=None, num_steps: int = None, plant_scales=None):
@@ -154,12 +177,7 @@ def rollout_diff(core, actions, kin0=None, num_steps: int = None, plant_scales=N
     They REPLACE the core's plant table (`set_plant(plant_scales.detach())`, with its validation), the forward then is the one above;
     a float tensor `[9, E]` / `[9, E, 1]` that requires grad receives its gradient in its own shape."""
     actions, K, a_stride = core._action_blocks(actions, num_steps)
-    if kin0 is None:
-        kin0 = core.kin_store.detach()
-    else:
-        if kin0.numel() != 13 * core.ld:
-            raise ValueError(f"kin0 has {kin0.numel()} elements, expected 13 x ld = {13 * core.ld} (the plane layout: pack_kin)")
-        kin0 = kin0.to(device=core.device, dtype=torch.float32).reshape(-1).contiguous()
+    kin0 = _state0(core, kin0, core.kin_store, "kin0", "the plane layout: pack_kin")
     if plant_scales is None:
         return RolloutDiff.apply(core, kin0, actions, K, a_stride)
     tape_floats(core, K)                                       # (the configuration check, before the plant table is touched)
@@ -235,18 +253,13 @@ class RolloutDiffPid(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, core, kin0, pid0, actions, K, a_stride, pid_gains=None):
-        dev, N, E = core.device, core.N, core.E
         size = tape_floats_pid(core, K)                        # (also the configuration check, before anything is touched)
         params = core._params if pid_gains is None else params_with_gains(core._params, pid_gains)
         if kin0.data_ptr() != core.kin_store.data_ptr():
             core.kin_store.copy_(kin0)
         if pid0.data_ptr() != core.pid.data_ptr():
             core.pid.copy_(pid0.view(9, core.ld))
-        obs = torch.empty((K, N, 12), dtype=torch.float32, device=dev)
-        rew = torch.empty((K, E), dtype=torch.float32, device=dev)
-        term = torch.empty((K, E), dtype=torch.bool, device=dev)
-        trunc = torch.empty((K, E), dtype=torch.bool, device=dev)
-        tape = torch.empty((size,), dtype=torch.float32, device=dev)
+        obs, rew, term, trunc, tape = _outputs(core, K, size)
         core.state_version += 1
         tape_forward_pid(core, params, K, actions, a_stride, obs, rew, term, trunc, tape)
         kin_k, pid_k = core.kin_store.clone(), core.pid.clone()
@@ -265,21 +278,16 @@ class RolloutDiffPid(torch.autograd.Function):
         core, K = ctx.core, ctx.K
         actions, tape = ctx.saved_tensors
         dev, N = core.device, core.N
-        g_obs = None if g_obs is None else g_obs.to(torch.float32).contiguous()
-        g_rew = None if g_rew is None else g_rew.to(torch.float32).contiguous()
-        g_kin = torch.zeros_like(core.kin_store) if g_kin is None else g_kin.to(torch.float32).clone(memory_format=torch.contiguous_format)
-        g_pid = torch.zeros_like(core.pid) if g_pid is None else g_pid.to(torch.float32).clone(memory_format=torch.contiguous_format)
+        g_kin, g_pid = _cot(g_kin, core.kin_store), _cot(g_pid, core.pid)
         g_act = torch.empty((K, N, core.A), dtype=torch.float32, device=dev)
         with_gains = ctx.with_gains and ctx.needs_input_grad[6]
         g_rows = torch.zeros((18, core.ld), dtype=torch.float32, device=dev) if with_gains else None     # (the kernel writes drones 0 .. N-1)
-        sweep_pid(core, ctx.params, K, actions, ctx.a_stride, tape, g_obs, g_rew, g_kin, g_pid, g_act, g_rows, ctx.target)
+        sweep_pid(core, ctx.params, K, actions, ctx.a_stride, tape, _cot(g_obs), _cot(g_rew), g_kin, g_pid, g_act, g_rows, ctx.target)
         g_gains = None
         if with_gains:         # the forward's gains are shared: the sum over drones, in float64 (N terms), in the caller's shape and place
             shape, dtype, device = ctx.gains_like
             g_gains = g_rows[:, :N].sum(dim=1, dtype=torch.float64).reshape(6, 3).to(device=device, dtype=dtype).reshape(shape)
-        if ctx.a_stride == 0:                                  # a shared action block: its gradient is the sum over the steps
-            g_act = g_act.sum(dim=0)
-        return None, g_kin, g_pid, g_act.view(actions.shape), None, None, g_gains
+        return None, g_kin, g_pid, _action_grad(g_act, ctx.a_stride, actions), None, None, g_gains
 
 
 def rollout_diff_pid(core, actions, kin0=None, pid0=None, num_steps: int = None, pid_gains=None):
@@ -302,18 +310,8 @@ def rollout_diff_pid(core, actions, kin0=None, pid0=None, num_steps: int = None,
         raise _native.GpdError("rollout_diff_pid: this core has no DSLPID controller (no controller members, or an airframe without one)")
     if core._state.dw_force:
         raise _native.GpdError("rollout_diff_pid: downwash computed outside the kernel (state.dw_force) is not differentiable")
-    if kin0 is None:
-        kin0 = core.kin_store.detach()
-    else:
-        if kin0.numel() != 13 * core.ld:
-            raise ValueError(f"kin0 has {kin0.numel()} elements, expected 13 x ld = {13 * core.ld} (the plane layout: pack_kin)")
-        kin0 = kin0.to(device=core.device, dtype=torch.float32).reshape(-1).contiguous()
-    if pid0 is None:
-        pid0 = core.pid.detach()
-    else:
-        if pid0.numel() != 9 * core.ld:
-            raise ValueError(f"pid0 has {pid0.numel()} elements, expected 9 x ld = {9 * core.ld} (the rows of the controller members: pack_pid)")
-        pid0 = pid0.to(device=core.device, dtype=torch.float32).reshape(9, core.ld).contiguous()
+    kin0 = _state0(core, kin0, core.kin_store, "kin0", "the plane layout: pack_kin")
+    pid0 = _state0(core, pid0, core.pid, "pid0", "the rows of the controller members: pack_pid")
     if pid_gains is not None:
         if not isinstance(pid_gains, torch.Tensor) or pid_gains.numel() != 18:
             raise ValueError("pid_gains must be a tensor of 6 x 3 gains (rows: p_for, i_for, d_for, p_tor, i_tor, d_tor)")
