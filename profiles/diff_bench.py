@@ -143,6 +143,9 @@ def main():
         print(f"S={S}", json.dumps(u), flush=True)
     if a.grad_figures and os.path.exists(a.grad_figures):
         res["gradient_error_vs_float64"] = json.load(open(a.grad_figures))
+    elif a.out and os.path.exists(a.out):                      # (new timings keep the figures tests/test_gpu_diff.py recorded there)
+        kept = json.load(open(a.out))
+        res.update({k: kept[k] for k in ("metric", "bound_rule", "gradient_error_vs_float64") if k in kept})
     if a.registers and os.path.exists(a.registers):
         res["registers"] = json.load(open(a.registers))
     print(json.dumps(res))

@@ -6,7 +6,11 @@ reference the device gradients are held against, and its forward is held against
 Selects are written so that the branch NOT taken cannot produce NaN gradients (`torch.where` multiplies the untaken branch's gradient
 by zero, and 0 * inf = NaN): every operand of an untaken branch is replaced by a harmless one first.  A plain sin(t) / |w| is NaN at rest.
 
-The same file holds the input generator of the GPU tests (`make_inputs`).  Test infrastructure."""
+`stats` (a dict) records the extremes a run met at each select -- the gimbal test, the no-turn test, the tumbling test, the reward clamp --
+and, under "lanes", the same per drone (`_lanes`): which lanes sat on which side, at every step and sub-step.
+
+The same file holds the input generators of the GPU tests: `make_inputs` (near hover, far from every threshold) and `make_edge_inputs`
+(part of the lanes on the far side of a select, with margin).  Test infrastructure."""
 import math
 from types import SimpleNamespace
 
@@ -56,6 +60,15 @@ def rpm_from_action(c, cfg, a):
     return a
 
 
+def _lanes(stats, key, value):
+    """per-lane record of a run: stats["lanes"][key] = (min, max) over every evaluation, each a float64 array [n] -- what the scalar
+    minima and maxima of `stats` cannot tell: how many lanes sat on which side of a select, and for how long"""
+    v = value.detach().to(torch.float64).numpy()
+    lanes = stats.setdefault("lanes", {})
+    lo, hi = lanes.get(key, (v, v))
+    lanes[key] = (np.minimum(lo, v), np.maximum(hi, v))
+
+
 def rotation(q):
     """btMatrix3x3::setRotation: columns-of-rows list R[i][j], each [n]"""
     x, y, z, w = q.unbind(-1)
@@ -75,6 +88,7 @@ def euler(q, stats=None):
     gim = lo | hi
     if stats is not None:
         stats["sarg_max"] = max(stats.get("sarg_max", 0.0), float(sarg.detach().abs().max()))
+        _lanes(stats, "sarg_abs", sarg.abs())
     one, zero = torch.ones_like(x), torch.zeros_like(x)
     # regular branch on safe operands where the gimbal branch is taken ...
     rb = torch.where(gim, one, w * w - x * x - y * y + z * z)
@@ -118,6 +132,9 @@ def substep(c, cfg, kin, rpm, drag_sum, stats=None):
     turn = n2 > TURN_N2                                            # !np.isclose(|w|, 0)
     if stats is not None:
         stats["n2_min"] = min(stats.get("n2_min", math.inf), float(n2.detach().min()))
+        stats["u_max"] = max(stats.get("u_max", 0.0), float(n2.detach().max()) * (0.25 * h * h))
+        _lanes(stats, "n2", n2)
+        _lanes(stats, "u", n2 * (0.25 * h * h))                       # (the half-angle squared: the kernels' tumbling test is u > 1)
     n = torch.sqrt(torch.where(turn, n2, torch.ones_like(n2)))     # (safe: sqrt and the division never see 0)
     th = n * h / 2
     qx, qy, qz, qw = quat.unbind(-1)
@@ -143,6 +160,7 @@ def step(c, cfg, kin, act, prev_sum, target=None, stats=None):
         arg = 2.0 - d2 * d2
         if stats is not None:
             stats["reward_arg_min"] = min(stats.get("reward_arg_min", math.inf), float(arg.detach().min()))
+            _lanes(stats, "reward_arg", arg)
         reward = torch.where(arg > 0, arg, torch.zeros_like(arg))
     else:
         reward = -torch.ones_like(pos[:, 0])
@@ -231,6 +249,13 @@ def group_errors(got, want):
     return {k: float(np.abs(np.asarray(got[k], dtype=np.float64) - want[k]).max() / max(float(np.abs(want[k]).max()), 1e-300)) for k in GROUPS}
 
 
+def forward_error(obs, obs64):
+    """the forward obs12 [K, n, 12] against the float64 run, relative to each column's scale: the largest over the columns of
+    max |obs - obs64| / max(1, max |obs64|) (absolute for columns of order one; the angular velocity of a tumbling drone is not)"""
+    obs, obs64 = np.asarray(obs, dtype=np.float64), np.asarray(obs64, dtype=np.float64)
+    return float((np.abs(obs - obs64).max(axis=(0, 1)) / np.maximum(1.0, np.abs(obs64).max(axis=(0, 1)))).max())
+
+
 #: the gradient cases of tests/test_gpu_diff.py (and of the host tests that vouch for the reference on the same inputs): 70 drones
 #: (ld = 128: two waves, one ragged), task hover.  `scales`: plant scale factors drawn within +-20 %.
 GPU_CASES = {
@@ -251,3 +276,114 @@ def case(name, n=70, seed=1):
     K, with_scales = d.pop("K"), d.pop("scales", False)
     scales = np.asarray(np.random.default_rng(seed + 100).uniform(0.8, 1.2, (9, n)), dtype=np.float32).astype(np.float64) if with_scales else None
     return config(**d), K, scales
+
+
+# ---- the far side of the selects ---------------------------------------------------------------------------------------------------
+#: the edge cases of tests/test_gpu_diff.py (and of the host tests that establish their conditions): 200 drones (ld = 256: four waves),
+#: task hover, one airframe per kind and all three over the table (the sub-step's adjoint branches on the airframe).  `tumble` keeps
+#: K S at 4 sub-steps: explicit Euler amplifies the off-axis rates by about 1.7x per sub-step at those speeds.
+EDGE_CASES = {
+    "tumble": dict(model="cf2x", act="rpm", S=2, drag=False, K=2),
+    "gimbal": dict(model="racer", act="one_d_rpm", S=2, drag=False, K=3),
+    "near_gimbal": dict(model="racer", act="one_d_rpm", S=2, drag=False, K=3),
+    "reward_far": dict(model="cf2x", act="rpm", S=2, drag=True, K=4),
+    "wide_attitude": dict(model="cf2p", act="rpm", S=2, drag=True, K=4),
+}
+EDGE_N = 200
+#: pitch of the `near_gimbal` lanes: sin(85 deg) = 0.99619, 3.8e-3 below the gimbal test, 1 / cos(pitch) = 11.5.  Nearer is not a
+#: float32 question any more: the asin adjoint divides by sqrt((1 - s)(1 + s)) of an s that float32 products round at 3e-8, and the
+#: float32 restatement itself leaves the 1e-5 rule of tests/test_host_diff.py (86.5 deg: 8e-6 .. 1.0e-5 over three draws, 88 deg --
+#: which also sits inside the 1e-3 every lane keeps from every threshold -- 1.5e-5 .. 2.5e-5; 85 deg: below 3e-6)
+NEAR_GIMBAL_PITCH = math.radians(85.0)
+
+
+def edge_case(kind):
+    """(cfg, K) of an edge case"""
+    d = dict(EDGE_CASES[kind])
+    K = d.pop("K")
+    return config(**d), K
+
+
+TUMBLE_PLANT_K = 1
+
+
+def edge_scales(n=EDGE_N, seed=1):
+    """plant scale factors [9, n] within +-20 %, every value a float32: `tumble` through the plant sweep, which flies the first step
+    alone (TUMBLE_PLANT_K) -- with unequal inertias the second step's float32 restatement comes within 3 % of the 1e-5 rule"""
+    return np.asarray(np.random.default_rng(seed + 100).uniform(0.8, 1.2, (9, n)), dtype=np.float32).astype(np.float64)
+
+
+def rare_lanes(n=EDGE_N):
+    """bool [n]: every third drone among drones 0 .. 127"""
+    i = np.arange(n)
+    return (i % 3 == 0) & (i < 128)
+
+
+def make_edge_inputs(C, cfg, n, K, kind, seed=1):
+    """`make_inputs` with the RARE lanes moved to the far side of a select, every value representable in float32.  The rare lanes are
+    every third drone among drones 0 .. 127 (`rare_lanes`): with n = 200 the lanes of waves 0 and 1 diverge and waves 2 and 3 hold
+    ordinary lanes only; every other lane is `make_inputs`' own.  By `kind`:
+      tumble         body rates of 520 .. 700 rad/s, about z for every other rare lane and about a random body axis for the rest: more
+                     than 1 rad per sub-step (u = (|w| h / 2)^2 > 1 beyond 480 rad/s), the exact sincos path of the quaternion update
+      gimbal         pitch exactly +-pi/2 (alternating), roll 0, a random yaw, body rates zero.  Meant for ONE_D_RPM: four equal thrusts
+                     give no torque, the rates stay zero and the lane stays in the gimbal branch at every step
+      near_gimbal    the same lanes at pitch +-85 deg (NEAR_GIMBAL_PITCH): the regular branch where 1 / cos(pitch) is 11.5
+      reward_far     1.25 .. 1.6 m from the target in a random direction: 2 - d^4 <= -0.44, the clamped side of the reward
+      wide_attitude  roll and yaw anywhere in +-3.1 rad, pitch in +-1.3 rad, the quaternion's sign random (w < 0 for half of them) and
+                     its length 0.95 .. 1.05, capped so that |q|^2 |sin pitch| <= 0.97: the gimbal test reads the unnormalised
+                     2 (w y - x z), and the cap keeps these lanes on its regular side with room for the flight's drift
+    numpy float64 arrays, plus `rare` (bool [n])."""
+    inp = make_inputs(C, cfg, n, K, seed=seed)
+    rng = np.random.default_rng(seed + 1000)
+    f32 = lambda x: np.asarray(x, dtype=np.float32).astype(np.float64)     # noqa: E731
+    rare = rare_lanes(n)
+    m = int(rare.sum())
+    if kind == "tumble":
+        axis = rng.standard_normal((m, 3))
+        axis /= np.linalg.norm(axis, axis=-1, keepdims=True)
+        axis[::2] = np.array([0.0, 0.0, 1.0])
+        inp.rates[rare] = f32(axis * (rng.uniform(520.0, 700.0, (m, 1)) * rng.choice([-1.0, 1.0], (m, 1))))
+    elif kind in ("gimbal", "near_gimbal"):
+        pitch = (0.5 * math.pi if kind == "gimbal" else NEAR_GIMBAL_PITCH) * np.where(np.arange(m) % 2 == 0, 1.0, -1.0)
+        rpy = np.stack([np.zeros(m), pitch, rng.uniform(-3.1, 3.1, m)], axis=-1)
+        inp.quat[rare] = f32(quat_from_rpy(rpy))
+        inp.rates[rare] = 0.0
+    elif kind == "reward_far":
+        direction = rng.standard_normal((m, 3))
+        direction /= np.linalg.norm(direction, axis=-1, keepdims=True)
+        inp.pos[rare] = f32(inp.target[rare] + direction * rng.uniform(1.25, 1.6, (m, 1)))
+    elif kind == "wide_attitude":
+        rpy = np.stack([rng.uniform(-3.1, 3.1, m), rng.uniform(-1.3, 1.3, m), rng.uniform(-3.1, 3.1, m)], axis=-1)
+        length = np.minimum(rng.uniform(0.95, 1.05, m), np.sqrt(0.97 / np.maximum(np.abs(np.sin(rpy[:, 1])), 1e-3)))
+        inp.quat[rare] = f32(quat_from_rpy(rpy) * (length * rng.choice([-1.0, 1.0], m))[:, None])
+    else:
+        raise ValueError(f"unknown edge kind {kind!r}")
+    inp.rare = rare
+    return inp
+
+
+def with_cotangents(inp, g_obs=None, g_rew=None):
+    """a copy of the inputs whose cotangents are zero but for the given ones (`g_obs` [K, n, 12], `g_rew` [K, n])"""
+    out = SimpleNamespace(**vars(inp))
+    out.g_obs = np.zeros_like(inp.g_obs) if g_obs is None else g_obs
+    out.g_rew = np.zeros_like(inp.g_rew) if g_rew is None else g_rew
+    for k in ("g_pos", "g_quat", "g_vel", "g_rates"):
+        setattr(out, k, np.zeros_like(getattr(inp, k)))
+    return out
+
+
+def first_steps(inp, k):
+    """the inputs cut to their first k steps"""
+    out = SimpleNamespace(**vars(inp))
+    out.K, out.actions, out.g_obs, out.g_rew = k, inp.actions[:k], inp.g_obs[:k], inp.g_rew[:k]
+    return out
+
+
+def lanes_of(inp, idx):
+    """the inputs of the drones `idx` alone (every per-drone array sliced)"""
+    out, idx = SimpleNamespace(**vars(inp)), np.asarray(idx)
+    for k, v in vars(inp).items():
+        if isinstance(v, np.ndarray):
+            setattr(out, k, v[:, idx] if k in ("actions", "g_obs", "g_rew") else v[idx])
+    out.n = len(idx)
+    return out

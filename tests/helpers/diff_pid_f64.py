@@ -154,6 +154,7 @@ def step(c, pc, cfg, kin, mem, act, target=None, stats=None):
         arg = 2.0 - d2 * d2
         if stats is not None:
             stats["reward_arg_min"] = min(stats.get("reward_arg_min", math.inf), float(arg.detach().min()))
+            ref._lanes(stats, "reward_arg", arg)
         reward = torch.where(arg > 0, arg, torch.zeros_like(arg))
     else:
         reward = -torch.ones_like(pos[:, 0])
@@ -179,6 +180,7 @@ GPU_CASES = {
     "cf2p_vel_k6_s5": dict(model="cf2p", act="vel", S=5, K=6, kind="plain", seed=7),
     "sat_int_k10_s5": dict(model="cf2x", act="pid", S=5, K=10, kind="sat_int", seed=472),
     "sat_pwm_k4_s5": dict(model="cf2x", act="vel", S=5, K=4, kind="sat_pwm", seed=59),
+    "far_vel_k4_s5": dict(model="cf2x", act="vel", S=5, K=4, kind="reward_far", seed=1),
 }
 # The seeds were chosen on the CPU, by this file alone: among the generator's draws, one whose float32 run of the restatement stays
 # within 1e-5 of its float64 run in every group and whose drone-steps all keep 1e-3 (relative) from every select threshold
@@ -191,6 +193,8 @@ GPU_CASES = {
 
 #: the shared-action test flies the first block of "vel_k8_s5"'s generator at every step; its seed was chosen by the same two rules
 SHARED_SEED = 5
+#: the size sweep flies "vel_k8_s5" at other N, where the generator's draws are others: a seed per N, chosen by the same two rules
+SIZE_SEEDS = {1: 1, 64: 4, 65: 5}
 
 
 def case(name):
@@ -213,7 +217,9 @@ def make_inputs(C, cfg, n, K, seed=0, kind="plain"):
                  engaged); the others carry 0.02 .. 0.08 and cannot reach it (z errors of +-0.2 m move the integral by 0.04 in 10 steps)
       "sat_pwm"  vel commands upwards at full speed fraction to a drone that descends at 0.2 .. 1 m/s: the thrust the velocity error
                  asks for (d_for_z = 0.5 N per m/s against a hover thrust of 0.26 N and a ceiling of 2.25 times that) pushes the
-                 rotors of part of the drones to MAX_PWM"""
+                 rotors of part of the drones to MAX_PWM
+      "reward_far"  every other drone 1.25 .. 1.6 m from the target in a random direction: 2 - d^4 <= -0.44 at every step, the clamped
+                 side of the reward (under VEL the target position is the position itself: the flight is the plain one)"""
     rng = np.random.default_rng(seed)
     f32 = lambda x: np.asarray(x, dtype=np.float32).astype(np.float64)     # noqa: E731
     A = ACT_DIM[cfg.act]
@@ -227,6 +233,11 @@ def make_inputs(C, cfg, n, K, seed=0, kind="plain"):
         vel[:, 2] = f32(-rng.uniform(0.2, 1.0, n))
     quat = f32(ref.quat_from_rpy(rpy0))
     last_rpy = f32(rpy0 + rng.uniform(-2e-4, 2e-4, (n, 3)))
+    if kind == "reward_far":
+        far_rng = np.random.default_rng(seed + 1000)               # (a generator of its own: the other draws are the plain kind's)
+        direction = far_rng.standard_normal(((n + 1) // 2, 3))
+        direction /= np.linalg.norm(direction, axis=-1, keepdims=True)
+        pos[::2] = f32(np.array([0.0, 0.0, 1.0]) + direction * far_rng.uniform(1.25, 1.6, ((n + 1) // 2, 1)))
     if cfg.act == "pid":
         direction = rng.standard_normal((K, n, 3))
         direction /= np.linalg.norm(direction, axis=-1, keepdims=True)

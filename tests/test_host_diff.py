@@ -1,5 +1,7 @@
 """The differentiable rollout without a GPU: the float64 yardstick (tests/helpers/diff_f64.py) held against the batched oracle and
-against finite differences, its float32 run against its float64 run on the GPU tests' inputs, the safety caps of those inputs, and the
+against finite differences (on the far side of the tumbling and gimbal selects too), its float32 run against its float64 run on the GPU
+tests' inputs, the safety caps of those inputs, the conditions of the edge cases (which lanes sit on which side of every select, with
+what margin), and the
 host side of the three new entries (include/gpd.h `gpd_rollout_tape_floats` / `gpd_rollout_tape` / `gpd_rollout_vjp`): the size query,
 every rejected configuration with its code and message, and tests/c/diff_host.c under AddressSanitizer + UBSan against the launch stub."""
 import ctypes
@@ -100,6 +102,153 @@ def test_gpu_inputs_stay_inside_the_references_safety_caps(case_runs, name):
         assert np.minimum(np.abs(a), np.abs(a - C.MAX_RPM)).min() > 1e-3
         outside = ((a < 0) | (a > C.MAX_RPM)).mean()
         assert 0.25 < outside < 0.42, outside          # "a third of the actions outside the clip"
+
+
+# ---- the far side of the selects: the conditions of the edge cases (conditions, not measurements) -------------------------------------
+@pytest.fixture(scope="module")
+def edge_runs():
+    """every edge case once, as `case_runs`: the statistics now per lane"""
+    out = {}
+    for kind in ref.EDGE_CASES:
+        cfg, K = ref.edge_case(kind)
+        C = _params(cfg.model)
+        inp = ref.make_edge_inputs(C, cfg, ref.EDGE_N, K, kind)
+        stats = {}
+        g64 = ref.reference_grads(C, cfg, inp, torch.float64, stats=stats)
+        g32 = ref.reference_grads(C, cfg, inp, torch.float32)
+        out[kind] = (C, cfg, inp, g64, g32, stats)
+    return out
+
+
+def _sides(stats):
+    """per lane, over every step and sub-step of a run: which side of each select it sat on, or neither (inside the margin).  The
+    margins: 1e-3 below and 5e-6 above the gimbal test, 1e-3 on either side of the reward clamp, a factor 100 above the no-turn test
+    or exactly at rest, 1e-2 on either side of the tumbling test u = 1."""
+    L = stats["lanes"]
+    return dict(gimbal=L["sarg_abs"][0] >= ref.GIMBAL + 5e-6, regular=L["sarg_abs"][1] < ref.GIMBAL - 1e-3,
+                far=L["reward_arg"][1] < -1e-3, near=L["reward_arg"][0] > 1e-3,
+                turning=L["n2"][0] > 100 * ref.TURN_N2, at_rest=L["n2"][1] == 0.0,
+                tumbling=L["u"][0] - 1.0 > 1e-2, slow=L["u"][1] < 1.0 - 1e-2)
+
+
+#: the side the rare lanes of each kind sit on at every step and sub-step (every other select: the ordinary side)
+RARE_SIDE = {"tumble": {"tumbling"}, "gimbal": {"gimbal", "at_rest"}, "near_gimbal": {"at_rest"}, "reward_far": {"far"}, "wide_attitude": set()}
+
+
+def test_edge_cases_cover_the_three_airframes_on_four_waves():
+    assert {d["model"] for d in ref.EDGE_CASES.values()} == {"cf2x", "cf2p", "racer"}
+    assert ref.EDGE_N == 200 and (ref.EDGE_N + 63) // 64 == 4
+    rare = ref.rare_lanes()
+    assert rare[:128:3].all() and rare.sum() == 43 and not rare[128:].any()          # waves 0 and 1 diverge, waves 2 and 3 do not
+    assert ref.EDGE_CASES["tumble"]["K"] * ref.EDGE_CASES["tumble"]["S"] <= 8
+
+
+@pytest.mark.parametrize("kind", list(ref.EDGE_CASES))
+def test_edge_inputs_sit_on_the_intended_side_of_every_select_with_margin(edge_runs, kind):
+    """the rare lanes on the far side at EVERY step and sub-step with the margins of `_sides`, every other lane -- and the rare lanes at
+    every other select -- on the ordinary side with the margins of the GPU cases: float32 and float64 take the same branches.  Both
+    sides are populated: at least 40 rare lanes and 100 ordinary ones."""
+    _, cfg, inp, _, _, stats = edge_runs[kind]
+    side, rare = _sides(stats), inp.rare
+    assert rare.sum() >= 40 and (~rare).sum() >= 100
+    for far, ordinary in (("gimbal", "regular"), ("far", "near"), ("at_rest", "turning"), ("tumbling", "slow")):
+        assert (side[far] | side[ordinary]).all(), (far, ordinary)                  # (no lane inside a margin, or on both sides in turn)
+        want = rare if far in RARE_SIDE[kind] else np.zeros_like(rare)
+        assert np.array_equal(side[far], want), far
+    L = stats["lanes"]
+    if kind == "tumble":
+        assert stats["u_max"] > 1.0 + 1e-2 and L["u"][0][rare].min() - 1.0 > 1e-2 and L["u"][1][~rare].max() < 1e-3
+        assert np.count_nonzero(inp.rates[rare, :2].any(axis=1)) >= 20 and np.count_nonzero(~inp.rates[rare, :2].any(axis=1)) >= 20     # off z, about z
+    if kind == "gimbal":
+        assert L["sarg_abs"][0][rare].min() >= ref.GIMBAL + 5e-6 and L["sarg_abs"][1][rare].max() > 1.0      # (some above 1: rsq of a negative)
+    if kind == "near_gimbal":
+        assert L["sarg_abs"][0][rare].min() > 0.99 and L["sarg_abs"][1][rare].max() < ref.GIMBAL - 1e-3
+    if kind == "reward_far":
+        assert L["reward_arg"][1][rare].max() < -1e-3 and L["reward_arg"][0][~rare].min() > 1e-3
+    if kind == "wide_attitude":
+        q = inp.quat[rare]
+        length = np.linalg.norm(q, axis=1)
+        assert (q[:, 3] < 0).sum() >= 10 and (q[:, 3] > 0).sum() >= 10
+        assert (length < 0.99).sum() >= 10 and (length > 1.01).sum() >= 5 and L["sarg_abs"][1][rare].max() > 0.9
+
+
+@pytest.mark.parametrize("kind", list(ref.EDGE_CASES))
+def test_float32_restatement_follows_the_float64_one_on_the_edge_inputs(edge_runs, kind):
+    """the rule of the GPU cases, unchanged: max |g32 - g64| / max |g64| per group below 1e-5 on the restatement itself, finite
+    gradients, and a forward whose float32 run stays within 1e-5 of each observation column's scale"""
+    _, _, _, g64, g32, _ = edge_runs[kind]
+    err = ref.group_errors(g32, g64)
+    print(kind, {k: f"{v:.1e}" for k, v in err.items()})
+    assert max(err.values()) < 1e-5, err
+    assert all(np.isfinite(g[k]).all() and np.abs(g[k]).max() > 0 for k in ref.GROUPS for g in (g64, g32))
+    assert ref.forward_error(g32["forward"][0].numpy(), g64["forward"][0].numpy()) < 1e-5
+    # the GPU test also holds the rare lanes on their own (a larger gradient elsewhere must not hide them): the same rule there
+    rare = edge_runs[kind][2].rare
+    lanes = lambda g: {k: (g[k][:, rare] if k == "actions" else g[k][rare]) for k in ref.GROUPS}     # noqa: E731
+    err = ref.group_errors(lanes(g32), lanes(g64))
+    print(kind, "rare lanes", {k: f"{v:.1e}" for k, v in err.items()})
+    assert max(err.values()) < 1e-5, err
+
+
+def test_tumbling_with_plant_scales_meets_the_same_conditions():
+    """`tumble` with per-drone scales within +-20 % and the scales as leaves (the GPU suite's run through gpd_rollout_vjp_plant, the first
+    step of the case): the rare lanes tumble at every sub-step, nobody else does, every other select keeps its margin, and the float32 restatement stays
+    within 1e-5 of the float64 one -- the five groups and every scale the configuration reads"""
+    import sysid_f64 as sid
+    cfg, K = ref.edge_case("tumble")
+    C = _params(cfg.model)
+    inp, scales = ref.first_steps(ref.make_edge_inputs(C, cfg, ref.EDGE_N, K, "tumble"), ref.TUMBLE_PLANT_K), ref.edge_scales()
+    stats = {}
+    g64 = ref.reference_grads(C, cfg, inp, torch.float64, scales, stats=stats, wrt_scales=True)
+    g32 = ref.reference_grads(C, cfg, inp, torch.float32, scales, wrt_scales=True)
+    side = _sides(stats)
+    assert np.array_equal(side["tumbling"], inp.rare) and np.array_equal(side["slow"], ~inp.rare)
+    assert side["regular"].all() and side["near"].all() and side["turning"].all()
+    err = dict(ref.group_errors(g32, g64), **sid.scale_errors(g32["scales"], g64["scales"]))
+    print({k: f"{v:.1e}" for k, v in err.items()})
+    assert set(err) == set(ref.GROUPS) | {"mass", "ixx", "iyy", "izz", "kf", "km"}
+    assert max(err.values()) < 1e-5, err
+
+
+@pytest.mark.parametrize("n", [1, 64, 65, 257])
+def test_size_sweep_inputs_meet_the_rules_of_the_gpu_cases(n):
+    """the GPU suite's size sweep (RPM, S = 2, K = 4, drag, `make_inputs` at N drones): the 1e-5 rule and the safety caps at every N"""
+    cfg = ref.config("cf2x", "rpm", 2, True, "hover")
+    C = _params("cf2x")
+    inp = ref.make_inputs(C, cfg, n, 4, seed=1)
+    stats = {}
+    g64 = ref.reference_grads(C, cfg, inp, torch.float64, stats=stats)
+    err = ref.group_errors(ref.reference_grads(C, cfg, inp, torch.float32), g64)
+    assert max(err.values()) < 1e-5, err
+    assert stats["sarg_max"] < ref.GIMBAL - 1e-3 and stats["reward_arg_min"] > 1e-3 and stats["n2_min"] > 100 * ref.TURN_N2 and stats["u_max"] < 1e-3
+
+
+@pytest.mark.parametrize("kind", ["tumble", "gimbal", "wide_attitude"])
+def test_restatement_gradients_pass_gradcheck_on_the_far_side(kind):
+    """the yardstick itself on the far side of the tumbling and gimbal selects and at wide attitudes: float64 autograd against finite
+    differences on 3 rare lanes (drones 0, 3 and 6 of a draw of 7), the eps and tolerances of the gradcheck above"""
+    cfg, K = ref.edge_case(kind)
+    C = _params(cfg.model)
+    inp = ref.lanes_of(ref.make_edge_inputs(C, cfg, 7, K, kind, seed=5), [0, 3, 6])
+    if kind == "gimbal":
+        # The gimbal lanes are at rest, and the no-turn select is a kink of its own: the function as executed keeps q there, a finite
+        # difference in the rates leaves it.  Here they roll instead: at pitch +-pi/2 the body's x axis is the vertical, a roll rate
+        # turns the yaw alone, J w is parallel to w and nothing makes a torque -- the lane turns and stays in the gimbal branch.
+        inp.rates[:, 0] = np.array([0.75, -0.5, 0.25])
+    c = ref.consts(C, 3)
+    T = lambda v: torch.as_tensor(v, dtype=torch.float64)     # noqa: E731
+    stats = {}
+
+    def f(pos, quat, vel, rates, a, st=None):
+        obs, rew, kin = ref.rollout(c, cfg, (pos, quat, vel, rates), a, T(inp.first_sum), T(inp.target), st)
+        return torch.cat([obs.reshape(-1), rew.reshape(-1)] + [k.reshape(-1) for k in kin])
+
+    args = [T(v).clone().requires_grad_(True) for v in (inp.pos, inp.quat, inp.vel, inp.rates, inp.actions)]
+    f(*args, st=stats)
+    side = _sides(stats)
+    assert inp.rare.all() and all(side[k].all() for k in RARE_SIDE[kind] - ({"at_rest"} if kind == "gimbal" else set()))
+    assert all((side[a] | side[b]).all() for a, b in (("gimbal", "regular"), ("far", "near"), ("at_rest", "turning"), ("tumbling", "slow")))
+    assert torch.autograd.gradcheck(f, args, eps=1e-6, atol=1e-6, rtol=1e-5)
 
 
 def test_at_rest_inputs_take_the_no_turn_branch_with_finite_gradients():

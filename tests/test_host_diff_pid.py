@@ -1,6 +1,6 @@
 """The differentiable rollout through the DSLPID loop without a GPU: the float64 yardstick (tests/helpers/diff_pid_f64.py) held against the
-batched oracle and against finite differences, its float32 run against its float64 run on the GPU tests' inputs, those inputs' distance
-to every select threshold, csrc/dslpid_vjp.inc evaluated on the host against float64 autograd of the restatement's controller, and the
+batched oracle and against finite differences, its float32 run against its float64 run on the GPU tests' inputs (the size sweep's
+included), those inputs' distance to every select threshold (the drones of the far case: beyond the reward clamp at every step), csrc/dslpid_vjp.inc evaluated on the host against float64 autograd of the restatement's controller, and the
 host side of the three entries (include/gpd.h `gpd_rollout_tape_pid_floats` / `gpd_rollout_tape_pid` / `gpd_rollout_vjp_pid`):
 tests/c/diff_pid_host.c under AddressSanitizer + UBSan against the launch stub."""
 import ctypes
@@ -127,7 +127,14 @@ def test_gpu_inputs_keep_their_distance_from_every_select_threshold(case_runs, n
     want = {"int_pos_2", "int_pos_z_0.15", "int_rpy_1500", "int_rpy_xy_1", "torque_3200", "pwm_limits", "along_0", "gimbal"} | ({"approach_1m"} if cfg.act == "pid" else set())
     assert set(near) == want
     assert min(near.values()) >= 1e-3, near
-    assert stats["reward_arg_min"] > 1e-3 and stats["n2_min"] > 100 * ref.TURN_N2
+    assert stats["n2_min"] > 100 * ref.TURN_N2
+    lo, hi = stats["lanes"]["reward_arg"]
+    if name == "far_vel_k4_s5":
+        # every other drone beyond the reward clamp at ALL steps (2 - d^4 below -1e-3 throughout), the others inside it throughout
+        far = hi < -1e-3
+        assert np.array_equal(far, np.arange(70) % 2 == 0) and (lo[~far] > 1e-3).all() and far.sum() == 35
+    else:
+        assert stats["reward_arg_min"] > 1e-3
     if name == "sat_int_k10_s5":
         assert stats["int_z_saturated"] >= 70 and stats["int_z_free"] >= 70, stats
     if name == "sat_pwm_k4_s5":
@@ -147,6 +154,21 @@ def test_shared_action_inputs_meet_the_same_two_rules():
     err = pref.group_errors(pref.reference_grads(C, cfg, inp, torch.float32, shared_action=True), g64)
     assert g64["actions"].shape == (1, 70, 4) and max(err.values()) < 1e-5, err
     assert min(stats["near"].values()) >= 1e-3 and (ref.GIMBAL - stats["sarg_max"]) / ref.GIMBAL >= 1e-3, stats["near"]
+
+
+@pytest.mark.parametrize("n", sorted(pref.SIZE_SEEDS))
+def test_size_sweep_inputs_meet_the_same_two_rules(n):
+    """the GPU suite's size sweep ("vel_k8_s5" at N = 1, 64 and 65 with the seeds of pref.SIZE_SEEDS): float32 restatement within 1e-5
+    of the float64 one, every drone-step 1e-3 from every threshold"""
+    cfg, K, kind, _ = pref.case("vel_k8_s5")
+    C = _params(cfg.model)
+    inp = pref.make_inputs(C, cfg, n, K, seed=pref.SIZE_SEEDS[n], kind=kind)
+    stats = {}
+    g64 = pref.reference_grads(C, cfg, inp, torch.float64, stats=stats)
+    err = pref.group_errors(pref.reference_grads(C, cfg, inp, torch.float32), g64)
+    assert max(err.values()) < 1e-5, err
+    assert min(stats["near"].values()) >= 1e-3 and (ref.GIMBAL - stats["sarg_max"]) / ref.GIMBAL >= 1e-3, stats["near"]
+    assert stats["reward_arg_min"] > 1e-3 and stats["n2_min"] > 100 * ref.TURN_N2
 
 
 def test_pack_and_unpack_pid_are_inverse_and_differentiable():
