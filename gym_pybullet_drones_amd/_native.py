@@ -30,8 +30,8 @@ ABI_VERSION = 9
 #                     slots of a rollout step)
 #   policy.hip        gpd_rollout_policy                 the default scheduler: 10 % faster on its MFMA + activation mix (round-2 A/B)
 #   swarm.hip         the one-world kernels              max-ilp, as in rounds 2-4
-#   abi.hip           small kernels, RCCL, library-level entries; the differentiable rollout (RPM and DSLPID), gpd_obstacles and gpd_mppi (csrc/*.inc pulled in at
-#                     its end)
+#   abi.hip           small kernels, RCCL, library-level entries; the differentiable rollout (RPM and DSLPID), gpd_obstacles, gpd_mppi and the
+#                     thrust-and-body-rate controller gpd_ctbr / gpd_rollout_ctbr (csrc/*.inc pulled in at its end)
 #   mrac.hip          gpd_mrac / gpd_mrac_reset / gpd_rollout_mrac: the adaptive controller and the rollout that carries it (max-ilp)
 #   -mllvm -amdgpu-kernarg-preload-count=14: the first 14 argument dwords of a kernel arrive in SGPRs with the wave (gfx942+ command
 #   processor) instead of through a scalar load -- gpd_step_kernel's argument list starts with what its load section needs
@@ -40,7 +40,7 @@ MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 HIPCC_FLAGS = COMMON_FLAGS + MAX_ILP + ["-shared"]        # (kept under this name for the ISA tests)
 UNITS = (("step_rollout.hip", MAX_ILP + KERNARG_PRELOAD), ("policy.hip", []), ("swarm.hip", MAX_ILP + KERNARG_PRELOAD), ("abi.hip", MAX_ILP), ("mrac.hip", MAX_ILP))
-HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc", "diff_pid_kernels.inc", "dslpid_vjp.inc", "obstacle_math.inc", "obstacles.inc", "mppi_math.inc", "mppi.inc")
+HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc", "diff_pid_kernels.inc", "dslpid_vjp.inc", "obstacle_math.inc", "obstacles.inc", "mppi_math.inc", "mppi.inc", "ctbr_math.inc", "ctbr.inc")
 
 
 class GpdError(RuntimeError):
@@ -103,6 +103,16 @@ class GpdMppi(ctypes.Structure):
                 ("obst_margin", ctypes.c_float), ("collision_radius", ctypes.c_float), ("seed", ctypes.c_uint32 * 2),
                 ("iteration", ctypes.c_uint32)]
 
+
+class GpdCtbr(ctypes.Structure):
+    """mirror of `struct GpdCtbr` (gpd_ctbr / gpd_rollout_ctbr: the outer loop's gains, the rate loop's gains, clips and allocation)"""
+    _fields_ = [("k_p", ctypes.c_float * 3), ("k_d", ctypes.c_float * 3), ("k_rates", ctypes.c_float * 3), ("g", ctypes.c_float),
+                ("k_rate", ctypes.c_float * 3), ("thrust_max", ctypes.c_float), ("rate_max", ctypes.c_float), ("alloc", ctypes.c_float * 12),
+                ("f_max", ctypes.c_float), ("inv_kf", ctypes.c_float), ("pad_", ctypes.c_float * 3)]
+
+
+#: `mode` of gpd_rollout_ctbr (GPD_CTBR_CMD / GPD_CTBR_POS)
+CTBR_MODES = {"cmd": 0, "pos": 1}
 
 #: floats of MRAC state per controller (GPD_MRAC_STATE): Kx [12][4] | Kr [4][4] | Xm [12]
 MRAC_STATE = 76
@@ -201,6 +211,10 @@ _SIGNATURES = {
     "gpd_rollout_mrac": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdMrac), ctypes.POINTER(GpdState),
                                         ctypes.POINTER(GpdStepCfg), _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64,
                                         ctypes.c_int32, _P]),
+    "gpd_sizeof_ctbr": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int32)]),
+    "gpd_ctbr": (ctypes.c_int, [ctypes.POINTER(GpdCtbr), _P, _P, _P, _P, _P, _P, ctypes.c_int32, _P]),
+    "gpd_rollout_ctbr": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdCtbr), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg),
+                                        ctypes.c_int32, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, ctypes.c_int32, _P]),
     "gpd_state_vectors": (ctypes.c_int, [ctypes.POINTER(GpdState), _P, _P, ctypes.c_int32, _P]),
     "gpd_comm_unique_id": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8)]),
     "gpd_comm_init": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32,
@@ -273,6 +287,9 @@ def lib() -> ctypes.CDLL:
     mrac_size = ctypes.c_int32(0)
     if L.gpd_sizeof_mrac(ctypes.byref(mrac_size)) != 0 or mrac_size.value != ctypes.sizeof(GpdMrac):
         raise GpdError(f"struct layout mismatch: GpdMrac is {mrac_size.value} bytes in the library, {ctypes.sizeof(GpdMrac)} in the binding")
+    ctbr_size = ctypes.c_int32(0)
+    if L.gpd_sizeof_ctbr(ctypes.byref(ctbr_size)) != 0 or ctbr_size.value != ctypes.sizeof(GpdCtbr):
+        raise GpdError(f"struct layout mismatch: GpdCtbr is {ctbr_size.value} bytes in the library, {ctypes.sizeof(GpdCtbr)} in the binding")
     _lib = L
     return L
 

@@ -600,3 +600,6 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
 // sampling-based MPC: gpd_mppi and its kernel
 #include "mppi.inc"
 
+// thrust and body-rate commands: gpd_sizeof_ctbr / gpd_ctbr / gpd_rollout_ctbr and their kernels
+#include "ctbr.inc"
+

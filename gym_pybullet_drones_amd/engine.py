@@ -565,6 +565,56 @@ class SimCore:
             self.obs12.copy_(obs[K - 1])
         return obs
 
+    def rollout_ctbr(self, ctrl, rows, num_steps: int, mode: str = "cmd", last_only: bool = False, want_cmd: bool = False):
+        """K control steps in ONE launch flown on thrust and body-rate commands (`gpd_rollout_ctbr`): a body-rate loop runs inside
+        every physics sub-step -- the inner loop the reference leaves to Betaflight (`envs/BetaAviary.py`) -- on the command held over
+        the control step.  `ctrl`: a `control.VectorCTBR` with one controller per drone (its gains, clips and rotor allocation).
+
+        `mode="cmd"`: `rows` are commands `[N, 4]` (held for all K steps) or `[K, N, 4]`: thrust [m/s^2] | body rates [rad/s].
+        `mode="pos"`: `rows` are targets `[N, 12]` or `[K, N, 12]` (target pos | rpy | vel | rpy rates; rows of 3 floats are
+        positions) and the reference's `CTBRControl.computeControl` gives each step's command from the state at its start.  Aviaries
+        of one drone, no task, RPM actions (`VectorCtrlAviary`).  A plant table (`set_plant`) is honoured: the airframes differ, the
+        controller's mass and inertia stay nominal.  Returns `obs12 [K, N, 12]` (a persistent buffer) or, with `last_only`, the latest
+        rows `[N, 12]`; with `want_cmd` a pair `(obs12, cmd)`, `cmd` a fresh tensor of the commands each step flew (before the rate
+        loop's clips), shaped like the command rows of "cmd" mode and `[K, N, 4]` in "pos" mode.  "pos" mode is bitwise K x
+        (`ctrl.compute(...)`, one step of "cmd" mode), and K1 then K2 steps are K1 + K2 in one launch."""
+        K = int(num_steps)
+        if K < 1:
+            raise ValueError("num_steps must be >= 1")
+        if mode not in _native.CTBR_MODES:
+            raise ValueError(f"rollout_ctbr: mode must be 'cmd' or 'pos', got {mode!r}")
+        if self.host_visible:
+            raise ValueError("rollout_ctbr: a host-visible core steps one aviary at a time (CtrlAviary.step takes RPMs)")
+        if self.act_ring is not None:
+            raise ValueError("rollout_ctbr: this core keeps an action history, which the fused rollout would not advance")
+        if getattr(ctrl, "n", None) != self.N or ctrl.device != self.device or not hasattr(ctrl, "thrust_max"):
+            raise ValueError(f"rollout_ctbr needs a VectorCTBR of {self.N} controllers on {self.device}")
+        t = torch.as_tensor(rows, dtype=torch.float32, device=self.device)
+        W = 4 if mode == "cmd" else 12
+        if mode == "pos" and t.shape[-1] == 3:
+            t = torch.cat([t, torch.zeros(t.shape[:-1] + (9,), dtype=torch.float32, device=self.device)], dim=-1)
+        if tuple(t.shape) == (self.N, W):
+            r_stride = 0
+        elif tuple(t.shape) == (K, self.N, W):
+            r_stride = self.N * W
+        else:
+            raise ValueError(f"rows must be [{self.N}, {W}] or [{K}, {self.N}, {W}]" + (" (or rows of 3: positions)" if mode == "pos" else "")
+                             + f" in mode {mode!r}, got {tuple(t.shape)}")
+        t = t.contiguous()
+        cmd = None
+        if want_cmd:
+            cmd = torch.empty((self.N, 4) if (mode == "cmd" and r_stride == 0) else (K, self.N, 4), dtype=torch.float32, device=self.device)
+        if last_only:
+            obs, o_stride = self.obs12, 0
+        else:
+            obs, o_stride = self._rollout_buffers(K)[0], self.N * 12
+        self.state_version += 1
+        _native.call("gpd_rollout_ctbr", self.device, self._stream(), self._params, ctrl.struct(), self._state, self._cfg,
+                     _native.CTBR_MODES[mode], t, r_stride, self.plant_rows, obs, o_stride, cmd, K)
+        if not last_only:
+            self.obs12.copy_(obs[K - 1])
+        return (obs, cmd) if want_cmd else obs
+
     def _latest_terminal(self, tobs, term, trunc, K):
         """`term_obs12` after a K-step launch = what K single steps would have left: for every aviary the terminal observation
         of the LAST step it ended in (aviaries that did not end keep what they held).  A few small torch kernels, off the

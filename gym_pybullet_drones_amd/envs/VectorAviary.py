@@ -214,6 +214,17 @@ class VectorAviary:
         obs = self.core.rollout_mrac(ctrl, targets, num_steps, last_only=last_only)
         return obs.view(-1, self.NUM_ENVS, self.NUM_DRONES, 12) if not last_only else obs.view(self.NUM_ENVS, self.NUM_DRONES, 12)
 
+    def rollout_ctbr(self, ctrl, rows, num_steps: int, mode: str = "cmd", last_only: bool = False, want_cmd: bool = False):
+        """K control steps in ONE launch flown on thrust and body-rate commands, the rate loop inside the physics sub-steps
+        (`SimCore.rollout_ctbr`).  `ctrl`: a `control.VectorCTBR` with one controller per drone; `rows`: commands (E, 4) / (K, E, 4) in
+        `mode="cmd"`, targets (E, 12) / (K, E, 12) (rows of 3: positions) in `mode="pos"`.  Single-drone aviaries without a task
+        (`VectorCtrlAviary`); a plant table is honoured.  Returns obs (K, E, 1, 12), or (E, 1, 12) with `last_only`; with `want_cmd` a
+        pair (obs, cmd)."""
+        out = self.core.rollout_ctbr(ctrl, rows, num_steps, mode=mode, last_only=last_only, want_cmd=want_cmd)
+        obs, cmd = out if want_cmd else (out, None)
+        obs = obs.view(-1, self.NUM_ENVS, self.NUM_DRONES, 12) if not last_only else obs.view(self.NUM_ENVS, self.NUM_DRONES, 12)
+        return (obs, cmd) if want_cmd else obs
+
     def state_vectors(self) -> torch.Tensor:
         """(E, D, 20) `_getDroneStateVector`-ordered states (needs `track_rpm=True` for the RPM columns)."""
         return self.core.state_vectors().view(self.NUM_ENVS, self.NUM_DRONES, 20)

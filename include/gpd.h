@@ -878,6 +878,83 @@ int gpd_rollout_mrac(const GpdParams* params, const GpdMrac* mrac, const GpdStat
                      void* stream);
 
 /*
+ * CTBR: collective thrust and body rates, the reference's control/CTBRControl.py -- which it flies through BetaAviary with Betaflight as
+ * the inner loop -- batched, and fused into the rollout with a rate loop of its own in place of the firmware.
+ * A command is 4 floats: thrust as a mass-normalised acceleration [m/s^2], then the body rates x, y, z [rad/s].  The arithmetic of both
+ * loops is csrc/ctbr_math.inc.  A HOST struct like GpdParams, passed by value in the kernel argument segment (wave-uniform).
+ */
+typedef struct GpdCtbr {
+    /* the outer loop, CTBRControl.computeControl (:149-168): the reference's constants by default */
+    float k_p[3];           /* K_P = (3, 3, 8) */
+    float k_d[3];           /* K_D = (2.5, 2.5, 5) */
+    float k_rates[3];       /* K_RATES = (5, 5, 1) */
+    float g;                /* -G[2] = 9.8 (a constant of the reference's method, not the class's `g`) */
+    /* the rate loop (new: the reference leaves it to the firmware), evaluated every physics sub-step */
+    float k_rate[3];        /* [1/s], (40, 40, 20) by default */
+    float thrust_max;       /* the command's clips: thrust to [0, thrust_max] (40.9 m/s^2) ... */
+    float rate_max;         /* ... each rate to +-rate_max (360 deg/s), BetaAviary.ctbr2beta's limits (envs/BetaAviary.py:176-188) */
+    float alloc[12];        /* [4][3]: f_i = M thrust / 4 + alloc[i] . tau, the exact inverse of the integrator's torque rows for the
+                             * airframe (CF2X / RACE: +-1/(4 L/sqrt 2) | +-1/(4 kz); CF2P: +-1/(2 L), 0 | +-1/(4 kz); kz = +-KM/KF),
+                             * host-computed in float64 */
+    float f_max;            /* KF MAX_RPM^2: a rotor's thrust is clipped to [0, f_max] */
+    float inv_kf;           /* 1/KF: rpm_i = sqrt(f_i / KF) */
+    float pad_[3];          /* (to a multiple of 16 bytes) */
+} GpdCtbr;
+
+/* the two ways gpd_rollout_ctbr is commanded */
+#define GPD_CTBR_CMD 0      /* rows are [N][4] commands */
+#define GPD_CTBR_POS 1      /* rows are [N][12] targets (pos | rpy | vel | rpy rates): the outer loop runs in the kernel */
+
+/* sizeof(GpdCtbr) -> *size_out, for a binding to verify its mirror (as gpd_sizeof_mrac).  GPD_EINVAL: NULL. */
+int gpd_sizeof_ctbr(int32_t* size_out);
+
+/*
+ * Batched CTBRControl.computeControl (the outer loop alone) for n independent drones: one lane each, asynchronous on `stream`, capturable.
+ *   ctbr         HOST pointer, like GpdParams
+ *   cur_pos, cur_vel [n][3]; cur_quat [n][4], x y z w -- the state's order -- 16-byte aligned; target_pos [n][3]
+ *   target_vel   [n][3] or NULL (= zeros, the reference's default).  The reference also accepts target_rpy and target_rpy_rates and
+ *                ignores them; this entry does not take them
+ *   cmd          [n][4] out, 16-byte aligned: thrust [m/s^2] | body rates [rad/s]
+ * Validated before any device work.  GPD_EINVAL: a NULL pointer other than target_vel, n <= 0, cur_quat or cmd not 16-byte aligned.
+ * GPD_ERANGE: n > 2^26 (32-bit byte offsets).
+ */
+int gpd_ctbr(const GpdCtbr* ctbr, const float* cur_pos, const float* cur_quat, const float* cur_vel, const float* target_pos,
+             const float* target_vel, float* cmd, int32_t n, void* stream);
+
+/*
+ * K control steps in ONE launch with a body-rate loop closed INSIDE the physics sub-steps.  A drone's state is loaded once, stays in
+ * registers for all K steps and their sub-steps, and is stored once.  A control step holds one command; every sub-step evaluates the rate
+ * loop of ctbr_math.inc on the body rates the integrator carries and hands its four RPMs to the physics exactly as a
+ * GPD_ACT_DIRECT_RPM action would.  The controller's M and J are those of `params` -- the nominal airframe -- with a plant table too.
+ *   mode           GPD_CTBR_CMD: step t reads [N][4] commands at rows + t*row_step_stride (floats).  GPD_CTBR_POS: step t reads [N][12]
+ *                  targets (pos | rpy | vel | rpy rates, gpd_rollout_mrac's layout; rpy and its rates are ignored, as the reference
+ *                  does) and evaluates the outer loop on the state at the START of the control step.  Stride 0 holds one block for all
+ *                  K steps.  16-byte aligned.  GPD_CTBR_POS is bit for bit K x (gpd_ctbr on the current state, GPD_CTBR_CMD with K = 1)
+ *   cfg            as gpd_rollout_mrac: drones_per_env = 1, task GPD_TASK_NONE, no auto-reset, act_type GPD_ACT_RAW_RPM or
+ *                  GPD_ACT_DIRECT_RPM (the two are the same here: the rate loop's RPMs are inside [0, MAX_RPM]), any sub-step count;
+ *                  GPD_PHYS_GND / DRAG / GROUND / DAMP allowed
+ *   state.last_rpm read for the drag term of the very first sub-step, written with the last sub-step's RPMs; the drag term of every
+ *                  other sub-step sees the previous sub-step's RPMs (the reference's last_clipped_action rule, envs/BaseAviary.py:
+ *                  359-372, carried to a controller that runs every sub-step).  The only state the controller carries
+ *   plant_rows     NULL, or the per-drone plant table of gpd_plant_derive (pitch state.ld)
+ *   obs12          step t writes [N][12] at obs12 + t*obs_step_stride; stride 0 keeps only the last step's rows.  16-byte aligned
+ *   cmd_out        NULL, or [N][4] per step, 16-byte aligned: the commands each step flew, BEFORE the rate loop's clips, at
+ *                  cmd_out + t*cmd_step_stride where cmd_step_stride is row_step_stride in GPD_CTBR_CMD (0: the held block, written K
+ *                  times with what was read) and 4*num_envs in GPD_CTBR_POS.  Must not alias rows
+ * K1 then K2 steps = K1 + K2 in one launch, bit for bit.  Validated before any device work.
+ *   GPD_EINVAL   a NULL pointer (plant_rows, cmd_out excepted), state.kin not 16-byte aligned or state.ld outside 1 .. 2^32 - 1, num_envs /
+ *                substeps / num_steps <= 0, an unknown physics flag or mode, state.ld < num_envs, GPD_PHYS_DRAG without state.last_rpm, a
+ *                negative step stride, a non-zero one below a step's rows (4*num_envs or 12*num_envs for rows, 12*num_envs for obs12) or
+ *                not a multiple of 4 floats, rows / obs12 / plant_rows / cmd_out not 16-byte aligned, cmd_out == rows, pyb_dt or
+ *                ctrl_dt <= 0
+ *   GPD_ENOTSUP  drones_per_env != 1, a task or auto_reset, an act_type other than the two RPM ones, GPD_PHYS_DW or state.dw_force
+ *   GPD_ERANGE   num_envs > 2^26 (32-bit byte offsets)
+ */
+int gpd_rollout_ctbr(const GpdParams* params, const GpdCtbr* ctbr, const GpdState* state, const GpdStepCfg* cfg, int32_t mode,
+                     const float* rows, int64_t row_step_stride, const float* plant_rows, float* obs12, int64_t obs_step_stride,
+                     float* cmd_out, int32_t num_steps, void* stream);
+
+/*
  * Gather the 20-float state vectors of BaseAviary._getDroneStateVector
  * (envs/BaseAviary.py:541-561): pos3 | quat4 | rpy3 | vel3 | ang_v3 | last_clipped_action4,
  * from the SoA state and the obs12 rows of the latest step.  state20 is [n][20].
