@@ -603,3 +603,5 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
 // thrust and body-rate commands: gpd_sizeof_ctbr / gpd_ctbr / gpd_rollout_ctbr and their kernels
 #include "ctbr.inc"
 
+// ... and the differentiable rollout through them: gpd_rollout_tape_ctbr_floats / gpd_rollout_tape_ctbr / gpd_rollout_vjp_ctbr
+#include "diff_ctbr_kernels.inc"

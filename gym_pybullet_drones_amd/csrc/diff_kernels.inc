@@ -487,9 +487,10 @@ __global__ __launch_bounds__(256) void gpd_plant_derive_vjp_kernel(const GpdPara
 }
 
 // What the entries of the rollout check of the configuration and refuse of it, before any device work: the span and the sizes, then what is
-// not differentiable in the family the entry serves (the RPM action types of this file, or the DSLPID ones of diff_pid_kernels.inc).
+// not differentiable in the family the entry serves (the RPM action types of this file, the DSLPID ones of diff_pid_kernels.inc, or the
+// thrust-and-body-rate loop of diff_ctbr_kernels.inc, which narrows the configuration as gpd_rollout_ctbr does).
 // `ld` comes without the state in two entries of each family.
-enum class DiffFamily { RPM, PID };
+enum class DiffFamily { RPM, PID, CTBR };
 int diff_cfg(Refuse bad, DiffFamily family, const GpdStepCfg* cfg, int64_t ld, int32_t num_steps, int64_t stride0 = 0, int64_t stride1 = 0,
              int64_t stride2 = 0) {
     if (int rc = check_steps(bad, num_steps, stride0, stride1, stride2)) return rc;
@@ -505,6 +506,13 @@ int diff_cfg(Refuse bad, DiffFamily family, const GpdStepCfg* cfg, int64_t ld, i
             return bad(GPD_ENOTSUP, "the DSLPID action types are not differentiable (RPM, ONE_D_RPM, RAW_RPM and DIRECT_RPM are)");
         if (cfg->physics_flags & ~static_cast<uint32_t>(GPD_PHYS_DRAG))
             return bad(GPD_ENOTSUP, "physics_flags other than GPD_PHYS_DRAG are not differentiable (ground effect, downwash, ground plane, damping)");
+    } else if (family == DiffFamily::CTBR) {
+        if (cfg->task != GPD_TASK_NONE) return bad(GPD_ENOTSUP, "GPD_TASK_NONE without auto-reset only");
+        if (cfg->act_type != GPD_ACT_RAW_RPM && cfg->act_type != GPD_ACT_DIRECT_RPM)
+            return bad(GPD_ENOTSUP, "act_type GPD_ACT_RAW_RPM or GPD_ACT_DIRECT_RPM (the rate loop's output is RPMs)");
+        if (cfg->physics_flags)
+            return bad(GPD_ENOTSUP, "physics_flags are not differentiable together with the body-rate loop (ground effect, drag -- its rpm sum has "
+                                    "no derivative at a rotor held at 0 --, downwash, ground plane, damping)");
     } else {
         if (cfg->act_type != GPD_ACT_PID && cfg->act_type != GPD_ACT_VEL && cfg->act_type != GPD_ACT_ONE_D_PID)
             return bad(GPD_ENOTSUP, "the RPM action types go through gpd_rollout_tape / gpd_rollout_vjp (this entry: PID, VEL and ONE_D_PID)");

@@ -25,6 +25,14 @@ The three action types that close the loop in the kernel go through `rollout_dif
 `gpd_rollout_vjp_pid`): the nine controller members (`pack_pid` / `unpack_pid`) are a differentiable input
 and output next to the kinematic state, and the 18 gains of the cascaded PID receive a gradient.  Tuning the controller by
 back-propagation through the flight: examples/tune_pid.py.
+
+    obs12, kin_K = core.rollout_diff_ctbr(ctrl, cmd, gains=gains)                         # cmd [K, N, 4]: thrust | body rates; gains [4, 3]
+    loss(obs12).backward()                                                                # cmd.grad, gains.grad
+
+Thrust and body-rate commands -- `SimCore.rollout_ctbr`'s flight, a rate loop inside every sub-step -- go through
+`rollout_diff_ctbr` (`gpd_rollout_tape_ctbr` / `gpd_rollout_vjp_ctbr`): commands (`mode="cmd"`) or target rows
+through the reference's outer loop (`mode="pos"`), the initial state and the controller's 12 gains receive gradients.  Policy
+gradients through the physics on the action space of agile flight: examples/apg_ctbr.py.
 """
 import ctypes
 
@@ -316,3 +324,132 @@ def rollout_diff_pid(core, actions, kin0=None, pid0=None, num_steps: int = None,
         if not isinstance(pid_gains, torch.Tensor) or pid_gains.numel() != 18:
             raise ValueError("pid_gains must be a tensor of 6 x 3 gains (rows: p_for, i_for, d_for, p_tor, i_tor, d_tor)")
     return RolloutDiffPid.apply(core, kin0, pid0, actions, K, a_stride, pid_gains)
+
+
+# ---- through the thrust-and-body-rate loop (include/gpd.h `gpd_rollout_tape_ctbr` / `gpd_rollout_vjp_ctbr`, csrc/diff_ctbr_kernels.inc) ---
+#: the rows of `gains` [4, 3], in the order of `g_gains [12][ld]` and of the fields of GpdCtbr
+CTBR_GAIN_FIELDS = ("k_p", "k_d", "k_rates", "k_rate")
+
+
+def ctbr_gains_of(ctbr):
+    """the 12 gains of a `GpdCtbr` as a float32 CPU tensor `[4, 3]` (rows: CTBR_GAIN_FIELDS)"""
+    return torch.tensor([list(getattr(ctbr, f)) for f in CTBR_GAIN_FIELDS], dtype=torch.float32)
+
+
+def ctbr_with_gains(ctbr, gains):
+    """a copy of the by-value `GpdCtbr` whose 12 gains are `gains` ([4, 3], rows: CTBR_GAIN_FIELDS).  Reads the tensor to the host:
+    a synchronisation when it lives on the device."""
+    host = gains.detach().to(device="cpu", dtype=torch.float32).reshape(4, 3).tolist()
+    out = type(ctbr).from_buffer_copy(ctbr)
+    for f, row in zip(CTBR_GAIN_FIELDS, host):
+        setattr(out, f, (ctypes.c_float * 3)(*row))
+    return out
+
+
+def tape_floats_ctbr(core, K: int) -> int:
+    """floats of the tape of a K-step call on `core` (`gpd_rollout_tape_ctbr_floats`); raises GpdError for an unsupported configuration"""
+    out = ctypes.c_int64(0)
+    _native.call("gpd_rollout_tape_ctbr_floats", None, _native.NO_STREAM, core._cfg, int(K), core.ld, ctypes.byref(out))
+    return out.value
+
+
+def tape_forward_ctbr(core, ctbr, mode, K, rows, r_stride, obs, tape, cmd=None, plant=OWN):
+    """one `gpd_rollout_tape_ctbr` launch on the core's params, state and cfg with the controller `ctbr` (a `GpdCtbr`): K steps of `rows`
+    (`r_stride` floats apart, 0: one held block) into `obs [K,N,12]`, `tape` and -- not None -- `cmd`"""
+    _native.call("gpd_rollout_tape_ctbr", core.device, core._stream(), core._params, ctbr, core._state, core._cfg, _native.CTBR_MODES[mode],
+                 rows, r_stride, core.plant_rows if plant is OWN else plant, obs, core.N * 12, cmd, K, tape)
+
+
+def sweep_ctbr(core, ctbr, mode, K, rows, r_stride, tape, g_obs, g_kin, g_rows, g_gains=None, plant=OWN):
+    """one `gpd_rollout_vjp_ctbr` launch over `tape`: `g_obs`: None = zeros; `g_kin [13*ld]` is read and overwritten, `g_rows [K,N,W]`
+    written, `g_gains [12, ld]` (None: not asked for) written per drone"""
+    _native.call("gpd_rollout_vjp_ctbr", core.device, core._stream(), core._params, ctbr, core._cfg, core.ld, _native.CTBR_MODES[mode], K,
+                 rows, r_stride, core.plant_rows if plant is OWN else plant, tape, g_obs, core.N * 12, g_kin, g_rows, g_gains)
+
+
+class RolloutDiffCtbr(torch.autograd.Function):
+    """forward: `gpd_rollout_tape_ctbr` from `kin0` (copied into the core's state first); backward: `gpd_rollout_vjp_ctbr`"""
+
+    @staticmethod
+    def forward(ctx, core, ctbr, kin0, rows, K, r_stride, mode, gains=None):
+        size = tape_floats_ctbr(core, K)                       # (also the configuration check, before anything is touched)
+        ctbr = ctbr if gains is None else ctbr_with_gains(ctbr, gains)
+        if kin0.data_ptr() != core.kin_store.data_ptr():
+            core.kin_store.copy_(kin0)
+        obs = torch.empty((K, core.N, 12), dtype=torch.float32, device=core.device)
+        tape = torch.empty((size,), dtype=torch.float32, device=core.device)
+        core.state_version += 1
+        tape_forward_ctbr(core, ctbr, mode, K, rows, r_stride, obs, tape)
+        kin_k = core.kin_store.clone()
+        core.obs12.copy_(obs[K - 1])                           # (the core's latest rows follow its state, as after rollout_ctbr())
+        ctx.core, ctx.ctbr, ctx.K, ctx.r_stride, ctx.mode, ctx.plant = core, ctbr, K, r_stride, mode, core.plant_rows
+        ctx.with_gains = gains is not None and gains.requires_grad
+        ctx.gains_like = None if gains is None else (gains.shape, gains.dtype, gains.device)
+        ctx.save_for_backward(rows, tape)
+        ctx.set_materialize_grads(False)                       # (an output nobody differentiates arrives as None: NULL = zeros)
+        return obs, kin_k
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_obs, g_kin):
+        core, K = ctx.core, ctx.K
+        rows, tape = ctx.saved_tensors
+        dev, N = core.device, core.N
+        g_kin = _cot(g_kin, core.kin_store)
+        g_rows = torch.empty((K, N, rows.shape[-1]), dtype=torch.float32, device=dev)
+        with_gains = ctx.with_gains and ctx.needs_input_grad[7]
+        g_table = torch.zeros((12, core.ld), dtype=torch.float32, device=dev) if with_gains else None     # (the kernel writes drones 0 .. N-1)
+        sweep_ctbr(core, ctx.ctbr, ctx.mode, K, rows, ctx.r_stride, tape, _cot(g_obs), g_kin, g_rows, g_table, ctx.plant)
+        g_gains = None
+        if with_gains:         # the forward's gains are shared: the sum over drones, in float64 (N terms), in the caller's shape and place
+            shape, dtype, device = ctx.gains_like
+            g_gains = g_table[:, :N].sum(dim=1, dtype=torch.float64).reshape(4, 3).to(device=device, dtype=dtype).reshape(shape)
+        return None, None, g_kin, _action_grad(g_rows, ctx.r_stride, rows), None, None, None, g_gains
+
+
+def rollout_diff_ctbr(core, ctrl, rows, kin0=None, num_steps: int = None, mode: str = "cmd", gains=None):
+    """`SimCore.rollout_diff_ctbr`: K control steps on thrust and body-rate commands in one launch (`SimCore.rollout_ctbr`'s flight),
+    differentiable with respect to `rows`, `kin0` and `gains`.
+
+    `ctrl`: a `control.VectorCTBR` with one controller per drone.  `rows`: in `mode="cmd"` commands `[K, N, 4]`, or -- with
+    `num_steps=K` -- ONE block `[N, 4]` held for all K steps (its gradient is the sum over the steps); in `mode="pos"` targets
+    `[K, N, 12]` / `[N, 12]` (pos | rpy | vel | rpy rates; rows of 3 floats are positions), whose rpy and rate slots -- ignored by the
+    forward -- receive exact zeros.  `kin0`: None (the core's own state) or a `[13 * ld]` tensor in the plane layout (`pack_kin`),
+    copied into the state first.  Returns fresh tensors `(obs12 [K,N,12], kin_K [13*ld])`, both carrying gradients; `kin_K` of one
+    call as `kin0` of the next chains the graph.  `gains`: None (the controller's own: constants, no gain gradient) or a `[4, 3]`
+    tensor, rows `CTBR_GAIN_FIELDS` = k_p, k_d, k_rates, k_rate; it REPLACES the controller's gains for this call (`ctrl` keeps its
+    own) and -- when it requires grad -- receives the gradient summed over drones.  Reading its 12 floats to the host is a
+    SYNCHRONISATION when it lives on the device.  Single-drone aviaries, no task, the two raw RPM action types, no add-on physics or
+    drag, no auto-reset, with or without a plant table (a constant): `GpdError` otherwise."""
+    if mode not in _native.CTBR_MODES:
+        raise ValueError(f"rollout_diff_ctbr: mode must be 'cmd' or 'pos', got {mode!r}")
+    if core.host_visible:
+        raise ValueError("rollout_diff_ctbr: a host-visible core steps one aviary at a time (CtrlAviary.step takes RPMs)")
+    if core.act_ring is not None:
+        raise ValueError("rollout_diff_ctbr: this core keeps an action history, which the fused rollout would not advance")
+    if getattr(ctrl, "n", None) != core.N or ctrl.device != core.device or not hasattr(ctrl, "thrust_max"):
+        raise ValueError(f"rollout_diff_ctbr needs a VectorCTBR of {core.N} controllers on {core.device}")
+    if gains is not None and (not isinstance(gains, torch.Tensor) or gains.numel() != 12):
+        raise ValueError("gains must be a tensor of 4 x 3 gains (rows: k_p, k_d, k_rates, k_rate)")
+    t = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(rows, dtype=torch.float32)
+    t = t.to(device=core.device, dtype=torch.float32)
+    W = 4 if mode == "cmd" else 12
+    if mode == "pos" and t.dim() >= 2 and t.shape[-1] == 3:
+        t = torch.cat([t, torch.zeros(t.shape[:-1] + (9,), dtype=torch.float32, device=core.device)], dim=-1)
+    if t.dim() == 3 and num_steps is None:
+        num_steps = t.shape[0]
+    if num_steps is None or int(num_steps) < 1:
+        raise ValueError("num_steps must be >= 1 (it may be left out only with one block of rows per step)")
+    K = int(num_steps)
+    if tuple(t.shape) == (core.N, W):
+        r_stride = 0
+    elif tuple(t.shape) == (K, core.N, W):
+        r_stride = core.N * W
+    else:
+        raise ValueError(f"rows must be [{core.N}, {W}] or [{K}, {core.N}, {W}]" + (" (or rows of 3: positions)" if mode == "pos" else "")
+                         + f" in mode {mode!r}, got {tuple(t.shape)}")
+    tape_floats_ctbr(core, K)                                  # (the configuration check, with the library's message, before anything else)
+    if core._state.dw_force:
+        raise _native.GpdError("rollout_diff_ctbr: downwash computed outside the kernel (state.dw_force) is not differentiable")
+    kin0 = _state0(core, kin0, core.kin_store, "kin0", "the plane layout: pack_kin")
+    return RolloutDiffCtbr.apply(core, ctrl.struct(), kin0, t.contiguous(), K, r_stride, mode, gains)

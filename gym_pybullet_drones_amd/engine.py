@@ -448,6 +448,19 @@ class SimCore:
         from . import diff
         return diff.rollout_diff_pid(self, actions, kin0, pid0, num_steps, pid_gains)
 
+    def rollout_diff_ctbr(self, ctrl, rows, kin0: torch.Tensor = None, num_steps: int = None, mode: str = "cmd", gains: torch.Tensor = None):
+        """`rollout_ctbr()` that `.backward()` goes through (`diff.rollout_diff_ctbr`: `gpd_rollout_tape_ctbr` forward,
+        `gpd_rollout_vjp_ctbr` backward).  `ctrl`, `rows` and `mode` as in `rollout_ctbr` (`num_steps` may be left out with one block of
+        rows per step).  Returns fresh tensors `(obs12 [K,N,12], kin_K [13*ld])`, bit for bit `rollout_ctbr`'s flight; both carry
+        gradients with respect to `rows` (a held block receives the sum over the steps; the rpy and rate slots of a target row exact
+        zeros), `kin0` (None: the core's own state; else the plane layout, copied into the state first -- `kin_K` of one call as
+        `kin0` of the next chains the graph) and `gains`: a `[4, 3]` tensor (rows k_p, k_d, k_rates, k_rate) that replaces the
+        controller's gains for this call and receives the gradient summed over drones; None: the controller's own, no gain gradient.
+        Reading the 12 gains to the host is a synchronisation when the tensor lives on the device.  Single-drone aviaries, no task,
+        RPM actions, no add-on physics or drag, no auto-reset; a plant table is honoured as a constant: GpdError otherwise."""
+        from . import diff
+        return diff.rollout_diff_ctbr(self, ctrl, rows, kin0, num_steps, mode, gains)
+
     def _fixed_args(self):
         """the arguments of gpd_step / gpd_rollout* that never change between two calls, as ctypes objects (set_target() drops them)"""
         self._step_args = tuple(_native.as_c(x) for x in (self._params, self._state, self._cfg, self.target, self.init_pose, self.obs12,

@@ -225,6 +225,14 @@ class VectorAviary:
         obs = obs.view(-1, self.NUM_ENVS, self.NUM_DRONES, 12) if not last_only else obs.view(self.NUM_ENVS, self.NUM_DRONES, 12)
         return (obs, cmd) if want_cmd else obs
 
+    def rollout_diff_ctbr(self, ctrl, rows, kin0: torch.Tensor = None, num_steps: int = None, mode: str = "cmd", gains: torch.Tensor = None):
+        """The differentiable rollout on thrust and body-rate commands (`SimCore.rollout_diff_ctbr`): `ctrl`, `rows` and `mode` as in
+        `rollout_ctbr` -> (obs12 (K,E,1,12), kin_K [13*ld]), both carrying gradients with respect to `rows`, `kin0` (the plane layout
+        of the kinematic state, `diff.pack_kin`; None: the current state) and `gains` ([4, 3]: k_p, k_d, k_rates, k_rate; replaces the
+        controller's gains for this call -- reading it to the host synchronises -- and receives the gradient summed over drones)."""
+        obs, kin_k = self.core.rollout_diff_ctbr(ctrl, rows, kin0, num_steps, mode, gains)
+        return obs.view(-1, self.NUM_ENVS, self.NUM_DRONES, 12), kin_k
+
     def state_vectors(self) -> torch.Tensor:
         """(E, D, 20) `_getDroneStateVector`-ordered states (needs `track_rpm=True` for the RPM columns)."""
         return self.core.state_vectors().view(self.NUM_ENVS, self.NUM_DRONES, 20)

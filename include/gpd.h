@@ -1155,6 +1155,54 @@ int gpd_rollout_vjp_pid(const GpdParams* params, const GpdStepCfg* cfg, int64_t 
                         int64_t obs_step_stride, const float* g_reward, int64_t env_step_stride, float* g_kin, float* g_pid,
                         float* g_actions, float* g_gains, void* stream);
 
+/*
+ * The differentiable rollout through the thrust-and-body-rate loop (additions to ABI 9): the three entries of the differentiable rollout
+ * for gpd_rollout_ctbr's flight -- a body-rate loop closed inside every physics sub-step, the command or the target row as the
+ * differentiable action -- and the cotangents of the controller's 12 gains.  Policy gradients through the physics on thrust and
+ * body-rate actions.  The reference has no counterpart.
+ *
+ * gpd_rollout_tape_ctbr is gpd_rollout_ctbr (its arguments, in its order) plus a record of what the sweep needs.  Whatever it leaves
+ * behind -- state, last_rpm, step_counter, bad, obs12, cmd_out -- is bit for bit what gpd_rollout_ctbr leaves on the same inputs (the same
+ * load_carry / gpd_ctbr_outer / gpd_ctbr_rate_loop / substep / store_carry code).  The tape is opaque, 16-byte aligned,
+ * gpd_rollout_tape_ctbr_floats(cfg, num_steps, state.ld) = 13 * num_steps * ld floats: the 13 kinematic floats every control step starts
+ * from, 52 B per drone-step.  obs_step_stride 0 keeps the last step's rows only, as in gpd_rollout_ctbr.
+ *
+ * gpd_rollout_vjp_ctbr is the vector-Jacobian product of (kin_0, row_0 .. row_K-1, the 12 gains) -> (kin_K, obs12_0 ..) of that call:
+ *   ctbr, ld, mode, num_steps, rows, row_step_stride, plant_rows   what the taped call was given (ld = state.ld).  plant_rows is a
+ *                       constant of the sweep: the plant scales receive no gradient here
+ *   g_obs12             cotangents of obs12, laid out like it (stride 0: the last step's rows only); NULL = zeros.  16-byte aligned
+ *   g_kin               [13*ld], the four-plane layout of GpdState.kin, IN PLACE: the final state's cotangent on entry, the initial
+ *                       state's on return.  16-byte aligned
+ *   g_rows              [K][N][4] (GPD_CTBR_CMD) or [K][N][12] (GPD_CTBR_POS) out, 16-byte aligned, ALWAYS one block per step, also for a
+ *                       held row block (stride 0: the caller sums over the steps).  In GPD_CTBR_POS the rpy and rpy-rate slots of a row
+ *                       (floats 3 .. 5 and 9 .. 11), which the forward ignores, receive exact zeros
+ *   g_gains             NULL, or [12][ld] out, 16-byte aligned, drones 0 .. N-1 of every row overwritten: PER DRONE, the cotangents of
+ *                       k_p[3] | k_d[3] | k_rates[3] | k_rate[3] of GpdCtbr, summed over the steps in registers and stored once after the
+ *                       loop (the caller sums over drones).  In GPD_CTBR_CMD the first nine rows are zeros.  g_kin and g_rows do not
+ *                       depend by a bit on whether it is given
+ * One lane per drone, steps K-1 .. 0, the 13 cotangents in registers.  The RPMs change every sub-step, so sub-step j's start state is
+ * recomputed by j x (rate loop, sub-step) from the taped state: S(S+1)/2 of each per control step, no scratch memory, no per-sub-step
+ * tape.  No atomics: two calls give the same bits.  The adjoint is that of the function as executed (csrc/ctbr_vjp.inc): the thrust clip,
+ * the three rate clips and the per-rotor clip [0, f_max] pass their cotangent on lo <= x <= hi and exactly nothing outside; the chain
+ * rotor thrust -> RPM -> thrust deviation is one map with the derivative KF_plant / KF_nominal, so a rotor held at 0 never divides by its
+ * RPM; Shepperd's four cases and the q_e.w < 0 negation of the outer loop differentiate the branch taken; the three normalisations are
+ * differentiated as 1 / sqrt.  The clips, the allocation, g and the nominal M and J are constants of the sweep.
+ *
+ * Supported: what gpd_rollout_ctbr serves, with physics_flags == 0.  GPD_ENOTSUP, before any device work and with a message that names
+ * the entry and the reason: drones_per_env != 1, a task or auto_reset, an act_type other than GPD_ACT_RAW_RPM / GPD_ACT_DIRECT_RPM, ANY
+ * physics flag (drag's rpm sum has an infinite derivative where a rotor is held at 0; ground effect, the ground plane and damping are
+ * not differentiated anywhere), state.dw_force.  GPD_EINVAL: NULL pointers (plant_rows, cmd_out, g_obs12, g_gains excepted), an unknown
+ * mode or physics flag, misaligned kin / rows / obs12 / plant_rows / cmd_out / tape / g_obs12 / g_kin / g_rows / g_gains, bad strides
+ * or sizes, cmd_out == rows, g_rows / g_gains / g_kin / tape overlapping one another.  GPD_ERANGE: more than 2^26 drones.
+ */
+int gpd_rollout_tape_ctbr_floats(const GpdStepCfg* cfg, int32_t num_steps, int64_t ld, int64_t* floats_out);
+int gpd_rollout_tape_ctbr(const GpdParams* params, const GpdCtbr* ctbr, const GpdState* state, const GpdStepCfg* cfg, int32_t mode,
+                          const float* rows, int64_t row_step_stride, const float* plant_rows, float* obs12, int64_t obs_step_stride,
+                          float* cmd_out, int32_t num_steps, float* tape, void* stream);
+int gpd_rollout_vjp_ctbr(const GpdParams* params, const GpdCtbr* ctbr, const GpdStepCfg* cfg, int64_t ld, int32_t mode, int32_t num_steps,
+                         const float* rows, int64_t row_step_stride, const float* plant_rows, const float* tape, const float* g_obs12,
+                         int64_t obs_step_stride, float* g_kin, float* g_rows, float* g_gains, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
