@@ -603,5 +603,8 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
 // thrust and body-rate commands: gpd_sizeof_ctbr / gpd_ctbr / gpd_rollout_ctbr and their kernels
 #include "ctbr.inc"
 
+// ... and the planner over them: gpd_mppi_ctbr and its kernel (mppi.inc's two passes on ctbr_math.inc's rate loop)
+#include "mppi_ctbr.inc"
+
 // ... and the differentiable rollout through them: gpd_rollout_tape_ctbr_floats / gpd_rollout_tape_ctbr / gpd_rollout_vjp_ctbr
 #include "diff_ctbr_kernels.inc"

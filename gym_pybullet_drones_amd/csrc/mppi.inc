@@ -158,6 +158,28 @@ __global__ __launch_bounds__(kBlock) void gpd_mppi_kernel(const GpdParams P, con
     if (lane == 0) stats4[n] = make_float4(smin, any ? sws * inv_sw : GPD_OBST_INF, any ? (sw * sw) / sww : 0.0f, cnt);
 }
 
+// what gpd_mppi and gpd_mppi_ctbr refuse of the plan itself: the sampler, the buffers, the strides, the list (N: the drones)
+[[maybe_unused]] int check_mppi_plan(Refuse bad, const GpdMppi& q, int64_t N, const float* u_in, int64_t u_step_stride, const float* goal,
+                                     int64_t goal_step_stride, const float* obst, int32_t n_obst, int64_t obst_ld, const float* u_out,
+                                     const float* stats4) {
+    if (q.horizon < 1) return bad(GPD_EINVAL, "horizon must be >= 1");
+    if (q.samples < 64 || q.samples > 1024 || q.samples % 64 != 0) return bad(GPD_EINVAL, "samples must be a multiple of 64 in 64 .. 1024");
+    if (!(q.lambda > 0.0f) || !(q.lambda < GPD_OBST_INF)) return bad(GPD_EINVAL, "lambda must be positive and finite");
+    for (int i = 0; i < 4; ++i) {
+        if (!(q.sigma[i] >= 0.0f) || !(q.sigma[i] < GPD_OBST_INF)) return bad(GPD_EINVAL, "sigma must be non-negative and finite");
+        if (!(q.act_lo[i] <= q.act_hi[i])) return bad(GPD_EINVAL, "act_lo must not exceed act_hi");
+    }
+    if (u_out == u_in) return bad(GPD_EINVAL, "u_out must not alias u_in");
+    if (misaligned16(u_in) || misaligned16(u_out) || misaligned16(goal) || misaligned16(stats4))
+        return bad(GPD_EINVAL, "u_in, u_out, goal and stats4 must be 16-byte aligned");
+    if (u_step_stride % 4 != 0 || goal_step_stride % 4 != 0 || goal_step_stride < 0 || (goal_step_stride != 0 && goal_step_stride < 4 * N) ||
+        u_step_stride < (q.horizon > 1 ? 4 * N : 0))
+        return bad(GPD_EINVAL, "step strides must be multiples of 4 floats: u_step_stride >= 4 * num_envs, goal_step_stride 0 or >= 4 * num_envs");
+    if (n_obst < 0 || n_obst > GPD_OBST_MAX) return bad(GPD_EINVAL, "n_obst must be in 0..1024");
+    if (obst != nullptr && n_obst > 0 && obst_ld != 0 && obst_ld < N) return bad(GPD_EINVAL, "obst_ld must be 0 (one shared list) or >= num_envs (one list per aviary)");
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int gpd_mppi(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, const GpdMppi* mppi, const float* u_in,
@@ -179,22 +201,8 @@ extern "C" int gpd_mppi(const GpdParams* params, const GpdState* state, const Gp
     if (cfg->act_type != GPD_ACT_RPM && cfg->act_type != GPD_ACT_VEL) return bad(GPD_ENOTSUP, "act_type must be GPD_ACT_RPM or GPD_ACT_VEL");
     if (int rc = check_needs(bad, params, state, cfg, nullptr, nullptr)) return rc;
     const GpdMppi& q = *mppi;
-    if (q.horizon < 1) return bad(GPD_EINVAL, "horizon must be >= 1");
-    if (q.samples < 64 || q.samples > 1024 || q.samples % 64 != 0) return bad(GPD_EINVAL, "samples must be a multiple of 64 in 64 .. 1024");
-    if (!(q.lambda > 0.0f) || !(q.lambda < GPD_OBST_INF)) return bad(GPD_EINVAL, "lambda must be positive and finite");
-    for (int i = 0; i < 4; ++i) {
-        if (!(q.sigma[i] >= 0.0f) || !(q.sigma[i] < GPD_OBST_INF)) return bad(GPD_EINVAL, "sigma must be non-negative and finite");
-        if (!(q.act_lo[i] <= q.act_hi[i])) return bad(GPD_EINVAL, "act_lo must not exceed act_hi");
-    }
-    if (u_out == u_in) return bad(GPD_EINVAL, "u_out must not alias u_in");
-    if (misaligned16(u_in) || misaligned16(u_out) || misaligned16(goal) || misaligned16(stats4))
-        return bad(GPD_EINVAL, "u_in, u_out, goal and stats4 must be 16-byte aligned");
-    if (u_step_stride % 4 != 0 || goal_step_stride % 4 != 0 || goal_step_stride < 0 || (goal_step_stride != 0 && goal_step_stride < 4 * N) ||
-        u_step_stride < (q.horizon > 1 ? 4 * N : 0))
-        return bad(GPD_EINVAL, "step strides must be multiples of 4 floats: u_step_stride >= 4 * num_envs, goal_step_stride 0 or >= 4 * num_envs");
-    if (n_obst < 0 || n_obst > GPD_OBST_MAX) return bad(GPD_EINVAL, "n_obst must be in 0..1024");
+    if (int rc = check_mppi_plan(bad, q, N, u_in, u_step_stride, goal, goal_step_stride, obst, n_obst, obst_ld, u_out, stats4)) return rc;
     const bool has_obst = obst != nullptr && n_obst > 0;
-    if (has_obst && obst_ld != 0 && obst_ld < N) return bad(GPD_EINVAL, "obst_ld must be 0 (one shared list) or >= num_envs (one list per aviary)");
     auto launch = [&](auto act, auto ob) {
         hipLaunchKernelGGL((gpd_mppi_kernel<decltype(act)::value, decltype(ob)::value>), dim3(blocks_for(N, kMppiDrones)), dim3(kBlock), 0,
                            static_cast<hipStream_t>(stream), *params, *cfg, q, state->kin, state->pid, state->ld, static_cast<int>(N), u_in,

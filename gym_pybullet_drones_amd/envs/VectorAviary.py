@@ -306,6 +306,15 @@ class VectorAviary:
         return _mppi.MPPI(self.core, horizon, samples, sigma, lam, cost=cost, seed=seed, field=getattr(self, "_obstacles", None),
                           act_lo=act_lo, act_hi=act_hi)
 
+    def mppi_ctbr(self, ctrl, horizon: int, samples: int, sigma, lam: float, cost: "_mppi.MPPICost" = None, seed: int = 0, act_lo=None,
+                  act_hi=None) -> "_mppi.CTBRMPPI":
+        """An `mppi.CTBRMPPI` planner over thrust and body-rate commands bound to this batch (single drones, RPM actions:
+        `VectorCtrlAviary`), to `ctrl` (a `control.VectorCTBR` with one controller per drone) and to the field given to
+        `set_obstacles()`, if any: `plan(goal)` returns `(E, 4)` commands for `rollout_ctbr(ctrl, cmd, 1, mode="cmd")`.  The default
+        bounds are the controller's clips.  The planning model is the flag-less DYN integrator of the nominal airframe."""
+        return _mppi.CTBRMPPI(self.core, ctrl, horizon, samples, sigma, lam, cost=cost, seed=seed, field=getattr(self, "_obstacles", None),
+                              act_lo=act_lo, act_hi=act_hi)
+
     # ---- domain randomisation: the plant of every drone (include/gpd.h GPD_SCALE_*; SimCore.set_plant) ------------------------
     def set_physical_params(self, mask=None, **scales):
         """Scale the plant of every drone (or of the aviaries in the bool/uint8 `mask` [E]) relative to the nominal airframe:

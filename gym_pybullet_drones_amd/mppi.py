@@ -1,4 +1,5 @@
-"""Sampling-based model-predictive control on the device: the binding of `gpd_mppi` (include/gpd.h).
+"""Sampling-based model-predictive control on the device: the binding of `gpd_mppi` (include/gpd.h) and of
+`gpd_mppi_ctbr`, the same planner over thrust and body-rate commands (section 3.19).
 
 Per drone, M perturbed action sequences around a nominal one are rolled H env steps through the in-register physics, scored, and the
 nominal is replaced by their cost-weighted average (MPPI, Williams et al.): one launch per plan, no trajectory in memory.  The
@@ -18,6 +19,7 @@ from . import _native
 from . import obstacles as _ob
 
 ACT_RPM, ACT_VEL = 0, 2
+ACT_RAW_RPM, ACT_DIRECT_RPM = 5, 6        # what `CTBRMPPI`'s core flies (the rate loop's output is RPMs)
 #: the default bounds of a sample's action: [-1, 1]^4 for RPM; a direction in [-1, 1]^3 and a speed fraction in [0, 1] for VEL
 DEFAULT_BOUNDS = {ACT_RPM: ((-1.0,) * 4, (1.0,) * 4), ACT_VEL: ((-1.0, -1.0, -1.0, 0.0), (1.0, 1.0, 1.0, 1.0))}
 
@@ -37,17 +39,13 @@ class MPPICost:
     collision_radius: float = None
 
 
-class MPPI:
-    """A planner bound to a `SimCore` of single drones with RPM or VEL actions: the nominal sequence `[H, N, 4]`, the samples' `costs`
-    `[N, M]` and `stats` `[N, 4]` (min cost, weighted mean cost, effective sample size, finite samples) are tensors allocated once;
-    every launch goes to the core's stream.  `field`: an `obstacles.ObstacleField` (or the `FieldQuery` an aviary built from one)."""
+class _Planner:
+    """What `MPPI` and `CTBRMPPI` share: the sampler's struct, the model's configuration, the tensors, and `nominal` / `plan` /
+    `advance` / `reset`.  A subclass checks its core, then calls `_bind` with its default bounds; it names its entry (`_ENTRY`), the
+    arguments in front of `GpdState` (`_lead`) and its hover action (`_hover`)."""
+    _ENTRY = None
 
-    def __init__(self, core, horizon: int, samples: int, sigma, lam: float, cost: MPPICost = None, seed: int = 0, field=None,
-                 act_lo=None, act_hi=None):
-        if core.D != 1:
-            raise ValueError("MPPI plans for aviaries of one drone (drones_per_env must be 1)")
-        if core.act_code not in DEFAULT_BOUNDS:
-            raise ValueError("MPPI plans over RPM or VEL actions (ActionType.RPM / ActionType.VEL)")
+    def _bind(self, core, horizon, samples, sigma, lam, cost, seed, field, lo, hi, act_lo, act_hi):
         self.core, self.device, self.N = core, core.device, core.N
         self.H, self.M = int(horizon), int(samples)
         if self.H < 1 or self.M % 64 != 0 or not 64 <= self.M <= 1024:
@@ -55,7 +53,6 @@ class MPPI:
         if not (lam > 0.0 and math.isfinite(lam)):
             raise ValueError("lam must be positive and finite")
         cost = MPPICost() if cost is None else cost
-        lo, hi = DEFAULT_BOUNDS[core.act_code]
         lo, hi = (lo if act_lo is None else tuple(act_lo)), (hi if act_hi is None else tuple(act_hi))
         sigma = (float(sigma),) * 4 if isinstance(sigma, (int, float)) else tuple(float(s) for s in sigma)
         if len(sigma) != 4 or len(lo) != 4 or len(hi) != 4:
@@ -88,11 +85,18 @@ class MPPI:
         """the nominal action sequence `[H, N, 4]` (the tensor the next plan starts from)"""
         return self._u[0]
 
+    def _lead(self) -> tuple:
+        """the entry's arguments in front of `GpdState`"""
+        return (self.core._params,)
+
+    def _hover(self) -> tuple:
+        raise NotImplementedError
+
     def reset(self, rows=None, value=None):
         """Set the nominal of the drones `rows` (index or mask tensor; None: all) to `value` (4 numbers or `[.., 4]`; None: hover --
-        zeros for RPM, a zero speed along +x for VEL, which commands a stop)."""
+        zeros for RPM, a zero speed along +x for VEL, which commands a stop, the thrust g without rates for CTBR)."""
         if value is None:
-            value = (0.0, 0.0, 0.0, 0.0) if self.core.act_code == ACT_RPM else (1.0, 0.0, 0.0, 0.0)
+            value = self._hover()
         v = torch.as_tensor(value, dtype=torch.float32, device=self.device)
         if rows is None:
             self._u[0][:] = v
@@ -103,7 +107,7 @@ class MPPI:
         self._q.iteration = self.iteration & 0xFFFFFFFF
         obst, n_obst, ld = self._obst
         c = self.core
-        _native.call("gpd_mppi", self.device, c._stream(), c._params, c._state, self._cfg, self._q, self._u[0], self.N * 4, goal, goal_stride,
+        _native.call(self._ENTRY, self.device, c._stream(), *self._lead(), c._state, self._cfg, self._q, self._u[0], self.N * 4, goal, goal_stride,
                      obst, n_obst, ld, self._u[1], self.costs, self.stats)
         self._u.reverse()
         self.iteration += 1
@@ -131,3 +135,50 @@ class MPPI:
             v[:-1] = u[1:]
         v[-1] = u[-1]
         self._u.reverse()
+
+
+class MPPI(_Planner):
+    """A planner bound to a `SimCore` of single drones with RPM or VEL actions: the nominal sequence `[H, N, 4]`, the samples' `costs`
+    `[N, M]` and `stats` `[N, 4]` (min cost, weighted mean cost, effective sample size, finite samples) are tensors allocated once;
+    every launch goes to the core's stream.  `field`: an `obstacles.ObstacleField` (or the `FieldQuery` an aviary built from one)."""
+    _ENTRY = "gpd_mppi"
+
+    def __init__(self, core, horizon: int, samples: int, sigma, lam: float, cost: MPPICost = None, seed: int = 0, field=None,
+                 act_lo=None, act_hi=None):
+        if core.D != 1:
+            raise ValueError("MPPI plans for aviaries of one drone (drones_per_env must be 1)")
+        if core.act_code not in DEFAULT_BOUNDS:
+            raise ValueError("MPPI plans over RPM or VEL actions (ActionType.RPM / ActionType.VEL)")
+        self._bind(core, horizon, samples, sigma, lam, cost, seed, field, *DEFAULT_BOUNDS[core.act_code], act_lo, act_hi)
+
+    def _hover(self) -> tuple:
+        return (0.0, 0.0, 0.0, 0.0) if self.core.act_code == ACT_RPM else (1.0, 0.0, 0.0, 0.0)
+
+
+class CTBRMPPI(_Planner):
+    """`MPPI` over thrust and body-rate commands (`gpd_mppi_ctbr`): a sample's action is a command `(thrust
+    [m/s^2], body rates x, y, z [rad/s])` held over the control step, and the model runs `ctrl`'s body-rate loop inside every physics
+    sub-step, exactly as `SimCore.rollout_ctbr(ctrl, cmd, K, mode="cmd")` flies it.  `core`: aviaries of one drone with RAW_RPM or
+    DIRECT_RPM actions (`VectorCtrlAviary`), what `rollout_ctbr` requires; `ctrl`: a `control.VectorCTBR` of `core.N` controllers on
+    the core's device.  The default bounds are the controller's clips, `(0, -rate_max x 3) .. (thrust_max, +rate_max x 3)`; wider ones
+    are legal, the rate loop clips.  The default nominal is the hover command `(g, 0, 0, 0)` with the controller's `g`.  `plan()`
+    returns `[N, 4]` commands for `rollout_ctbr(ctrl, cmd, 1, mode="cmd")`."""
+    _ENTRY = "gpd_mppi_ctbr"
+
+    def __init__(self, core, ctrl, horizon: int, samples: int, sigma, lam: float, cost: MPPICost = None, seed: int = 0, field=None,
+                 act_lo=None, act_hi=None):
+        if core.D != 1:
+            raise ValueError("CTBRMPPI plans for aviaries of one drone (drones_per_env must be 1)")
+        if core.act_code not in (ACT_RAW_RPM, ACT_DIRECT_RPM):
+            raise ValueError("CTBRMPPI needs a core with RAW_RPM or DIRECT_RPM actions (the rate loop's output is RPMs), as rollout_ctbr")
+        if getattr(ctrl, "n", None) != core.N or ctrl.device != core.device or not hasattr(ctrl, "thrust_max"):
+            raise ValueError(f"CTBRMPPI needs a VectorCTBR of {core.N} controllers on {core.device}")
+        self.ctrl = ctrl
+        r = ctrl.rate_max
+        self._bind(core, horizon, samples, sigma, lam, cost, seed, field, (0.0, -r, -r, -r), (ctrl.thrust_max, r, r, r), act_lo, act_hi)
+
+    def _lead(self) -> tuple:
+        return (self.core._params, self.ctrl.struct())
+
+    def _hover(self) -> tuple:
+        return (float(self.ctrl.struct().g), 0.0, 0.0, 0.0)

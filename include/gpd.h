@@ -750,7 +750,28 @@ int gpd_mppi(const GpdParams* params, const GpdState* state, const GpdStepCfg* c
              float* u_out, float* costs, float* stats4, void* stream);
 
 /*
- * Masked reset.  Replaces BaseAviary.reset/_housekeeping (envs/BaseAviary.py:220-255, 451-477)
+ * gpd_mppi over thrust and body-rate commands (struct GpdCtbr and gpd_rollout_ctbr, below): the semantics of gpd_mppi word for word --
+ * noise, clamp, cost terms, softmax over the finite costs, u_out, costs, stats4, strides, obstacle lists, struct GpdMppi -- except
+ *   a     a CTBR command: thrust [m/s^2], then body rates x, y, z [rad/s]; clamp(u_in[h][n] + sigma o z, act_lo, act_hi) as above
+ *   step  one control step exactly as gpd_rollout_ctbr takes it in GPD_CTBR_CMD with physics_flags 0 and no plant table: the command
+ *         is held, and in every one of `substeps` sub-steps the rate loop (csrc/ctbr_math.inc, the controller's M and J those of
+ *         `params`) gives the RPMs from the integrator's own body rates.  The rate loop clips the command to [0, thrust_max] and
+ *         +-rate_max and the rotor thrusts to [0, f_max]: bounds wider than the clips are legal and act as the clips.
+ * state.last_rpm is not read (no drag), nothing of GpdState is written.
+ *   ctbr            HOST pointer, like GpdParams
+ *   cfg             as for gpd_mppi, but act_type GPD_ACT_RAW_RPM or GPD_ACT_DIRECT_RPM, as gpd_rollout_ctbr has it
+ * Refused before any device work, every message starting "gpd_mppi_ctbr: ".  GPD_EINVAL: everything gpd_mppi answers with it
+ * (state.pid is never needed), and NULL ctbr.  GPD_ENOTSUP: drones_per_env != 1, any physics flag, a task or auto_reset, any other
+ * action type.  GPD_ERANGE: N > 2^26.  Asynchronous on `stream`, no allocation, one launch; two calls with the same arguments give
+ * the same bits.  DESIGN.md section 3.19.
+ */
+struct GpdCtbr;
+int gpd_mppi_ctbr(const GpdParams* params, const struct GpdCtbr* ctbr, const GpdState* state, const GpdStepCfg* cfg, const GpdMppi* mppi,
+                  const float* u_in, int64_t u_step_stride, const float* goal, int64_t goal_step_stride, const float* obst, int32_t n_obst,
+                  int64_t obst_ld, float* u_out, float* costs, float* stats4, void* stream);
+
+/*
+ * Masked reset. Replaces BaseAviary.reset/_housekeeping (envs/BaseAviary.py:220-255, 451-477)
  * for the envs whose mask byte is non-zero (mask == NULL: all).  Sets pos/quat to init_pose,
  * vel, rpy_rates, last_rpm and step_counter to zero and writes the initial obs12 rows.  As in
  * the reference, the DSLPID state is NOT reset unless reset_pid != 0.
