@@ -606,5 +606,8 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
 // ... and the planner over them: gpd_mppi_ctbr and its kernel (mppi.inc's two passes on ctbr_math.inc's rate loop)
 #include "mppi_ctbr.inc"
 
+// ... and the planner that keeps away from the other drones' published paths: gpd_mppi_peers and its kernel
+#include "mppi_peers.inc"
+
 // ... and the differentiable rollout through them: gpd_rollout_tape_ctbr_floats / gpd_rollout_tape_ctbr / gpd_rollout_vjp_ctbr
 #include "diff_ctbr_kernels.inc"

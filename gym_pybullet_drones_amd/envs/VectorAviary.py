@@ -315,6 +315,16 @@ class VectorAviary:
         return _mppi.CTBRMPPI(self.core, ctrl, horizon, samples, sigma, lam, cost=cost, seed=seed, field=getattr(self, "_obstacles", None),
                               act_lo=act_lo, act_hi=act_hi)
 
+    def mppi_swarm(self, horizon: int, samples: int, sigma, lam: float, cost: "_mppi.MPPICost" = None, seed: int = 0, ctrl=None, k: int = 8,
+                   radius: float = None, w_peer: float = 100.0, peer_dist: float = None, intruders: int = 0, box=None, act_lo=None,
+                   act_hi=None) -> "_mppi.SwarmMPPI":
+        """An `mppi.SwarmMPPI` planner bound to this batch and to the field given to `set_obstacles()`, if any: `mppi()` (or, with
+        `ctrl`, `mppi_ctbr()`) for single drones that SHARE ONE AIRSPACE -- every drone's cost also keeps it `peer_dist` away from
+        where its `k` nearest peers last published they would be, and every plan publishes the drone's own path (`gpd_mppi_peers`,
+        one launch per plan)."""
+        return _mppi.SwarmMPPI(self.core, horizon, samples, sigma, lam, cost=cost, seed=seed, field=getattr(self, "_obstacles", None), ctrl=ctrl,
+                               k=k, radius=radius, w_peer=w_peer, peer_dist=peer_dist, intruders=intruders, box=box, act_lo=act_lo, act_hi=act_hi)
+
     # ---- domain randomisation: the plant of every drone (include/gpd.h GPD_SCALE_*; SimCore.set_plant) ------------------------
     def set_physical_params(self, mask=None, **scales):
         """Scale the plant of every drone (or of the aviaries in the bool/uint8 `mask` [E]) relative to the nominal airframe:

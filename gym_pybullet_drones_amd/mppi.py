@@ -1,5 +1,6 @@
 """Sampling-based model-predictive control on the device: the binding of `gpd_mppi` (include/gpd.h) and of
-`gpd_mppi_ctbr`, the same planner over thrust and body-rate commands (section 3.19).
+`gpd_mppi_ctbr`, the same planner over thrust and body-rate commands (section 3.19), and of `gpd_mppi_peers`, either of them with the
+other drones' published paths in the cost (section 3.20).
 
 Per drone, M perturbed action sequences around a nominal one are rolled H env steps through the in-register physics, scored, and the
 nominal is replaced by their cost-weighted average (MPPI, Williams et al.): one launch per plan, no trajectory in memory.  The
@@ -16,6 +17,7 @@ import math
 import torch
 
 from . import _native
+from . import neighbors as _nb
 from . import obstacles as _ob
 
 ACT_RPM, ACT_VEL = 0, 2
@@ -182,3 +184,135 @@ class CTBRMPPI(_Planner):
 
     def _hover(self) -> tuple:
         return (float(self.ctrl.struct().g), 0.0, 0.0, 0.0)
+
+
+class SwarmMPPI(_Planner):
+    """`MPPI` (`ctrl=None`: a core of single drones with RPM or VEL actions) or `CTBRMPPI` (`ctrl`: a `control.VectorCTBR`; a core with
+    RAW_RPM or DIRECT_RPM actions) for drones that SHARE ONE AIRSPACE (`gpd_mppi_peers`): the N single-drone
+    aviaries of `core` are taken to fly in the same world, and the running cost gets `w_peer * sum_j max(0, peer_dist - |p - p_j(h)|)^2`
+    over the drone's `k` nearest peers within `radius`, p_j(h) where peer j last PUBLISHED it would be after step h.  Every launch plans
+    all drones against table A of published paths `[H, N + intruders, 4]` and publishes the paths of the new nominals into table B,
+    then the tables swap: every drone answers its peers' previous paths (a Jacobi iteration), all in one launch, decentralised.
+
+    `peer_dist` None: `2 * COLLISION_R + cost.obst_margin` (two hulls and the margin the obstacles get).  `radius` None:
+    `peer_dist + 2 * SPEED_LIMIT * horizon * ctrl_dt` -- two drones that fly at each other at the speed limit for the whole horizon
+    close that much; a peer beyond it cannot come within `peer_dist` inside the horizon.  `intruders`: rows N .. N + intruders - 1 of
+    the tables are other moving bodies whose paths the caller gives to `plan()`; every drone counts every one of them
+    (`k + intruders <= 32`).  `box` (x0, y0, x1, y1): the neighbour search's grid; None: the bounds of the current positions padded by
+    `radius`, recomputed by `reset()` (it changes the search's speed, never its result).  `SwarmAviary` has no binding: its core runs
+    one sub-step per control step, and a multi-rank world numbers peers across ranks."""
+    _ENTRY = "gpd_mppi_peers"
+
+    def __init__(self, core, horizon: int, samples: int, sigma, lam: float, cost: MPPICost = None, seed: int = 0, field=None, ctrl=None,
+                 k: int = 8, radius: float = None, w_peer: float = 100.0, peer_dist: float = None, intruders: int = 0, box=None,
+                 act_lo=None, act_hi=None):
+        if core.D != 1:
+            raise ValueError("SwarmMPPI plans for aviaries of one drone (drones_per_env must be 1)")
+        if ctrl is None:
+            if core.act_code not in DEFAULT_BOUNDS:
+                raise ValueError("SwarmMPPI without ctrl plans over RPM or VEL actions (ActionType.RPM / ActionType.VEL)")
+            lo, hi = DEFAULT_BOUNDS[core.act_code]
+        else:
+            if core.act_code not in (ACT_RAW_RPM, ACT_DIRECT_RPM):
+                raise ValueError("SwarmMPPI with ctrl needs a core with RAW_RPM or DIRECT_RPM actions (the rate loop's output is RPMs), as rollout_ctbr")
+            if getattr(ctrl, "n", None) != core.N or ctrl.device != core.device or not hasattr(ctrl, "thrust_max"):
+                raise ValueError(f"SwarmMPPI needs a VectorCTBR of {core.N} controllers on {core.device}")
+            r = ctrl.rate_max
+            lo, hi = (0.0, -r, -r, -r), (ctrl.thrust_max, r, r, r)
+        self.ctrl, self.intruders = ctrl, int(intruders)
+        cost = MPPICost() if cost is None else cost
+        peer_dist = 2.0 * core.P.COLLISION_R + cost.obst_margin if peer_dist is None else float(peer_dist)
+        w_peer = float(w_peer)
+        if not (w_peer >= 0.0 and math.isfinite(w_peer) and peer_dist >= 0.0 and math.isfinite(peer_dist)):
+            raise ValueError("w_peer and peer_dist must be non-negative and finite")
+        if self.intruders < 0 or int(k) + self.intruders > _nb.MAX_K:
+            raise ValueError(f"intruders must be >= 0 and k + intruders <= {_nb.MAX_K}")
+        if int(horizon) < 1:
+            raise ValueError("horizon must be >= 1 and samples a multiple of 64 in 64..1024")
+        radius = peer_dist + 2.0 * core.P.SPEED_LIMIT * int(horizon) * core._cfg.ctrl_dt if radius is None else radius
+        self.radius, self.k = _nb.check_args(radius, k)
+        self.peer_dist, self.w_peer, self._box = peer_dist, w_peer, None if box is None else tuple(float(v) for v in box)
+        self._paths = None
+        self._bind(core, horizon, samples, sigma, lam, cost, seed, field, lo, hi, act_lo, act_hi)
+        # the nominals and the tables share ONE row stride, N + intruders rows: path_out has the layout and stride of u_out
+        rows, f32 = self.N + self.intruders, dict(dtype=torch.float32, device=self.device)
+        self._rows = rows
+        if self.intruders:
+            self._u = [torch.zeros((self.H, rows, 4), **f32)[:, :self.N] for _ in range(2)]
+        self._paths = [torch.full((self.H, rows, 4), float("nan"), **f32) for _ in range(2)]
+        self._idx = torch.full((self.N, self.k + self.intruders), -1, dtype=torch.int32, device=self.device)
+        if self.intruders:
+            self._idx[:, self.k:] = torch.arange(self.N, rows, dtype=torch.int32, device=self.device)
+        self._r = _native.GpdMppiPeers(idx=self._idx.data_ptr(), pos_step_stride=rows * 4, k=self.k + self.intruders, idx_ld=self.k + self.intruders,
+                                       n_rows=rows, w_peer=w_peer, peer_dist=peer_dist)
+        self.reset()
+
+    def _hover(self) -> tuple:
+        if self.ctrl is not None:
+            return (float(self.ctrl.struct().g), 0.0, 0.0, 0.0)
+        return (0.0, 0.0, 0.0, 0.0) if self.core.act_code == ACT_RPM else (1.0, 0.0, 0.0, 0.0)
+
+    @property
+    def paths(self) -> torch.Tensor:
+        """the published paths `[H, N, 4]`: x, y, z after each step of the nominal, and the distance to the nearest counted peer there"""
+        return self._paths[0][:, :self.N]
+
+    @property
+    def min_separation(self) -> torch.Tensor:
+        """`[N]`: the smallest distance to a counted peer's published path along the drone's own published path (+inf: no peer)"""
+        return self.paths[..., 3].amin(dim=0)
+
+    def reset(self, rows=None, value=None):
+        """`_Planner.reset`, and the published paths are forgotten: the next `plan()` starts from constant-velocity paths.  Without a
+        `box` the search's grid is laid over the current positions again (one host synchronisation)."""
+        super().reset(rows, value)
+        if self._paths is None:             # (the base's own call, before the tables exist)
+            return
+        self._published = False
+        box = self._box
+        if box is None:
+            p = self.core.kin_P[:self.N, :2]
+            lo, hi = p.amin(dim=0).tolist(), p.amax(dim=0).tolist()
+            box = (lo[0] - self.radius, lo[1] - self.radius, hi[0] + self.radius, hi[1] + self.radius)
+        self.search = _nb.WorldSearch(self.device, self.N, 0, self.N, self.radius, self.k, box, rel=False)
+
+    def _launch(self, goal, goal_stride):
+        self._q.iteration = self.iteration & 0xFFFFFFFF
+        obst, n_obst, ld = self._obst
+        c, r = self.core, self._r
+        r.pos, r.path_out = self._paths[0].data_ptr(), self._paths[1].data_ptr()
+        _native.call(self._ENTRY, self.device, c._stream(), c._params, None if self.ctrl is None else self.ctrl.struct(), c._state, self._cfg,
+                     self._q, r, self._u[0], self._rows * 4, goal, goal_stride, obst, n_obst, ld, self._u[1], self.costs, self.stats)
+        if self.intruders:
+            self._paths[1][:, self.N:] = self._paths[0][:, self.N:]
+        self._u.reverse()
+        self._paths.reverse()
+        self.iteration += 1
+
+    def plan(self, goal, iterations: int = 1, intruder_paths=None) -> torch.Tensor:
+        """`_Planner.plan` against the peers: the k-nearest lists are refreshed ONCE per call from the current positions; if nothing is
+        published yet (or after `reset()`) the table is filled by constant velocity from the current state; then `iterations`
+        launches, each reading table A and writing the drones' rows of table B, then swapping.  `intruder_paths` `[H, intruders, 3]`
+        (or `[.., 4]`): where the other bodies will be after each step; None: the rows stay what they were (NaN, not counted, until
+        given once).  No host synchronisation."""
+        c = self.core
+        found = self.search(c.kin_P, c._stream())
+        self._idx[:, :self.k] = found.idx
+        if not self._published:
+            steps = torch.arange(1, self.H + 1, dtype=torch.float32, device=self.device)[:, None, None] * self._cfg.ctrl_dt
+            self._paths[0][:, :self.N, :3] = c.kin_P[None, :self.N, :3] + steps * c.kin_V[None, :self.N, :3]
+            self._paths[0][:, :self.N, 3] = 0.0
+            self._published = True
+        if intruder_paths is not None:
+            t = torch.as_tensor(intruder_paths, dtype=torch.float32, device=self.device)
+            self._paths[0][:, self.N:, :t.shape[-1]] = t
+        return super().plan(goal, iterations)
+
+    def advance(self):
+        """The warm start of the next plan: shift the nominal AND the published paths one step, repeating their last rows."""
+        super().advance()
+        a, b = self._paths
+        if self.H > 1:
+            b[:-1] = a[1:]
+        b[-1] = a[-1]
+        self._paths.reverse()

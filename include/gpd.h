@@ -771,6 +771,45 @@ int gpd_mppi_ctbr(const GpdParams* params, const struct GpdCtbr* ctbr, const Gpd
                   int64_t obst_ld, float* u_out, float* costs, float* stats4, void* stream);
 
 /*
+ * MPPI that keeps away from moving PEERS -- the other drones of one airspace, and other moving bodies: gpd_mppi (ctbr NULL: its model
+ * and action types) or gpd_mppi_ctbr (ctbr given: its model and action types) word for word -- noise, clamp, model step, the other
+ * cost terms, softmax over the finite costs, u_out, costs, stats4, strides, obstacle lists, a state that is only read -- with one more
+ * term in the running cost and one more output.  The N single-drone aviaries are taken to share one airspace.
+ *   c_h  += w_peer * sum over the counted entries j = 0 .. k-1 of drone n's row of `idx`, in that order, of
+ *           max(0, peer_dist - |p - pos[h][idx[n][j]]|)^2        (csrc/mppi_peers_math.inc), p the sample's position AFTER step h,
+ *         added after the other terms' sum.  An entry < 0, >= n_rows or equal to n is not counted (and ends nothing: later entries
+ *         count); a row of pos that is not finite adds 0; a peer at p itself adds peer_dist^2.  The term is continuous and C1 in p.
+ *         With no counted entry, or w_peer = 0, u_out, costs and stats4 are those of gpd_mppi / gpd_mppi_ctbr bit for bit.
+ *   pos, pos_step_stride   [H][n_rows][4] x, y, z, (ignored), 16-byte aligned: where row r is AFTER step h (a peer's path_out of an
+ *         earlier call, or any prediction); rows 0 .. N-1 are the planned drones, rows beyond them other bodies.  Stride 0: ONE row
+ *         set [n_rows][4] for every step (peers held where they are); else a multiple of 4 floats, >= 4 n_rows
+ *   idx, k, idx_ld         [N][idx_ld] int32, 1 <= k <= 32 entries read per drone (the k-nearest lists of gpd_neighbors, -1 padded,
+ *         are such rows)
+ *   path_out   [H][N][4] out or NULL, the layout and stride of u_out, 16-byte aligned; must not be u_in or u_out, and must not
+ *         overlap pos.  After the update the NEW nominal -- u_out as stored, the clamped one -- is flown without noise from the
+ *         start state through the same model: x, y, z the position after step h, w the distance to the nearest counted peer at
+ *         that step (+inf: none).  One writer per row.
+ * Refused before any device work, every message starting "gpd_mppi_peers: ".  GPD_EINVAL: everything the model's own entry answers
+ * with it, and NULL peers / idx / pos, k outside 1 .. 32, idx_ld < k, n_rows < N, a pos_step_stride that is neither 0 nor a multiple
+ * of 4 >= 4 n_rows, a misaligned pos or path_out, path_out equal to u_in or u_out, w_peer or peer_dist negative or not finite.
+ * GPD_ENOTSUP, GPD_ERANGE: as the model's own entry.  Asynchronous on `stream`, no allocation, one launch, no atomics; two calls
+ * with the same arguments give the same bits.  DESIGN.md section 3.20.
+ */
+typedef struct GpdMppiPeers {
+    const int32_t* idx;       /* device [N][idx_ld]: rows of `pos` to keep away from; an entry < 0, >= n_rows, or equal to the drone's own row n is skipped (not a terminator) */
+    const float*   pos;       /* device [H][n_rows][4] x, y, z, (ignored), 16-byte aligned: where row r is AFTER step h; rows 0 .. N-1 are the planned drones, rows beyond them other moving bodies */
+    float*         path_out;  /* device [H][N][4] or NULL, the layout and stride of u_out: see above */
+    int64_t pos_step_stride;  /* floats; 0: one table row set for every step (peers held where they are), else a multiple of 4, >= 4 n_rows */
+    int32_t k, idx_ld;        /* 1 <= k <= 32 (neighbors.MAX_K), idx_ld >= k */
+    int32_t n_rows;           /* >= N */
+    float w_peer, peer_dist;  /* c_h += w_peer * sum over the counted entries j = 0 .. k-1, in that order, of max(0, peer_dist - |p - pos[h][idx[n][j]]|)^2 */
+} GpdMppiPeers;
+int gpd_mppi_peers(const GpdParams* params, const struct GpdCtbr* ctbr /* NULL: gpd_mppi's model and action types; else gpd_mppi_ctbr's */,
+                   const GpdState* state, const GpdStepCfg* cfg, const GpdMppi* mppi, const GpdMppiPeers* peers, const float* u_in,
+                   int64_t u_step_stride, const float* goal, int64_t goal_step_stride, const float* obst, int32_t n_obst, int64_t obst_ld,
+                   float* u_out, float* costs, float* stats4, void* stream);
+
+/*
  * Masked reset. Replaces BaseAviary.reset/_housekeeping (envs/BaseAviary.py:220-255, 451-477)
  * for the envs whose mask byte is non-zero (mask == NULL: all).  Sets pos/quat to init_pose,
  * vel, rpy_rates, last_rpm and step_counter to zero and writes the initial obs12 rows.  As in
