@@ -31,7 +31,7 @@ ABI_VERSION = 9
 #   policy.hip        gpd_rollout_policy                 the default scheduler: 10 % faster on its MFMA + activation mix (round-2 A/B)
 #   swarm.hip         the one-world kernels              max-ilp, as in rounds 2-4
 #   abi.hip           small kernels, RCCL, library-level entries; the differentiable rollout (RPM and DSLPID), gpd_obstacles, gpd_mppi and the
-#                     thrust-and-body-rate controller gpd_ctbr / gpd_rollout_ctbr with its planner gpd_mppi_ctbr, gpd_mppi_peers and its differentiable
+#                     thrust-and-body-rate controller gpd_ctbr / gpd_rollout_ctbr with its planner gpd_mppi_ctbr, gpd_mppi_peers, gpd_mppi_plant and its differentiable
 #                     rollout (csrc/*.inc pulled in at its end)
 #   mrac.hip          gpd_mrac / gpd_mrac_reset / gpd_rollout_mrac: the adaptive controller and the rollout that carries it (max-ilp)
 #   -mllvm -amdgpu-kernarg-preload-count=14: the first 14 argument dwords of a kernel arrive in SGPRs with the wave (gfx942+ command
@@ -41,7 +41,7 @@ MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 HIPCC_FLAGS = COMMON_FLAGS + MAX_ILP + ["-shared"]        # (kept under this name for the ISA tests)
 UNITS = (("step_rollout.hip", MAX_ILP + KERNARG_PRELOAD), ("policy.hip", []), ("swarm.hip", MAX_ILP + KERNARG_PRELOAD), ("abi.hip", MAX_ILP), ("mrac.hip", MAX_ILP))
-HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc", "diff_pid_kernels.inc", "dslpid_vjp.inc", "obstacle_math.inc", "obstacles.inc", "mppi_math.inc", "mppi.inc", "ctbr_math.inc", "ctbr.inc", "mppi_ctbr.inc", "mppi_peers_math.inc", "mppi_peers.inc", "ctbr_vjp.inc", "diff_ctbr_kernels.inc")
+HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc", "diff_pid_kernels.inc", "dslpid_vjp.inc", "obstacle_math.inc", "obstacles.inc", "mppi_math.inc", "mppi.inc", "ctbr_math.inc", "ctbr.inc", "mppi_ctbr.inc", "mppi_peers_math.inc", "mppi_peers.inc", "mppi_plant.inc", "ctbr_vjp.inc", "diff_ctbr_kernels.inc")
 
 
 class GpdError(RuntimeError):
@@ -211,6 +211,9 @@ _SIGNATURES = {
     "gpd_mppi_peers": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdCtbr), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg),
                                       ctypes.POINTER(GpdMppi), ctypes.POINTER(GpdMppiPeers), _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int32,
                                       ctypes.c_int64, _P, _P, _P, _P]),
+    "gpd_mppi_plant": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdCtbr), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg),
+                                      ctypes.POINTER(GpdMppi), _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int32, ctypes.c_int64,
+                                      _P, _P, _P, _P]),
     "gpd_reset": (ctypes.c_int, [ctypes.POINTER(GpdState), _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32,
                                  ctypes.c_int32, _P, _P]),
     "gpd_pid": (ctypes.c_int, [ctypes.POINTER(GpdParams), _P, ctypes.c_int64, ctypes.c_float, _P, _P, _P, _P, _P, _P,

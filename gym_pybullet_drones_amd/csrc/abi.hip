@@ -609,5 +609,8 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
 // ... and the planner that keeps away from the other drones' published paths: gpd_mppi_peers and its kernel
 #include "mppi_peers.inc"
 
+// ... and the planner on the aviary's own model, plant rows and force terms: gpd_mppi_plant and its kernel
+#include "mppi_plant.inc"
+
 // ... and the differentiable rollout through them: gpd_rollout_tape_ctbr_floats / gpd_rollout_tape_ctbr / gpd_rollout_vjp_ctbr
 #include "diff_ctbr_kernels.inc"

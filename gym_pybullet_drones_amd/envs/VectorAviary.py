@@ -298,22 +298,23 @@ class VectorAviary:
 
     # ---- sampling-based MPC (include/gpd.h gpd_mppi; the reference has no planner) ---------------------------------------------------
     def mppi(self, horizon: int, samples: int, sigma, lam: float, cost: "_mppi.MPPICost" = None, seed: int = 0, act_lo=None,
-             act_hi=None) -> "_mppi.MPPI":
+             act_hi=None, model: str = "nominal", plant=None) -> "_mppi.MPPI":
         """An `mppi.MPPI` planner bound to this batch (single drones, RPM or VEL actions) and to the field given to `set_obstacles()`,
         if any: `plan(goal)` returns the next action `(E, 4)` from the current state, `advance()` shifts the nominal after it was
-        flown.  The default bounds are [-1, 1]^4 for RPM and [-1, 1]^3 x [0, 1] for VEL.  The planning model is the flag-less DYN
-        integrator, whatever `physics` this batch was built with."""
+        flown.  The default bounds are [-1, 1]^4 for RPM and [-1, 1]^3 x [0, 1] for VEL.  `model="nominal"`: the planning model is
+        the flag-less DYN integrator of the nominal airframe, whatever this batch flies; `model="aviary"`: this batch's `physics` flags
+        and its per-drone airframes as they are at each plan (`randomize=`, `set_physical_params`), or the belief `plant`."""
         return _mppi.MPPI(self.core, horizon, samples, sigma, lam, cost=cost, seed=seed, field=getattr(self, "_obstacles", None),
-                          act_lo=act_lo, act_hi=act_hi)
+                          act_lo=act_lo, act_hi=act_hi, model=model, plant=plant)
 
     def mppi_ctbr(self, ctrl, horizon: int, samples: int, sigma, lam: float, cost: "_mppi.MPPICost" = None, seed: int = 0, act_lo=None,
-                  act_hi=None) -> "_mppi.CTBRMPPI":
+                  act_hi=None, model: str = "nominal", plant=None) -> "_mppi.CTBRMPPI":
         """An `mppi.CTBRMPPI` planner over thrust and body-rate commands bound to this batch (single drones, RPM actions:
         `VectorCtrlAviary`), to `ctrl` (a `control.VectorCTBR` with one controller per drone) and to the field given to
         `set_obstacles()`, if any: `plan(goal)` returns `(E, 4)` commands for `rollout_ctbr(ctrl, cmd, 1, mode="cmd")`.  The default
-        bounds are the controller's clips.  The planning model is the flag-less DYN integrator of the nominal airframe."""
+        bounds are the controller's clips.  `model`, `plant`: as for `mppi()`."""
         return _mppi.CTBRMPPI(self.core, ctrl, horizon, samples, sigma, lam, cost=cost, seed=seed, field=getattr(self, "_obstacles", None),
-                              act_lo=act_lo, act_hi=act_hi)
+                              act_lo=act_lo, act_hi=act_hi, model=model, plant=plant)
 
     def mppi_swarm(self, horizon: int, samples: int, sigma, lam: float, cost: "_mppi.MPPICost" = None, seed: int = 0, ctrl=None, k: int = 8,
                    radius: float = None, w_peer: float = 100.0, peer_dist: float = None, intruders: int = 0, box=None, act_lo=None,

@@ -1,14 +1,18 @@
 """Sampling-based model-predictive control on the device: the binding of `gpd_mppi` (include/gpd.h) and of
 `gpd_mppi_ctbr`, the same planner over thrust and body-rate commands (section 3.19), and of `gpd_mppi_peers`, either of them with the
-other drones' published paths in the cost (section 3.20).
+other drones' published paths in the cost (section 3.20), and of `gpd_mppi_plant`, either of them on the aviary's own model (section 3.21).
 
 Per drone, M perturbed action sequences around a nominal one are rolled H env steps through the in-register physics, scored, and the
 nominal is replaced by their cost-weighted average (MPPI, Williams et al.): one launch per plan, no trajectory in memory.  The
 reference has no planner; its examples steer by hand-written DSLPID set-points.
 
-THE PLANNING MODEL IS THE FLAG-LESS DYN INTEGRATOR of a single drone: `physics_flags` is 0 whatever the environment's is (no drag,
-ground effect, downwash, ground plane or damping), the plant is the nominal airframe, and there are no episode ends.  The environment
-the plan is flown in may have all of these; the plan is then a plan under a simpler model, as in any MPC.
+The planning model is a single drone without episode ends, and `MPPI` / `CTBRMPPI` offer two of them.  `model="nominal"` (the default)
+is the nominal airframe under the flag-less DYN integrator, whatever the environment flies: no drag, ground effect, ground plane or
+damping, and no plant table -- a plan under a simpler model, as in any MPC.  `model="aviary"` is the core's own model: its
+`physics_flags` (ground effect, drag, the ground plane, damping) and, per drone, whatever plant table the core holds at each launch
+(`SimCore.set_plant`, `VectorAviary(randomize=...)`), or the planner's own belief about the airframes (`plant=`, `set_plant`), which is
+where an identified airframe (examples/sysid.py) goes.  Downwash is in neither model (it needs mates), and `SwarmMPPI` plans on the
+nominal model only.
 """
 import ctypes
 import dataclasses
@@ -19,6 +23,9 @@ import torch
 from . import _native
 from . import neighbors as _nb
 from . import obstacles as _ob
+from .utils.enums import PHYS_DW
+
+MODELS = ("nominal", "aviary")
 
 ACT_RPM, ACT_VEL = 0, 2
 ACT_RAW_RPM, ACT_DIRECT_RPM = 5, 6        # what `CTBRMPPI`'s core flies (the rate loop's output is RPMs)
@@ -46,9 +53,21 @@ class _Planner:
     `advance` / `reset`.  A subclass checks its core, then calls `_bind` with its default bounds; it names its entry (`_ENTRY`), the
     arguments in front of `GpdState` (`_lead`) and its hover action (`_hover`)."""
     _ENTRY = None
+    model = "nominal"
+    #: the planner's own belief about the airframes (`plant=` / `set_plant`): [9, ld] scales and the [19, ld] derived rows; None: the
+    #: core's table, whatever it is at each launch
+    plant_scales = None
+    plant_rows = None
 
-    def _bind(self, core, horizon, samples, sigma, lam, cost, seed, field, lo, hi, act_lo, act_hi):
+    def _bind(self, core, horizon, samples, sigma, lam, cost, seed, field, lo, hi, act_lo, act_hi, model="nominal", plant=None):
         self.core, self.device, self.N = core, core.device, core.N
+        if model not in MODELS:
+            raise ValueError(f"model must be one of {MODELS}")
+        if plant is not None and model != "aviary":
+            raise ValueError('plant= is the belief of model="aviary"; the nominal model flies the nominal airframe')
+        if model == "aviary" and ((core.physics_flags & PHYS_DW) or core._state.dw_force):
+            raise ValueError('model="aviary" has no downwash (it needs mates): the core has GPD_PHYS_DW or computes it outside the kernel')
+        self.model = model
         self.H, self.M = int(horizon), int(samples)
         if self.H < 1 or self.M % 64 != 0 or not 64 <= self.M <= 1024:
             raise ValueError("horizon must be >= 1 and samples a multiple of 64 in 64..1024")
@@ -68,7 +87,8 @@ class _Planner:
                                   seed=(ctypes.c_uint32 * 2)(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF), iteration=0)
         # the model's configuration: the core's rates and action type, nothing else of it
         c = core._cfg
-        self._cfg = _native.GpdStepCfg(num_envs=core.E, drones_per_env=1, act_type=core.act_code, substeps=core.S, physics_flags=0,
+        self._cfg = _native.GpdStepCfg(num_envs=core.E, drones_per_env=1, act_type=core.act_code, substeps=core.S,
+                                       physics_flags=core.physics_flags if model == "aviary" else 0,
                                        pyb_dt=c.pyb_dt, ctrl_dt=c.ctrl_dt, inv_ctrl_dt=c.inv_ctrl_dt, lanes_per_wave=c.lanes_per_wave,
                                        task=0, auto_reset=0)
         if isinstance(field, _ob.ObstacleField):
@@ -80,7 +100,45 @@ class _Planner:
         self._goal = torch.zeros((self.N, 4), **f32)
         self.costs, self.stats = torch.zeros((self.N, self.M), **f32), torch.zeros((self.N, 4), **f32)
         self.iteration = 0
+        if plant is not None:
+            self.set_plant(plant)
         self.reset()
+
+    # (what `SimCore._plant_input` reads of its core: the belief is parsed and completed exactly as the core's own table is)
+    E = property(lambda self: self.N)
+    D = 1
+
+    def plant_view(self) -> torch.Tensor:
+        """[9, N, 1] VIEW of the belief's scale table (None without one)."""
+        return None if self.plant_scales is None else self.plant_scales[:, :self.N].view(-1, self.N, 1)
+
+    def set_plant(self, scales, mask=None):
+        """Set the planner's OWN BELIEF about the airframes (`model="aviary"` only): anything `SimCore.set_plant` accepts -- a tensor
+        `[9, N]` / `[9, N, 1]` of scale factors or a dict {field: tensor / scalar}, fields left out keeping the belief's current values
+        (1.0 on first use); `mask` (bool/uint8 [N]): only those drones change.  The rows are derived through `gpd_plant_derive`, used
+        in place of the core's table from the next launch on, and never written to the core.  One host sync (the validation)."""
+        if self.model != "aviary":
+            raise ValueError('set_plant: the belief belongs to model="aviary"')
+        c = self.core
+        full = type(c)._plant_input(self, scales)
+        if bool((~(torch.isfinite(full) & (full > 0))).any()):
+            raise ValueError("set_plant: every scale must be finite and > 0")
+        first = self.plant_scales is None
+        if first:
+            self.plant_scales = torch.ones((len(_native.SCALE_FIELDS), c.ld), dtype=torch.float32, device=self.device)
+            self.plant_rows = torch.empty((_native.PLANT_ROWS, c.ld), dtype=torch.float32, device=self.device)
+        view = self.plant_view()
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+            torch.where(mask.view(1, self.N, 1).bool(), full, view, out=view)
+        else:
+            view.copy_(full)
+        _native.call("gpd_plant_derive", self.device, c._stream(), c._params, self.plant_scales, None if first else mask, self.N, 1, c.ld,
+                     self.plant_rows)
+
+    def _ctbr(self):
+        """the model's `GpdCtbr` (None: RPM / VEL actions), as `gpd_mppi_plant` takes it"""
+        return None
 
     @property
     def nominal(self) -> torch.Tensor:
@@ -109,8 +167,13 @@ class _Planner:
         self._q.iteration = self.iteration & 0xFFFFFFFF
         obst, n_obst, ld = self._obst
         c = self.core
-        _native.call(self._ENTRY, self.device, c._stream(), *self._lead(), c._state, self._cfg, self._q, self._u[0], self.N * 4, goal, goal_stride,
-                     obst, n_obst, ld, self._u[1], self.costs, self.stats)
+        if self.model == "aviary":         # the belief, else the core's table AS IT IS NOW (None: the nominal airframe)
+            rows = self.plant_rows if self.plant_rows is not None else c.plant_rows
+            _native.call("gpd_mppi_plant", self.device, c._stream(), c._params, self._ctbr(), c._state, self._cfg, self._q, rows, self._u[0],
+                         self.N * 4, goal, goal_stride, obst, n_obst, ld, self._u[1], self.costs, self.stats)
+        else:
+            _native.call(self._ENTRY, self.device, c._stream(), *self._lead(), c._state, self._cfg, self._q, self._u[0], self.N * 4, goal,
+                         goal_stride, obst, n_obst, ld, self._u[1], self.costs, self.stats)
         self._u.reverse()
         self.iteration += 1
 
@@ -142,16 +205,18 @@ class _Planner:
 class MPPI(_Planner):
     """A planner bound to a `SimCore` of single drones with RPM or VEL actions: the nominal sequence `[H, N, 4]`, the samples' `costs`
     `[N, M]` and `stats` `[N, 4]` (min cost, weighted mean cost, effective sample size, finite samples) are tensors allocated once;
-    every launch goes to the core's stream.  `field`: an `obstacles.ObstacleField` (or the `FieldQuery` an aviary built from one)."""
+    every launch goes to the core's stream.  `field`: an `obstacles.ObstacleField` (or the `FieldQuery` an aviary built from one).
+    `model`: "nominal" (`gpd_mppi`: the nominal airframe, no physics flags) or "aviary" (`gpd_mppi_plant`: the core's physics flags and
+    its plant table at each launch, or the belief `plant` -- anything `SimCore.set_plant` accepts; `set_plant` updates it)."""
     _ENTRY = "gpd_mppi"
 
     def __init__(self, core, horizon: int, samples: int, sigma, lam: float, cost: MPPICost = None, seed: int = 0, field=None,
-                 act_lo=None, act_hi=None):
+                 act_lo=None, act_hi=None, model: str = "nominal", plant=None):
         if core.D != 1:
             raise ValueError("MPPI plans for aviaries of one drone (drones_per_env must be 1)")
         if core.act_code not in DEFAULT_BOUNDS:
             raise ValueError("MPPI plans over RPM or VEL actions (ActionType.RPM / ActionType.VEL)")
-        self._bind(core, horizon, samples, sigma, lam, cost, seed, field, *DEFAULT_BOUNDS[core.act_code], act_lo, act_hi)
+        self._bind(core, horizon, samples, sigma, lam, cost, seed, field, *DEFAULT_BOUNDS[core.act_code], act_lo, act_hi, model, plant)
 
     def _hover(self) -> tuple:
         return (0.0, 0.0, 0.0, 0.0) if self.core.act_code == ACT_RPM else (1.0, 0.0, 0.0, 0.0)
@@ -164,11 +229,12 @@ class CTBRMPPI(_Planner):
     DIRECT_RPM actions (`VectorCtrlAviary`), what `rollout_ctbr` requires; `ctrl`: a `control.VectorCTBR` of `core.N` controllers on
     the core's device.  The default bounds are the controller's clips, `(0, -rate_max x 3) .. (thrust_max, +rate_max x 3)`; wider ones
     are legal, the rate loop clips.  The default nominal is the hover command `(g, 0, 0, 0)` with the controller's `g`.  `plan()`
-    returns `[N, 4]` commands for `rollout_ctbr(ctrl, cmd, 1, mode="cmd")`."""
+    returns `[N, 4]` commands for `rollout_ctbr(ctrl, cmd, 1, mode="cmd")`.  `model`, `plant`: as for `MPPI` ("aviary": the model is
+    `rollout_ctbr`'s on the core's physics flags and plant table; the rate loop stays on the nominal M and J)."""
     _ENTRY = "gpd_mppi_ctbr"
 
     def __init__(self, core, ctrl, horizon: int, samples: int, sigma, lam: float, cost: MPPICost = None, seed: int = 0, field=None,
-                 act_lo=None, act_hi=None):
+                 act_lo=None, act_hi=None, model: str = "nominal", plant=None):
         if core.D != 1:
             raise ValueError("CTBRMPPI plans for aviaries of one drone (drones_per_env must be 1)")
         if core.act_code not in (ACT_RAW_RPM, ACT_DIRECT_RPM):
@@ -177,10 +243,13 @@ class CTBRMPPI(_Planner):
             raise ValueError(f"CTBRMPPI needs a VectorCTBR of {core.N} controllers on {core.device}")
         self.ctrl = ctrl
         r = ctrl.rate_max
-        self._bind(core, horizon, samples, sigma, lam, cost, seed, field, (0.0, -r, -r, -r), (ctrl.thrust_max, r, r, r), act_lo, act_hi)
+        self._bind(core, horizon, samples, sigma, lam, cost, seed, field, (0.0, -r, -r, -r), (ctrl.thrust_max, r, r, r), act_lo, act_hi, model, plant)
 
     def _lead(self) -> tuple:
         return (self.core._params, self.ctrl.struct())
+
+    def _ctbr(self):
+        return self.ctrl.struct()
 
     def _hover(self) -> tuple:
         return (float(self.ctrl.struct().g), 0.0, 0.0, 0.0)

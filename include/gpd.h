@@ -810,6 +810,33 @@ int gpd_mppi_peers(const GpdParams* params, const struct GpdCtbr* ctbr /* NULL: 
                    float* u_out, float* costs, float* stats4, void* stream);
 
 /*
+ * MPPI on the AVIARY'S OWN MODEL: gpd_mppi (ctbr NULL: its model and action types) or gpd_mppi_ctbr (ctbr given: its model and action
+ * types) word for word -- noise, clamp, cost terms, softmax over the finite costs, u_out, costs, stats4, strides, obstacle lists, struct
+ * GpdMppi, a state that is only read -- except the model step, which flies every drone's own airframe under the force terms of
+ * cfg.physics_flags, as gpd_rollout_plant / gpd_rollout_ctbr fly it.
+ *   plant_rows   NULL (the nominal airframe), or the per-drone plant table of gpd_plant_derive ([GPD_PLANT_ROWS][state.ld], 16-byte
+ *         aligned): drone n's model is column n.  One wave plans one drone, so its row is read once, at wave-uniform addresses.  The
+ *         controller (DSLPID's model and gains, the rate loop's M and J), the action mapping (HOVER_RPM, the MAX_RPM clip), the
+ *         geometry, gnd_eff_h_clip and ground_z stay nominal, exactly as the plant path defines it (GPD_PLANT_*, above).
+ *   cfg.physics_flags   any of GPD_PHYS_GND, GPD_PHYS_DRAG, GPD_PHYS_GROUND, GPD_PHYS_DAMP.
+ *   step  ctbr NULL: one env step as gpd_step takes it for one drone -- the action mapped on the plant, then `substeps` sub-steps; the drag
+ *         term sees the previous step's RPMs on the first sub-step and this step's after it, and the last RPMs are carried from step to
+ *         step of a sample.  ctbr given: one control step as gpd_rollout_ctbr takes it in GPD_CTBR_CMD -- the rate loop on the nominal M
+ *         and J, the rotor thrusts and the sub-step on the plant, the drag term on the RPMs applied one sub-step earlier.
+ *         A sample's first "previous RPMs" are state.last_rpm, required with GPD_PHYS_DRAG as everywhere else.
+ * With plant_rows NULL and no flag the call equals the model's own entry bit for bit; so does a table of all-ones scales.
+ * Refused before any device work, every message starting "gpd_mppi_plant: ".  Everything the model's own entry refuses, with the same
+ * code (a physics flag other than GPD_PHYS_DW is legal here); GPD_ENOTSUP: GPD_PHYS_DW or state.dw_force (downwash needs mates);
+ * GPD_EINVAL: GPD_PHYS_DRAG without state.last_rpm, plant_rows not 16-byte aligned.  Asynchronous on `stream`, no allocation, one launch,
+ * no atomics; two calls with the same arguments give the same bits.  DESIGN.md section 3.21.
+ */
+int gpd_mppi_plant(const GpdParams* params, const struct GpdCtbr* ctbr /* NULL: gpd_mppi's model and action types; else gpd_mppi_ctbr's */,
+                   const GpdState* state, const GpdStepCfg* cfg, const GpdMppi* mppi,
+                   const float* plant_rows /* [GPD_PLANT_ROWS][state->ld] as gpd_rollout_plant reads them; NULL: the nominal airframe */,
+                   const float* u_in, int64_t u_step_stride, const float* goal, int64_t goal_step_stride, const float* obst, int32_t n_obst,
+                   int64_t obst_ld, float* u_out, float* costs, float* stats4, void* stream);
+
+/*
  * Masked reset. Replaces BaseAviary.reset/_housekeeping (envs/BaseAviary.py:220-255, 451-477)
  * for the envs whose mask byte is non-zero (mask == NULL: all).  Sets pos/quat to init_pose,
  * vel, rpy_rates, last_rpm and step_counter to zero and writes the initial obs12 rows.  As in
