@@ -24,9 +24,11 @@ SHAPES = [(8, 7, "rpm", 1), (8, 7, "pid", 1), (2, 4, "rpm", 1), (2, 4, "vel", 1)
           (8, 15, "rpm", 1), (2, 12, "vel", 1), (1, 15, "one_d_rpm", 1), (3, 31, "pid", 1), (1, 8, "rpm", 1), (1, 8, "one_d_rpm", 8), (1, 24, "pid", 5),
           (2, 8, "rpm", 8), (2, 24, "one_d_pid", 1),
           # the add-on sets under the sub-step loop
-          (1, 15, "rpm", 8), (1, 7, "pid", 5), (2, 12, "rpm", 8), (8, 7, "one_d_rpm", 4), (4, 23, "vel", 8)]
+          (1, 15, "rpm", 8), (1, 7, "pid", 5), (2, 12, "rpm", 8), (8, 7, "one_d_rpm", 4), (4, 23, "vel", 8),
+          # the any-size <flags 7> variants at larger aviaries: groups of four mates in full waves (16, 64), 31 pad lanes per wave (33)
+          (16, 7, "rpm", 1), (33, 7, "rpm", 8), (64, 15, "pid", 1)]
 for D, phys, act, S in SHAPES:
-    E = 777 if D == 1 else 300
+    E = 777 if D == 1 else {16: 17, 33: 9, 64: 5}.get(D, 300)          # (the larger aviaries: two workgroups, the last one ragged)
     rng = np.random.default_rng(100 * D + phys)
     xyz = np.zeros((E, D, 3))
     xyz[..., :2] = rng.uniform(-0.3, 0.3, size=(E, D, 2))

@@ -7,15 +7,20 @@ All tests here need a real MI355X (`-m gpu`).  Tolerances (fp32 kernel vs fp64 o
         err_g(t) = ||x32_g - x64_g||_inf / max(||x64_g||_inf over batch and time, floor_g)
     with floors 1 m, 1, 1 m/s, 1 rad/s, 1 rad; bound 1e-4 after 1920 physics steps.
 """
+import os
+import sys
 import zlib
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import golden, urdf
+from conftest import REPO, golden, urdf
 from oracle.aviary_oracle import ACT_DIM
 from oracle.batched_oracle import BatchedAviary
+
+sys.path.insert(0, os.path.join(REPO, "tests", "helpers"))
+from aviary_sizes import tall_column  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -647,11 +652,7 @@ def test_largest_aviaries_one_workgroup_per_aviary(gpu_device, D, flags):
     others, the MultiHover reductions run over the whole workgroup; D = 200 / 129 leave idle lanes in it."""
     rng = np.random.default_rng(D)
     E, S = 3, 2
-    # a tall, slightly tilted column: 0.3 m vertical spacing (away from the dz -> 0+ and dz = 0.6875 m singularities
-    # of the downwash model for the nearest neighbours), lateral jitter
-    xyz = rng.uniform(-0.02, 0.02, size=(E, D, 3)) + np.arange(D)[None, :, None] * np.array([0.013, 0.007, 0.3]) + \
-        np.array([0, 0, 0.5])
-    rpy = rng.uniform(-0.05, 0.05, size=(E, D, 3))
+    xyz, rpy = tall_column(rng, E, D)      # (0.3 m vertical spacing, lateral jitter: tests/helpers/aviary_sizes.py)
     b = BatchedAviary(urdf("cf2x"), "cf2x", num_envs=E, num_drones=D, initial_xyzs=xyz, initial_rpys=rpy,
                       physics_flags=flags, pyb_freq=240, ctrl_freq=240 // S, act="rpm", task="multihover",
                       pid_urdf_path=urdf("cf2x"))

@@ -139,17 +139,22 @@ def test_derive_reproduces_the_nominal_struct_and_the_float64_reference(gpu_devi
 # gpd_rollout_kernel (terminal observations, D > 64; single and multi)
 NOMINAL_SHAPES = [("rpm", 0, 1, 1, 20, False), ("rpm", 0, 1, 1, 1, False), ("pid", 7, 2, 8, 20, False), ("vel", 8, 3, 1, 1, True),
                   ("one_d_rpm", 24, 8, 8, 20, True), ("one_d_pid", 31, 100, 1, 20, False), ("raw_rpm", 31, 1, 8, 20, True),
-                  ("direct_rpm", 7, 100, 1, 1, False), ("one_d_pid", 24, 1, 8, 1, False), ("vel", 0, 2, 1, 20, False)]
+                  ("direct_rpm", 7, 100, 1, 1, False), ("one_d_pid", 24, 1, 8, 1, False), ("vel", 0, 2, 1, 20, False),
+                  # the lane maps of larger aviaries: 33 drones (31 pad lanes per wave in gpd_rollout1_kernel, 231-lane workgroups in
+                  # gpd_step_kernel) and 64 (full waves, groups of four mates), two workgroups with a ragged last one
+                  ("rpm", 7, 33, 1, 20, False), ("pid", 7, 33, 2, 1, False), ("one_d_rpm", 31, 64, 1, 20, False), ("rpm", 7, 64, 8, 1, False)]
 
 
 @pytest.mark.parametrize("act,flags,D,S,K,keep", NOMINAL_SHAPES)
 def test_all_ones_table_is_the_uniform_path_bit_for_bit(gpu_device, act, flags, D, S, K, keep):
-    E = {1: 300, 2: 150, 3: 150, 8: 40, 100: 6}[D]
+    E = {1: 300, 2: 150, 3: 150, 8: 40, 100: 6, 33: 9, 64: 5}[D]
     calls = 3 if K > 1 else (45 if S == 1 else 8)            # (episodes of 36 physics steps: every horizon spans auto-resets)
     a = _core(gpu_device, act, flags, D, S, E, keep_term=keep)
     b = _core(gpu_device, act, flags, D, S, E, keep_term=keep)
     b.set_plant(torch.ones((NF, E), device=gpu_device))
     assert b.plant_rows is not None and a.plant_rows is None
+    if D in (33, 64):          # (z_bound above the stack: these aviaries end by time, not at every step)
+        a._cfg.z_bound = b._cfg.z_bound = 0.4 + 0.3 * D + 1.0
     oa, sa = _drive(a, act, K, calls)
     ob, sb = _drive(b, act, K, calls)
     assert len(oa) == len(ob)

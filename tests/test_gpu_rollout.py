@@ -1,14 +1,19 @@
 """`gpd_rollout` (K env steps per launch, state in registers) against K calls of `gpd_step` -- bitwise --
 and against the float64 oracle stepped K times."""
+import os
+import sys
 import zlib
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import urdf
+from conftest import REPO, urdf
 from oracle.batched_oracle import BatchedAviary
 from test_gpu_parity import _actions, _core, _oracle_kin, _random_scene, _sync_from_oracle
+
+sys.path.insert(0, os.path.join(REPO, "tests", "helpers"))
+from aviary_sizes import rollout_equals_steps  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -41,6 +46,11 @@ RAGGED = [  # act, flags, D, S, model, E, K: ragged last workgroups, whole-aviar
     # more workgroups than the chip holds at once (256 CUs x 8) AND a ragged tail: the clone lanes of the last workgroup
     # start long after workgroup 0 has finished and rewritten its state (round-1 advisor finding)
     ("rpm", 0, 1, 1, "cf2x", 1200001, 6), ("rpm", 4, 2, 1, "cf2x", 600001, 5),
+    # K >= 48 at up to 2^17 plain RPM drones, one sub-step: the ordinary-store instantiation of gpd_rollout1_kernel (`plain_obs`, what a
+    # default 64-step launch runs) -- a ragged batch (clone lanes), five drones, one drone, K = 0, 1, 2 mod 3 of the three-step loop --
+    # and K = 47, the last one on the non-temporal side
+    ("rpm", 0, 1, 1, "cf2x", 1000, 48), ("rpm", 0, 1, 1, "cf2x", 5, 49), ("rpm", 0, 1, 1, "cf2x", 1, 50), ("rpm", 0, 1, 1, "cf2x", 300, 64),
+    ("rpm", 0, 1, 1, "cf2x", 1000, 47),
 ]
 
 
@@ -63,32 +73,8 @@ def test_rollout_is_bitwise_k_steps(gpu_device, act, flags, D, S, model, E, K, k
     kin[7:13] = torch.as_tensor(rng.uniform(-0.5, 0.5, size=(6, a.ld)), dtype=torch.float32, device=gpu_device)
     a.set_state(kin=kin[:, :a.N]); b.set_state(kin=kin[:, :b.N])
     acts = torch.as_tensor(_actions(rng, act, (K, E, D), a.P.HOVER_RPM).astype(np.float32), device=gpu_device)
-    obs_s, rew_s, te_s, tr_s, tobs_s = [], [], [], [], []
-    for k in range(K):
-        o, r, te, tr = a.step(acts[k])
-        obs_s.append(o.clone()); rew_s.append(r.clone()); te_s.append(te.clone()); tr_s.append(tr.clone())
-        if keep_term:
-            tobs_s.append(a.term_obs12.clone())
-    obs, rew, te, tr = b.rollout(acts)
-    assert act == "raw_rpm" or K * S <= 10 or torch.stack(tr_s).any(), "test must exercise the auto-reset"
-    assert torch.equal(torch.stack(obs_s), obs)
-    assert torch.equal(torch.stack(rew_s), rew)
-    assert torch.equal(torch.stack(te_s), te) and torch.equal(torch.stack(tr_s), tr)
-    for name in ("kin", "last_rpm", "pid", "step_counter", "obs12", "reward", "terminated", "truncated"):
-        x, y = getattr(a, name), getattr(b, name)
-        if x is not None:
-            assert torch.equal(x, y), name
-    if not keep_term:
-        return
-    # terminal observations: rollout row t holds the rows written at step t; the single-step buffer accumulates
-    tob = b._rollout_buf[4]
-    done = (torch.stack(te_s) | torch.stack(tr_s))                                     # [K, E]
-    for k in range(K):
-        m = done[k].repeat_interleave(D)
-        assert torch.equal(tob[k][m], tobs_s[k][m])
-    # ... and the persistent term_obs12 afterwards is what the K single steps left (the plain rollout did not update it)
-    if a.auto_reset:
-        assert torch.equal(a.term_obs12, b.term_obs12)
+    te_s, tr_s = rollout_equals_steps(a, b, acts, keep_term)
+    assert act == "raw_rpm" or K * S <= 10 or tr_s.any(), "test must exercise the auto-reset"
 
 
 def _scramble_arguments(rng, *cores):
@@ -202,22 +188,26 @@ def test_full_observation_rows_step_vs_rollout(gpu_device, act, D, ctrl):
 @pytest.mark.parametrize("act,D,ctrl,E,K,fused", [("rpm", 1, 240, 1000, 7, True), ("rpm", 1, 30, 333, 40, True), ("pid", 1, 48, 300, 30, True),
                                                   ("one_d_rpm", 2, 30, 257, 20, True), ("vel", 4, 240, 130, 9, True), ("rpm", 3, 48, 100, 12, True),
                                                   ("pid", 7, 48, 41, 12, True), ("rpm", 70, 48, 5, 12, False)])
-def test_rollout_with_lazy_history_pushes_the_ring_inside_the_kernel(gpu_device, act, D, ctrl, E, K, fused):
+def test_rollout_with_lazy_history_pushes_the_ring_inside_the_kernel(gpu_device, act, D, ctrl, E, K, fused, scene=None):
     """`gpd_rollout_history` (VectorAviary(full_obs="lazy").rollout): every step's action goes into the action ring inside the
     rollout kernel.  Same observations, same ring (the zero-copy history view, the ring positions), same continuation as K
     single steps -- for rollouts shorter and longer than the history, ragged batches, aviaries of 2, 3, 4 and 7 drones (whole
     aviaries per wave: 63 of a wave's lanes hold a drone for 3 and 7); an aviary of 70 drones has no fused variant and takes the
-    post-pass (`pushed_history` False), with the same result."""
+    post-pass (`pushed_history` False), with the same result.
+    `scene` (tests/test_gpu_aviary_sizes.py): constructor arguments on top of these, and the z_bound of the two cores."""
     from gym_pybullet_drones_amd.envs import VectorAviary
     from gym_pybullet_drones_amd.utils.enums import ActionType
     rng = np.random.default_rng(K)
+    kw, z_bound = scene or ({}, None)
     mk = lambda: VectorAviary(E, D, act=ActionType(act), ctrl_freq=ctrl, task="hover" if D == 1 else "multihover",  # noqa: E731
-                              full_obs="lazy", auto_reset=True, episode_len_sec=0.1, device=gpu_device)
+                              full_obs="lazy", auto_reset=True, episode_len_sec=0.1, device=gpu_device, **kw)
     a, b = mk(), mk()
     A = a.ACT_DIM
     # (every float of the kernel arguments scaled by a factor of its own: the fused variants are instantiations of their own,
     # with their own register allocation -- see test_rollout_is_bitwise_with_every_argument_word_distinct)
     _scramble_arguments(np.random.default_rng(79), a.core, b.core)
+    if z_bound is not None:                  # (after the scaling: above the column whatever its factor)
+        a.core._cfg.z_bound = b.core._cfg.z_bound = z_bound
     acts = torch.as_tensor(rng.uniform(-1, 1, size=(2 * K + 3, E, D, A)).astype(np.float32), device=gpu_device)
     for k in range(3):                       # some history first
         a.step(acts[k]); b.step(acts[k])
@@ -234,6 +224,7 @@ def test_rollout_with_lazy_history_pushes_the_ring_inside_the_kernel(gpu_device,
         assert torch.equal(r, (r1 if k < K else r2)[k % K]) and torch.equal(te, (te1 if k < K else te2)[k % K]) and \
             torch.equal(tr, (tr1 if k < K else tr2)[k % K]), k
     assert torch.stack([f[2] for f in flags]).any() or 2 * K + 3 < 0.1 * ctrl or act in ("pid", "vel"), "the test should see episodes end"
+    assert scene is None or not torch.stack([f[2] for f in flags]).all(), "... and not at every step"
     assert torch.equal(a.history(), b.history()) and torch.equal(a.core.ring_pos, b.core.ring_pos)
     assert torch.equal(a.core.act_ring, b.core.act_ring)
     # the view after the first rollout ends with that rollout's last actions, oldest first
@@ -287,7 +278,7 @@ def test_rollout_arena_places_the_blocks_and_changes_no_bit(gpu_device):
 def test_kernels_compiled_for_one_aviary_size_and_flag_set_are_the_generic_kernels_bit_for_bit():
     """`gpd_rollout1_kernel` / `gpd_step_kernel` have variants with the aviary size, the physics flags and "one sub-step per step" as
     template parameters (BASELINE configs 3 (i), 3 (ii), 5 run 12 / 26 / 28 % faster with them).  Same operations,
-    same order: rollouts and single steps of twenty-seven shapes, and four rollouts that keep terminal observations (the third kernel's variants) -- every variant, and shapes that fall through to the generic kernels --
+    same order: rollouts and single steps of thirty shapes (aviaries of 16, 33 and 64 drones among them), and four rollouts that keep terminal observations (the third kernel's variants) -- every variant, and shapes that fall through to the generic kernels --
     digest identically with GPD_ROLLOUT_SIZED=0 (generic kernels only; the switch is read once per process, hence the two children)."""
     import json
     import os
@@ -302,4 +293,4 @@ def test_kernels_compiled_for_one_aviary_size_and_flag_set_are_the_generic_kerne
         line = next((l for l in res.stdout.splitlines() if l.startswith("{")), None)
         assert res.returncode == 0 and line, res.stderr[-1500:]
         got[label] = json.loads(line)
-    assert len(got["generic"]) == 31 and got["generic"] == got["sized"], {k: (v, got["sized"].get(k)) for k, v in got["generic"].items() if got["sized"].get(k) != v}
+    assert len(got["generic"]) == 34 and got["generic"] == got["sized"], {k: (v, got["sized"].get(k)) for k, v in got["generic"].items() if got["sized"].get(k) != v}

@@ -53,3 +53,18 @@ def test_host_side_of_the_c_abi_under_asan_and_ubsan():
     assert len(recorded) > 700
     assert [r[:3] for r in rows] == [r[:3] for r in recorded], [(a, b) for a, b in zip(rows, recorded) if a[:3] != b[:3]][:5]
     assert not [r for r in rows if int(r[2]) == 0 or not r[3].startswith(r[0] + ": ") or len(r[3]) <= len(r[0]) + 2][:5]
+
+
+def test_lanes_per_wave_is_refused_or_sizes_the_single_step_grid():
+    """`GpdStepCfg.lanes_per_wave` (tests/c/lanes_per_wave.c): 8, 48, -1 and four more values are refused with GPD_EINVAL and "<entry>:
+    lanes_per_wave must be 0, 16, 32 or 64" by the five entries that read it, nothing launched; 0 launches what 64 launches; 16 and 32
+    make the single-step grid (also of a one-step rollout) four and two times as large, and change neither a longer rollout's nor a
+    multi-drone aviary's."""
+    exe = host_lib.program("lanes_per_wave")
+    run = host_lib.run(exe)
+    print(run.stdout[-3000:])
+    assert "AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-4000:]
+    assert run.returncode == 0 and "\n0 checks failed" in run.stdout, run.stdout[-3000:] + run.stderr[-2000:]
+    assert run.stdout.count("\nok ") + run.stdout.startswith("ok ") == 5 * 11 + 4 * 3 + 4
+    for value in (8, 48, -1):
+        assert f"ok   gpd_step refuses lanes_per_wave = {value}\n" in run.stdout
