@@ -30,7 +30,7 @@ ABI_VERSION = 9
 #                     slots of a rollout step)
 #   policy.hip        gpd_rollout_policy                 the default scheduler: 10 % faster on its MFMA + activation mix (round-2 A/B)
 #   swarm.hip         the one-world kernels              max-ilp, as in rounds 2-4
-#   abi.hip           small kernels, RCCL, library-level entries; the differentiable rollout (RPM and DSLPID), gpd_obstacles, gpd_mppi and the
+#   abi.hip           small kernels, RCCL, library-level entries; the differentiable rollout (RPM and DSLPID), gpd_obstacles, gpd_rollout_obst, gpd_mppi and the
 #                     thrust-and-body-rate controller gpd_ctbr / gpd_rollout_ctbr with its planner gpd_mppi_ctbr, gpd_mppi_peers, gpd_mppi_plant and its differentiable
 #                     rollout (csrc/*.inc pulled in at its end)
 #   mrac.hip          gpd_mrac / gpd_mrac_reset / gpd_rollout_mrac: the adaptive controller and the rollout that carries it (max-ilp)
@@ -41,7 +41,7 @@ MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 HIPCC_FLAGS = COMMON_FLAGS + MAX_ILP + ["-shared"]        # (kept under this name for the ISA tests)
 UNITS = (("step_rollout.hip", MAX_ILP + KERNARG_PRELOAD), ("policy.hip", []), ("swarm.hip", MAX_ILP + KERNARG_PRELOAD), ("abi.hip", MAX_ILP), ("mrac.hip", MAX_ILP))
-HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc", "diff_pid_kernels.inc", "dslpid_vjp.inc", "obstacle_math.inc", "obstacles.inc", "mppi_math.inc", "mppi.inc", "ctbr_math.inc", "ctbr.inc", "mppi_ctbr.inc", "mppi_peers_math.inc", "mppi_peers.inc", "mppi_plant.inc", "ctbr_vjp.inc", "diff_ctbr_kernels.inc")
+HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc", "diff_pid_kernels.inc", "dslpid_vjp.inc", "obstacle_math.inc", "obstacles.inc", "obst_task_math.inc", "obst_task.inc", "mppi_math.inc", "mppi.inc", "ctbr_math.inc", "ctbr.inc", "mppi_ctbr.inc", "mppi_peers_math.inc", "mppi_peers.inc", "mppi_plant.inc", "ctbr_vjp.inc", "diff_ctbr_kernels.inc")
 
 
 class GpdError(RuntimeError):
@@ -117,6 +117,13 @@ class GpdCtbr(ctypes.Structure):
     _fields_ = [("k_p", ctypes.c_float * 3), ("k_d", ctypes.c_float * 3), ("k_rates", ctypes.c_float * 3), ("g", ctypes.c_float),
                 ("k_rate", ctypes.c_float * 3), ("thrust_max", ctypes.c_float), ("rate_max", ctypes.c_float), ("alloc", ctypes.c_float * 12),
                 ("f_max", ctypes.c_float), ("inv_kf", ctypes.c_float), ("pad_", ctypes.c_float * 3)]
+
+
+class GpdObstTask(ctypes.Structure):
+    """mirror of `struct GpdObstTask` (gpd_rollout_obst: contact, the proximity hinge and the range sensor of the obstacle task)"""
+    _fields_ = [("collision_radius", ctypes.c_float), ("hit_terminates", ctypes.c_int32), ("hit_reward", ctypes.c_float),
+                ("prox_margin", ctypes.c_float), ("prox_weight", ctypes.c_float), ("n_rays", ctypes.c_int32), ("ray_frame", ctypes.c_int32),
+                ("max_range", ctypes.c_float)]
 
 
 #: `mode` of gpd_rollout_ctbr (GPD_CTBR_CMD / GPD_CTBR_POS)
@@ -204,6 +211,10 @@ _SIGNATURES = {
                                      _P, _P, _P, _P]),
     "gpd_obstacles": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, _P, _P, _P,
                                      _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _P, _P, _P]),
+    "gpd_sizeof_obst_task": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int32)]),
+    "gpd_rollout_obst": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg), ctypes.POINTER(GpdObstTask),
+                                        ctypes.c_int32, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int32, ctypes.c_int64, _P, _P, ctypes.c_int64,
+                                        ctypes.c_int64, _P, _P, _P, _P, ctypes.c_int64, _P]),
     "gpd_mppi": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg), ctypes.POINTER(GpdMppi), _P,
                                 ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int32, ctypes.c_int64, _P, _P, _P, _P]),
     "gpd_mppi_ctbr": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdCtbr), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg),
@@ -312,6 +323,9 @@ def lib() -> ctypes.CDLL:
     ctbr_size = ctypes.c_int32(0)
     if L.gpd_sizeof_ctbr(ctypes.byref(ctbr_size)) != 0 or ctbr_size.value != ctypes.sizeof(GpdCtbr):
         raise GpdError(f"struct layout mismatch: GpdCtbr is {ctbr_size.value} bytes in the library, {ctypes.sizeof(GpdCtbr)} in the binding")
+    obst_size = ctypes.c_int32(0)
+    if L.gpd_sizeof_obst_task(ctypes.byref(obst_size)) != 0 or obst_size.value != ctypes.sizeof(GpdObstTask):
+        raise GpdError(f"struct layout mismatch: GpdObstTask is {obst_size.value} bytes in the library, {ctypes.sizeof(GpdObstTask)} in the binding")
     _lib = L
     return L
 

@@ -1,6 +1,7 @@
 // abi.hip -- the small kernels (masked reset, action-history rows, batched DSLPID, state vectors, clock probe), RCCL, and the library-level
 // entries of the C ABI (version, last error, struct sizes, debug status); at its end the differentiable rollout (diff_kernels.inc; through the
-// DSLPID loop: diff_pid_kernels.inc), the obstacle queries (obstacles.inc) and the sampling-based planner (mppi.inc)
+// DSLPID loop: diff_pid_kernels.inc), the obstacle queries (obstacles.inc; as a task inside the rollout: obst_task.inc) and the
+// sampling-based planner (mppi.inc)
 #include <chrono>
 #include "gpd_common.inc"
 
@@ -596,6 +597,9 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
 
 // obstacle fields: gpd_obstacles and its two kernels
 #include "obstacles.inc"
+
+// ... as a task: gpd_sizeof_obst_task / gpd_rollout_obst and its kernel (collisions and range scans inside the rollout)
+#include "obst_task.inc"
 
 // sampling-based MPC: gpd_mppi and its kernel
 #include "mppi.inc"

@@ -48,6 +48,27 @@ __device__ __forceinline__ bool finite3(float x, float y, float z) {
     return (fabsf(x) < GPD_OBST_INF) & (fabsf(y) < GPD_OBST_INF) & (fabsf(z) < GPD_OBST_INF);      // (false for NaN)
 }
 
+// a ray direction of the table turned into the world frame by the attitude q (GPD_RAY_BODY: |q| does not matter) or by its yaw alone
+// (GPD_RAY_LEVEL: the yaw of pybullet's Euler angles of the normalised quaternion); GPD_RAY_WORLD leaves it.  `frame` is wave-uniform.
+// Shared by obst_scan_kernel and the fused task kernel (obst_task.inc): one text, the same bits.
+__device__ __forceinline__ void obst_turn_ray(int frame, float qx, float qy, float qz, float qw, float& dx, float& dy, float& dz) {
+    if (frame == GPD_RAY_BODY) {
+        const Mat3 R = quat_to_mat(qx, qy, qz, qw);
+        const float bx = dx, by = dy, bz = dz;
+        dx = fmaf(R.r02, bz, fmaf(R.r01, by, R.r00 * bx));
+        dy = fmaf(R.r12, bz, fmaf(R.r11, by, R.r10 * bx));
+        dz = fmaf(R.r22, bz, fmaf(R.r21, by, R.r20 * bx));
+    } else if (frame == GPD_RAY_LEVEL) {
+        const float s = fast_rsq(fmaf(qx, qx, fmaf(qy, qy, fmaf(qz, qz, qw * qw))));
+        float roll, pitch, yaw, sy, cy;
+        quat_to_rpy(qx * s, qy * s, qz * s, qw * s, roll, pitch, yaw);
+        sy = sinf(yaw); cy = cosf(yaw);
+        const float bx = dx, by = dy;
+        dx = fmaf(cy, bx, -(sy * by));
+        dy = fmaf(sy, bx, cy * by);
+    }
+}
+
 template <bool SHARED>
 __global__ __launch_bounds__(kBlock) void obst_clear_kernel(const float4* __restrict__ pos4, int n, int D, const float* __restrict__ obst,
                                                             int n_obst, int64_t ld, float collision_radius, float4* __restrict__ clear4,
@@ -92,21 +113,7 @@ __global__ __launch_bounds__(kBlock) void obst_scan_kernel(const float4* __restr
     float dx = ray_dirs[3 * ray], dy = ray_dirs[3 * ray + 1], dz = ray_dirs[3 * ray + 2];
     if (frame != GPD_RAY_WORLD) {              // (wave-uniform)
         const float4 q = quat4[i];
-        if (frame == GPD_RAY_BODY) {
-            const Mat3 R = quat_to_mat(q.x, q.y, q.z, q.w);
-            const float bx = dx, by = dy, bz = dz;
-            dx = fmaf(R.r02, bz, fmaf(R.r01, by, R.r00 * bx));
-            dy = fmaf(R.r12, bz, fmaf(R.r11, by, R.r10 * bx));
-            dz = fmaf(R.r22, bz, fmaf(R.r21, by, R.r20 * bx));
-        } else {
-            const float s = fast_rsq(fmaf(q.x, q.x, fmaf(q.y, q.y, fmaf(q.z, q.z, q.w * q.w))));
-            float roll, pitch, yaw, sy, cy;
-            quat_to_rpy(q.x * s, q.y * s, q.z * s, q.w * s, roll, pitch, yaw);
-            sy = sinf(yaw); cy = cosf(yaw);
-            const float bx = dx, by = dy;
-            dx = fmaf(cy, bx, -(sy * by));
-            dy = fmaf(sy, bx, cy * by);
-        }
+        obst_turn_ray(frame, q.x, q.y, q.z, q.w, dx, dy, dz);
     }
     float best = max_range;
     int who = -1;

@@ -628,6 +628,48 @@ class SimCore:
             self.obs12.copy_(obs[K - 1])
         return (obs, cmd) if want_cmd else obs
 
+    #: output buffers of `rollout_obst`, per (steps kept, row pitch): allocated once
+    _obst_cache = None
+
+    def rollout_obst(self, task: "_native.GpdObstTask", obst: torch.Tensor, n_obst: int, obst_ld: int, ray_dirs, actions: torch.Tensor,
+                     num_steps: int = None, last_only: bool = False):
+        """K env steps of an obstacle course in ONE launch (`gpd_rollout_obst`): every step is `rollout()`'s step, then the clearance
+        of the pose it reached against the obstacle list (`obst`, `n_obst`, `obst_ld`: an `obstacles.ObstacleField.table()`), contact
+        scored and -- `task.hit_terminates` -- ending the episode, the same-step auto-reset on the combined flags, and the observation
+        row of the pose that is left behind: pos rpy vel ang_v | nx ny nz d | the `task.n_rays` ranges along `ray_dirs`.  `actions`,
+        `num_steps`: as in `rollout()`.
+
+        Returns `(rows [K, N, row_ld], reward [K, E], terminated [K, E], truncated [K, E], collided [K, E])`, row_ld = 16 + n_rays
+        rounded up to a multiple of 4 -- persistent buffers that the next call of the same shape overwrites; with `last_only` the
+        last step's values alone, `[1, ...]`.  Single-drone aviaries, RPM / VEL / PID actions, no downwash, no action history, no
+        non-finite guard, no plant table: GpdError otherwise.  The latest-step tensors of `step()` (`obs12`, `reward` ...) are not
+        touched."""
+        if self.plant_rows is not None:
+            raise _native.GpdError("rollout_obst: the obstacle task flies the nominal airframe only; a per-drone plant table is set")
+        if self.host_visible:
+            raise _native.GpdError("rollout_obst: a host-visible core steps one aviary at a time")
+        actions, K, a_stride = self._action_blocks(actions, num_steps)
+        row_ld = (16 + int(task.n_rays) + 3) // 4 * 4
+        kept = 1 if last_only else K
+        if self._obst_cache is None:
+            self._obst_cache = {}
+        buf = self._obst_cache.get((kept, row_ld))
+        if buf is None:
+            dev = self.device
+            buf = (torch.zeros((kept, self.N, row_ld), dtype=torch.float32, device=dev), torch.zeros((kept, self.E), dtype=torch.float32, device=dev),
+                   torch.zeros((kept, self.E), dtype=torch.bool, device=dev), torch.zeros((kept, self.E), dtype=torch.bool, device=dev),
+                   torch.zeros((kept, self.E), dtype=torch.bool, device=dev))
+            while len(self._obst_cache) >= 4:
+                self._obst_cache.pop(next(iter(self._obst_cache)))
+            self._obst_cache[(kept, row_ld)] = buf
+        rows, rew, term, trunc, coll = buf
+        r_stride, e_stride = (0, 0) if last_only else (self.N * row_ld, self.E)
+        a = self._step_args or self._fixed_args()
+        self.state_version += 1
+        _native.call("gpd_rollout_obst", self.device, self._stream(), a[0], a[1], a[2], task, K, actions, a_stride, a[3], a[4], obst,
+                     int(n_obst), int(obst_ld), ray_dirs, rows, row_ld, r_stride, rew, term, trunc, coll, e_stride)
+        return buf
+
     def _latest_terminal(self, tobs, term, trunc, K):
         """`term_obs12` after a K-step launch = what K single steps would have left: for every aviary the terminal observation
         of the LAST step it ended in (aviaries that did not end keep what they held).  A few small torch kernels, off the

@@ -437,6 +437,141 @@ class VectorVelocityAviary(VectorAviary):
                          act=ActionType.VEL, task="none", **kw)
 
 
+class VectorObstacleAviary(VectorAviary):
+    """E single-drone aviaries flying an obstacle course AS A TASK: contact with the `field` is scored and (by default) ends the episode,
+    a proximity hinge shapes the reward, and the observation row carries the nearest obstacle and a range-sensor fan --
+    `(E, 1, 16 + R)`: pos rpy vel ang_v | nx ny nz d | range_0 .. range_{R-1}.  One launch per `step()` and one per K-step
+    `rollout()` (`gpd_rollout_obst`): the collision test, the reset it triggers and the scan of the pose that is observed all happen
+    inside the step kernel.  The reference gestures at this with `BaseRLAviary._addObstacles` and never scores it.
+
+    `field`: an `obstacles.ObstacleField`, shared or one list per aviary.  `rays`: `[R, 3]` unit directions (`obstacles.fan(16, ...)`) or
+    None; `max_range`, `frame` ("body", "level", "world") as in `range_scan()`.  reward = the task's reward + `hit_reward` in the step
+    that ends in contact - `prox_weight` * max(0, `prox_margin` - gap), gap the distance left before contact; `collision_radius`: the
+    drone as a sphere (default: the airframe's COLLISION_R).  There is no collision response: with `hit_terminates=False` a drone flies
+    on through the obstacle.  Terminal observations and the action history are not kept.  What `step()` and `rollout()` return are views of
+    buffers that the next call overwrites."""
+
+    def __init__(self, num_envs: int, field: "_ob.ObstacleField", rays=None, max_range: float = 5.0, frame: str = "body",
+                 hit_terminates: bool = True, hit_reward: float = -1.0, prox_margin: float = 0.0, prox_weight: float = 0.0,
+                 collision_radius: float = None, act=ActionType.VEL, task: str = "hover", target_pos=None, num_drones: int = 1,
+                 drone_model: DroneModel = DroneModel.CF2X, initial_xyzs=None, initial_rpys=None, physics: Physics = Physics.DYN,
+                 pyb_freq: int = 240, ctrl_freq: int = 48, episode_len_sec: float = 8, auto_reset: bool = True, full_obs: bool = False,
+                 keep_terminal_obs: bool = False, track_rpm: bool = False, pyb_like: bool = None, nan_guard: bool = False,
+                 randomize: dict = None, device=None):
+        self._refuse(num_drones, act, task, physics, pyb_like, full_obs, keep_terminal_obs, nan_guard, randomize)
+        rays = self.check_rays(rays)
+        n_rays = 0 if rays is None else len(rays)
+        if field.num_envs is not None and field.num_envs != int(num_envs):
+            raise ValueError(f"the field has a list for each of {field.num_envs} aviaries; the simulation has {int(num_envs)}")
+        r = DroneParams(drone_model).COLLISION_R if collision_radius is None else collision_radius
+        self._task = self.task_struct(r, hit_terminates, hit_reward, prox_margin, prox_weight, n_rays, frame, max_range)    # (before any device work)
+        super().__init__(num_envs=num_envs, num_drones=1, drone_model=drone_model, initial_xyzs=initial_xyzs, initial_rpys=initial_rpys,
+                         physics=physics, pyb_freq=pyb_freq, ctrl_freq=ctrl_freq, act=act, task=task, target_pos=target_pos,
+                         episode_len_sec=episode_len_sec, auto_reset=auto_reset, track_rpm=track_rpm, pyb_like=pyb_like, device=device)
+        self.N_RAYS, self.MAX_RANGE, self.FRAME = n_rays, float(max_range), frame
+        self.OBS_DIM = 16 + n_rays
+        self.ROW_LD = (self.OBS_DIM + 3) // 4 * 4
+        self._rays = None if rays is None else torch.as_tensor(rays).to(self.device).contiguous()
+        self._obstacles = _ob.FieldQuery(field, self.device, self.NUM_ENVS, 1, r)        # (also what clearance() / range_scan() answer about)
+        self._row = torch.zeros((self.NUM_ENVS, self.ROW_LD), dtype=torch.float32, device=self.device)
+        self._latest = self._row
+        self.collided = torch.zeros(self.NUM_ENVS, dtype=torch.bool, device=self.device)
+        self._fill_rows(None)
+
+    @staticmethod
+    def _refuse(num_drones, act, task, physics, pyb_like, full_obs, keep_terminal_obs, nan_guard, randomize):
+        """what the obstacle task does not serve (include/gpd.h gpd_rollout_obst), before any device work"""
+        if int(num_drones) != 1:
+            raise NotImplementedError("VectorObstacleAviary: num_drones > 1 (an obstacle course is flown by single drones)")
+        for name, value in (("randomize", randomize), ("full_obs", full_obs), ("keep_terminal_obs", keep_terminal_obs), ("nan_guard", nan_guard)):
+            if value:
+                raise NotImplementedError(f"VectorObstacleAviary: {name} is not served by the fused obstacle task")
+        if act not in (ActionType.RPM, ActionType.VEL, ActionType.PID):
+            raise NotImplementedError("VectorObstacleAviary: act must be ActionType.RPM, ActionType.VEL or ActionType.PID")
+        if task not in ("hover", "none"):
+            raise NotImplementedError("VectorObstacleAviary: task must be 'hover' or 'none'")
+        flags = physics.mask(pyb_like) if isinstance(physics, Physics) else int(physics)
+        if flags & 4:
+            raise NotImplementedError("VectorObstacleAviary: downwash needs mates, the course is flown alone")
+
+    @staticmethod
+    def check_rays(rays):
+        """`rays` as a contiguous float32 `[R, 3]` array, 1 <= R <= 64 (None stays None)"""
+        if rays is None:
+            return None
+        rays = np.ascontiguousarray(rays.cpu().numpy() if isinstance(rays, torch.Tensor) else rays, dtype=np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 3 or not 1 <= rays.shape[0] <= _ob.MAX_RAYS:
+            raise ValueError(f"rays must be [1..{_ob.MAX_RAYS}, 3] unit vectors or None, got {rays.shape}")
+        return rays
+
+    @staticmethod
+    def task_struct(collision_radius, hit_terminates, hit_reward, prox_margin, prox_weight, n_rays, frame, max_range) -> "_native.GpdObstTask":
+        """the `GpdObstTask` of the arguments; ValueError for what `gpd_rollout_obst` would refuse"""
+        code = _ob.FRAMES.get(frame)
+        if code is None:
+            raise ValueError(f"frame must be one of {', '.join(_ob.FRAMES)}, got {frame!r}")
+        vals = dict(collision_radius=float(collision_radius), hit_reward=float(hit_reward), prox_margin=float(prox_margin),
+                    prox_weight=float(prox_weight), max_range=float(max_range))
+        if not all(math.isfinite(v) for v in vals.values()):
+            raise ValueError(f"collision_radius, hit_reward, prox_margin, prox_weight and max_range must be finite, got {vals}")
+        if not vals["collision_radius"] > 0.0 or not vals["max_range"] > 0.0:
+            raise ValueError("collision_radius and max_range must be positive")
+        if vals["prox_margin"] < 0.0 or vals["prox_weight"] < 0.0:
+            raise ValueError("prox_margin and prox_weight must be non-negative")
+        return _native.GpdObstTask(hit_terminates=int(bool(hit_terminates)), n_rays=int(n_rays), ray_frame=code, **vals)
+
+    def _obs(self):
+        return self._latest.view(self.NUM_ENVS, 1, self.ROW_LD)[..., :self.OBS_DIM]
+
+    def _fill_rows(self, mask):
+        """the rows of the poses a reset left, from the existing entries (gpd_obstacles; reset is not hot)"""
+        c, q = self.core, self._obstacles
+        new = torch.zeros_like(self._row)
+        new[:, :12] = c.obs12
+        q.clearance(c.kin_P, c._stream())
+        new[:, 12:16] = q._clear4
+        if self.N_RAYS:
+            new[:, 16:self.OBS_DIM] = q.scan(c.kin_P, c.kin_Q, self._rays, self.MAX_RANGE, self.FRAME, False, c._stream())[0]
+        if mask is None:
+            self._row.copy_(new)
+        else:
+            keep = self._latest
+            torch.where(mask.to(device=self.device, dtype=torch.bool).unsqueeze(1), new, keep, out=self._row)
+        self._latest = self._row
+
+    def reset(self, seed=None, options=None, mask=None):
+        """Reset all aviaries (or those of the bool/uint8 `mask` [E]); the rows of the reset poses carry their clearance and ranges."""
+        self.core.reset(mask=mask)
+        self._fill_rows(mask)
+        return self._obs(), {}
+
+    def _launch(self, actions, num_steps, last_only):
+        q = self._obstacles
+        return self.core.rollout_obst(self._task, q.obst, q.n_obst, q.obst_ld, self._rays, actions, num_steps=num_steps, last_only=last_only)
+
+    def step(self, action: torch.Tensor):
+        """action (E, 1, A) -> (obs (E, 1, 16 + R), reward [E], terminated [E], truncated [E], {"collided": (E,) bool}): ONE launch.
+        Everything returned -- `info["collided"]` and `self.collided` included -- is a VIEW of the core's persistent output buffers:
+        the next `step()` overwrites it.  `clone()` what has to outlive the next call."""
+        rows, reward, terminated, truncated, collided = self._launch(action, 1, True)
+        self._latest = rows[0]
+        self.collided = collided[0]
+        return self._obs(), reward[0], terminated[0], truncated[0], {"collided": collided[0]}
+
+    def rollout(self, actions: torch.Tensor):
+        """actions (K, E, 1, A) -> (obs (K, E, 1, 16 + R), reward (K, E), terminated (K, E), truncated (K, E), {"collided": (K, E)}):
+        K steps in ONE launch, bit for bit K calls of `step()`.  Views of persistent buffers, as in `step()`: the next `rollout()` of
+        the same K overwrites them."""
+        K = actions.shape[0]
+        rows, reward, terminated, truncated, collided = self._launch(actions, None, False)
+        self._latest = rows[K - 1]
+        self.collided = collided[K - 1]
+        return rows.view(K, self.NUM_ENVS, 1, self.ROW_LD)[..., :self.OBS_DIM], reward, terminated, truncated, {"collided": collided}
+
+    def set_obstacles(self, field, collision_radius: float = None):
+        raise NotImplementedError("VectorObstacleAviary: the field is part of the task, given at construction")
+
+
 class VecEnvAdapter:
     """Stable-Baselines3 `VecEnv`-shaped front end of a `VectorAviary` (duck-typed: SB3 is not installed here).
 

@@ -694,6 +694,57 @@ int gpd_obstacles(const float* pos4, const float* quat4, int32_t n, int32_t dron
                   int32_t n_rays, int32_t ray_frame, float max_range, float* ranges, int32_t* ray_hit, void* stream);
 
 /*
+ * Obstacle courses as a task: gpd_rollout with the obstacle list inside the step.  num_steps = 1 is the env.step() of an
+ * obstacle-avoidance environment, num_steps = K its rollout; one launch either way.  The reference gestures at such a task with
+ * BaseRLAviary._addObstacles (envs/BaseRLAviary.py:99-128) and never scores it.  Per step and drone, in this order:
+ *   1. the env step exactly as gpd_rollout takes it (action mapping, `substeps` sub-steps, the rpy refresh, the task's reward and flags);
+ *   2. the clearance of the position the step reached, as gpd_obstacles computes it: d the minimum over the records of each one's
+ *      signed distance (ties to the lower record), n that record's gradient; (0, 0, 0, +inf) without a live record or a finite
+ *      position;  hit = d < collision_radius;
+ *   3. (csrc/obst_task_math.inc)  reward = task_reward + hit_reward * hit - prox_weight * max(0, prox_margin - (d - collision_radius)),
+ *      terminated |= hit_terminates & hit,  collided = hit;
+ *   4. with cfg.auto_reset, the same-step reset on terminated | truncated, as gpd_step does it (the pose and its rpy restored, the
+ *      rates, last_clipped_action and the step counter zeroed; the DSLPID members survive);
+ *   5. the observation row of the state the step LEAVES BEHIND -- of the reset pose where the aviary was reset, clearance included:
+ *      pos rpy vel ang_v | nx ny nz d | range_0 .. range_{n_rays - 1}  (16 + n_rays floats), each range the smallest entry of
+ *      gpd_obstacles' ray over the records, capped at max_range, the directions turned by ray_frame as gpd_obstacles turns them.
+ *
+ *   params, state, cfg, actions, action_step_stride, target_pos, init_pose   as gpd_rollout (a stride of 0 holds one block)
+ *   task            GpdObstTask: collision_radius > 0 (the drone as a sphere, as in gpd_obstacles), hit_terminates 0 / 1, hit_reward
+ *                   (finite), prox_margin and prox_weight (>= 0), n_rays 0 .. GPD_OBST_MAX_RAYS, ray_frame GPD_RAY_*, max_range > 0
+ *                   (the last two are read only when n_rays > 0); every float finite
+ *   obst, n_obst, obst_ld   the records of gpd_obstacles: obst_ld = 1 one shared list [n_obst][8], obst_ld >= num_envs field planes
+ *                   per aviary; 1 <= n_obst <= GPD_OBST_MAX
+ *   ray_dirs        [n_rays][3] unit vectors (NULL allowed with n_rays = 0)
+ *   rows            out, 16-byte aligned: row of drone n at step t at rows + t * row_step_stride + n * row_ld; row_ld a multiple of 4
+ *                   and >= 16 + n_rays, row_step_stride a multiple of 4 (floats past 16 + n_rays of a row are not written)
+ *   reward, terminated, truncated, collided   [num_envs] per step, env_step_stride elements apart
+ * The state, the step counters, last_rpm and the DSLPID members are written back once per launch.
+ * Supported: drones_per_env == 1; GPD_ACT_RPM, GPD_ACT_VEL, GPD_ACT_PID; GPD_TASK_NONE and GPD_TASK_HOVER; physics_flags 0 or any of
+ * GPD_PHYS_GND | DRAG | GROUND | DAMP.  GPD_ENOTSUP, before any device call: drones_per_env > 1, another action type,
+ * GPD_TASK_MULTIHOVER, GPD_PHYS_DW, state.bad or state.act_ring non-NULL.  GPD_EINVAL: a NULL pointer, the state's layout, sizes and
+ * strides, unknown enums, the task's values, the rows' alignment and pitch, obst_ld, whatever the configuration needs and misses
+ * (state.pid, state.last_rpm, target_pos, init_pose).  GPD_ERANGE: n_obst, n_rays, more than 2^26 drones.  Asynchronous on `stream`,
+ * no allocation, one launch.  There is no collision RESPONSE: a drone that is not reset flies on through the obstacle.
+ */
+typedef struct GpdObstTask {
+    float   collision_radius;          /* > 0, finite: the drone as a sphere, as in gpd_obstacles */
+    int32_t hit_terminates;            /* 0 / 1: terminated |= hit */
+    float   hit_reward;                /* added to the reward of the step that ends in contact (finite) */
+    float   prox_margin, prox_weight;  /* >= 0, finite: reward -= prox_weight * max(0, prox_margin - (d - collision_radius)) */
+    int32_t n_rays;                    /* 0 .. GPD_OBST_MAX_RAYS */
+    int32_t ray_frame;                 /* GPD_RAY_* */
+    float   max_range;                 /* > 0, finite (read only when n_rays > 0) */
+} GpdObstTask;
+int gpd_sizeof_obst_task(int32_t* size_out);
+int gpd_rollout_obst(const GpdParams* params, const GpdState* state, const GpdStepCfg* cfg, const GpdObstTask* task, int32_t num_steps,
+                     const float* actions, int64_t action_step_stride, const float* target_pos, const float* init_pose,
+                     const float* obst, int32_t n_obst, int64_t obst_ld, const float* ray_dirs,
+                     float* rows, int64_t row_ld, int64_t row_step_stride,
+                     float* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* collided, int64_t env_step_stride,
+                     void* stream);
+
+/*
  * Sampling-based model-predictive control (MPPI, Williams et al., "Information theoretic MPC for model-based reinforcement
  * learning", ICRA 2017): per drone, M perturbed action sequences around a nominal one are rolled H env steps through the physics,
  * scored, and the nominal is replaced by their cost-weighted average.  The reference has no planner; the nearest it comes is the
