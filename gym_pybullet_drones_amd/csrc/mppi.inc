@@ -31,6 +31,11 @@ __device__ __forceinline__ float wave_min(float v) {
     return v;
 }
 
+// the weighted cost sum is kept as sum w (S 2^-11): M <= 1024 finite costs of up to FLT_MAX (w_obs as a hard wall) then sum without an
+// overflow, and a power of two changes no other bit
+constexpr float kMppiSumScale = 4.8828125e-4f, kMppiSumUnscale = 2048.0f;
+__device__ __forceinline__ float mppi_mean_cost(float sws, float inv_sw) { return fminf(sws * inv_sw * kMppiSumUnscale, 3.4028234e38f); }
+
 // the action of sample m of drone n at step h: the clamped perturbation of the nominal u
 __device__ __forceinline__ float4 mppi_action(const GpdMppi& Q, uint32_t n, uint32_t m, uint32_t h, const float4 u) {
     float z0, z1, z2, z3;
@@ -130,7 +135,7 @@ __global__ __launch_bounds__(kBlock) void gpd_mppi_kernel(const GpdParams P, con
         const float w = gpd_mppi_weight(S, smin, inv_lambda);
         sw += w;
         sww = fmaf(w, w, sww);
-        sws += fin ? w * S : 0.0f;
+        sws += fin ? w * (S * kMppiSumScale) : 0.0f;
         cnt += fin ? 1.0f : 0.0f;
     }
     sw = wave_sum(sw); sww = wave_sum(sww); sws = wave_sum(sws); cnt = wave_sum(cnt);
@@ -155,7 +160,7 @@ __global__ __launch_bounds__(kBlock) void gpd_mppi_kernel(const GpdParams P, con
                          clampf(fmaf(az, inv_sw, u.z), Q.act_lo[2], Q.act_hi[2]), clampf(fmaf(aw, inv_sw, u.w), Q.act_lo[3], Q.act_hi[3])};
         if (lane == 0) *reinterpret_cast<f4v*>(on + h * u_stride) = out;
     }
-    if (lane == 0) stats4[n] = make_float4(smin, any ? sws * inv_sw : GPD_OBST_INF, any ? (sw * sw) / sww : 0.0f, cnt);
+    if (lane == 0) stats4[n] = make_float4(smin, any ? mppi_mean_cost(sws, inv_sw) : GPD_OBST_INF, any ? (sw * sw) / sww : 0.0f, cnt);
 }
 
 // what gpd_mppi and gpd_mppi_ctbr refuse of the plan itself: the sampler, the buffers, the strides, the list (N: the drones)

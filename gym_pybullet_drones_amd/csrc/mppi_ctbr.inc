@@ -56,7 +56,7 @@ __device__ __forceinline__ void mppi_update(const GpdMppi& Q, const int n, const
         const float w = gpd_mppi_weight(S, smin, inv_lambda);
         sw += w;
         sww = fmaf(w, w, sww);
-        sws += fin ? w * S : 0.0f;
+        sws += fin ? w * (S * kMppiSumScale) : 0.0f;            // (as gpd_mppi_kernel: no overflow of the sum)
         cnt += fin ? 1.0f : 0.0f;
     }
     sw = wave_sum(sw); sww = wave_sum(sww); sws = wave_sum(sws); cnt = wave_sum(cnt);
@@ -77,7 +77,7 @@ __device__ __forceinline__ void mppi_update(const GpdMppi& Q, const int n, const
                          clampf(fmaf(az, inv_sw, u.z), Q.act_lo[2], Q.act_hi[2]), clampf(fmaf(aw, inv_sw, u.w), Q.act_lo[3], Q.act_hi[3])};
         if (lane == 0) *reinterpret_cast<f4v*>(on + h * u_stride) = out;
     }
-    if (lane == 0) stats4[n] = make_float4(smin, any ? sws * inv_sw : GPD_OBST_INF, any ? (sw * sw) / sww : 0.0f, cnt);
+    if (lane == 0) stats4[n] = make_float4(smin, any ? mppi_mean_cost(sws, inv_sw) : GPD_OBST_INF, any ? (sw * sw) / sww : 0.0f, cnt);
 }
 
 // OBST: a list is given

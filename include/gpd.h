@@ -175,7 +175,11 @@ typedef struct GpdState {
      * of the episode, envs/BaseAviary.py:831-877); a NaN position also never trips a truncation bound
      * (every comparison is false), so without the flag a poisoned aviary runs on until the episode clock ends it.  (Deviation for
      * garbage input, DSLPID action types only: a NaN set-point is absorbed by the controller's clips -- the hardware min/max return
-     * the bound where numpy's clip propagates the NaN -- so the drone sees one step of saturated commands and stays finite.)  Costs
+     * the bound where numpy's clip propagates the NaN -- so the drone sees one step of saturated commands and stays finite.)  (Two more
+     * states that heal, both by the model's own rules: under GPD_PHYS_GROUND a height of -inf is below the plane, so the next sub-step
+     * puts the drone on it and it ends finite; and a NaN in the quaternion reads pitch = -pi/2 -- the clamp in front of the arcsine
+     * returns its bound -- which trips tilt_bound: a task with that bound truncates the aviary in the same step, and auto_reset then
+     * resets it.  Without either the state stays non-finite and the byte stays 1.)  Costs
      * thirteen adds and a compare per drone and launch, outside the step loop.  The byte describes the state the call LEAVES BEHIND: an
      * aviary that went non-finite inside a K-step launch and was reset by its episode clock in the same launch (auto_reset) ends finite
      * and reads 0 -- a caller that must see every event checks between shorter launches. */
@@ -763,7 +767,9 @@ int gpd_rollout_obst(const GpdParams* params, const GpdState* state, const GpdSt
  *         continuous in the state.
  * S_m = sum_h c_h;  w_m = exp(-(S_m - min S) / lambda), minimum and sums over the FINITE S_m only, a sample whose cost is not finite
  * has weight 0;  u_out[h] = u_in[h] + sum_m w_m (a_mh - u_in[h]) / sum_m w_m, clamped once more against rounding.  No finite sample
- * at all: u_out = clamp(u_in), stats4 = (+inf, +inf, 0, 0).
+ * at all: u_out = clamp(u_in), stats4 = (+inf, +inf, 0, 0) -- what a drone whose start state is not finite gets, every one of its costs
+ * being NaN or +-inf.  Finite costs up to FLT_MAX (w_obs as a hard wall: the hinge of a sample that comes too close overflows to +inf,
+ * the others stay large and finite) are averaged without overflow: the sums are taken over w and w (S 2^-11).
  *
  *   cfg             drones_per_env = 1, physics_flags 0 (the planning model is the flag-less explicit integrator), task GPD_TASK_NONE,
  *                   no auto-reset, act_type GPD_ACT_RPM or GPD_ACT_VEL; any sub-step count
@@ -839,7 +845,8 @@ int gpd_mppi_ctbr(const GpdParams* params, const struct GpdCtbr* ctbr, const Gpd
  *   path_out   [H][N][4] out or NULL, the layout and stride of u_out, 16-byte aligned; must not be u_in or u_out, and must not
  *         overlap pos.  After the update the NEW nominal -- u_out as stored, the clamped one -- is flown without noise from the
  *         start state through the same model: x, y, z the position after step h, w the distance to the nearest counted peer at
- *         that step (+inf: none).  One writer per row.
+ *         that step (+inf: none).  One writer per row.  A drone whose start state is not finite: x, y, z are those of the flight
+ *         from that state, some component not finite at every step, and w is +inf (a distance that is not finite is no peer's).
  * Refused before any device work, every message starting "gpd_mppi_peers: ".  GPD_EINVAL: everything the model's own entry answers
  * with it, and NULL peers / idx / pos, k outside 1 .. 32, idx_ld < k, n_rows < N, a pos_step_stride that is neither 0 nor a multiple
  * of 4 >= 4 n_rows, a misaligned pos or path_out, path_out equal to u_in or u_out, w_peer or peer_dist negative or not finite.
@@ -869,7 +876,8 @@ int gpd_mppi_peers(const GpdParams* params, const struct GpdCtbr* ctbr /* NULL: 
  *         aligned): drone n's model is column n.  One wave plans one drone, so its row is read once, at wave-uniform addresses.  The
  *         controller (DSLPID's model and gains, the rate loop's M and J), the action mapping (HOVER_RPM, the MAX_RPM clip), the
  *         geometry, gnd_eff_h_clip and ground_z stay nominal, exactly as the plant path defines it (GPD_PLANT_*, above).
- *   cfg.physics_flags   any of GPD_PHYS_GND, GPD_PHYS_DRAG, GPD_PHYS_GROUND, GPD_PHYS_DAMP.
+ *   cfg.physics_flags   any of GPD_PHYS_GND, GPD_PHYS_DRAG, GPD_PHYS_GROUND, GPD_PHYS_DAMP.  (Under GPD_PHYS_GROUND a start height of -inf is below
+ *         the plane: the first sub-step of every sample puts the drone on it, and it plans like any other.)
  *   step  ctbr NULL: one env step as gpd_step takes it for one drone -- the action mapped on the plant, then `substeps` sub-steps; the drag
  *         term sees the previous step's RPMs on the first sub-step and this step's after it, and the last RPMs are carried from step to
  *         step of a sample.  ctbr given: one control step as gpd_rollout_ctbr takes it in GPD_CTBR_CMD -- the rate loop on the nominal M
