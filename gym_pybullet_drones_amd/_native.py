@@ -31,7 +31,7 @@ ABI_VERSION = 9
 #   policy.hip        gpd_rollout_policy                 the default scheduler: 10 % faster on its MFMA + activation mix (round-2 A/B)
 #   swarm.hip         the one-world kernels              max-ilp, as in rounds 2-4
 #   abi.hip           small kernels, RCCL, library-level entries; the differentiable rollout (RPM and DSLPID), gpd_obstacles, gpd_rollout_obst, gpd_mppi and the
-#                     thrust-and-body-rate controller gpd_ctbr / gpd_rollout_ctbr with its planner gpd_mppi_ctbr, gpd_mppi_peers, gpd_mppi_plant and its differentiable
+#                     thrust-and-body-rate controller gpd_ctbr / gpd_rollout_ctbr (as a task: gpd_task_eval / gpd_rollout_ctbr_task) with its planner gpd_mppi_ctbr, gpd_mppi_peers, gpd_mppi_plant and its differentiable
 #                     rollout (csrc/*.inc pulled in at its end)
 #   mrac.hip          gpd_mrac / gpd_mrac_reset / gpd_rollout_mrac: the adaptive controller and the rollout that carries it (max-ilp)
 #   -mllvm -amdgpu-kernarg-preload-count=14: the first 14 argument dwords of a kernel arrive in SGPRs with the wave (gfx942+ command
@@ -41,7 +41,7 @@ MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 HIPCC_FLAGS = COMMON_FLAGS + MAX_ILP + ["-shared"]        # (kept under this name for the ISA tests)
 UNITS = (("step_rollout.hip", MAX_ILP + KERNARG_PRELOAD), ("policy.hip", []), ("swarm.hip", MAX_ILP + KERNARG_PRELOAD), ("abi.hip", MAX_ILP), ("mrac.hip", MAX_ILP))
-HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc", "diff_pid_kernels.inc", "dslpid_vjp.inc", "obstacle_math.inc", "obstacles.inc", "obst_task_math.inc", "obst_task.inc", "mppi_math.inc", "mppi.inc", "ctbr_math.inc", "ctbr.inc", "mppi_ctbr.inc", "mppi_peers_math.inc", "mppi_peers.inc", "mppi_plant.inc", "ctbr_vjp.inc", "diff_ctbr_kernels.inc")
+HEADERS = ("gpd_common.inc", "policy_kernel.inc", "diff_kernels.inc", "plant_derive_vjp.inc", "diff_pid_kernels.inc", "dslpid_vjp.inc", "obstacle_math.inc", "obstacles.inc", "obst_task_math.inc", "obst_task.inc", "mppi_math.inc", "mppi.inc", "ctbr_math.inc", "ctbr.inc", "ctbr_task.inc", "mppi_ctbr.inc", "mppi_peers_math.inc", "mppi_peers.inc", "mppi_plant.inc", "ctbr_vjp.inc", "diff_ctbr_kernels.inc")
 
 
 class GpdError(RuntimeError):
@@ -124,6 +124,11 @@ class GpdObstTask(ctypes.Structure):
     _fields_ = [("collision_radius", ctypes.c_float), ("hit_terminates", ctypes.c_int32), ("hit_reward", ctypes.c_float),
                 ("prox_margin", ctypes.c_float), ("prox_weight", ctypes.c_float), ("n_rays", ctypes.c_int32), ("ray_frame", ctypes.c_int32),
                 ("max_range", ctypes.c_float)]
+
+
+class GpdCtbrTask(ctypes.Structure):
+    """mirror of `struct GpdCtbrTask` (gpd_rollout_ctbr_task: the affine map from a normalised action to the command)"""
+    _fields_ = [("act_scale", ctypes.c_float * 4), ("act_bias", ctypes.c_float * 4), ("normalized", ctypes.c_int32), ("pad_", ctypes.c_int32 * 3)]
 
 
 #: `mode` of gpd_rollout_ctbr (GPD_CTBR_CMD / GPD_CTBR_POS)
@@ -242,6 +247,11 @@ _SIGNATURES = {
     "gpd_ctbr": (ctypes.c_int, [ctypes.POINTER(GpdCtbr), _P, _P, _P, _P, _P, _P, ctypes.c_int32, _P]),
     "gpd_rollout_ctbr": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdCtbr), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg),
                                         ctypes.c_int32, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, ctypes.c_int32, _P]),
+    "gpd_task_eval": (ctypes.c_int, [ctypes.POINTER(GpdStepCfg), _P, _P, _P, _P, _P, _P, _P]),
+    "gpd_sizeof_ctbr_task": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int32)]),
+    "gpd_rollout_ctbr_task": (ctypes.c_int, [ctypes.POINTER(GpdParams), ctypes.POINTER(GpdCtbr), ctypes.POINTER(GpdState), ctypes.POINTER(GpdStepCfg),
+                                             ctypes.POINTER(GpdCtbrTask), ctypes.c_int32, _P, ctypes.c_int64, _P, _P, _P, _P, _P, ctypes.c_int64, _P, _P, _P,
+                                             ctypes.c_int64, _P, _P]),
     "gpd_state_vectors": (ctypes.c_int, [ctypes.POINTER(GpdState), _P, _P, ctypes.c_int32, _P]),
     "gpd_comm_unique_id": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8)]),
     "gpd_comm_init": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32,
@@ -326,6 +336,9 @@ def lib() -> ctypes.CDLL:
     obst_size = ctypes.c_int32(0)
     if L.gpd_sizeof_obst_task(ctypes.byref(obst_size)) != 0 or obst_size.value != ctypes.sizeof(GpdObstTask):
         raise GpdError(f"struct layout mismatch: GpdObstTask is {obst_size.value} bytes in the library, {ctypes.sizeof(GpdObstTask)} in the binding")
+    task_size = ctypes.c_int32(0)
+    if L.gpd_sizeof_ctbr_task(ctypes.byref(task_size)) != 0 or task_size.value != ctypes.sizeof(GpdCtbrTask):
+        raise GpdError(f"struct layout mismatch: GpdCtbrTask is {task_size.value} bytes in the library, {ctypes.sizeof(GpdCtbrTask)} in the binding")
     _lib = L
     return L
 

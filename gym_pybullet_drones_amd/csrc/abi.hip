@@ -607,6 +607,9 @@ int gpd_clock_probe(double* shader_ghz, double* ns_per_fma, void* stream) {
 // thrust and body-rate commands: gpd_sizeof_ctbr / gpd_ctbr / gpd_rollout_ctbr and their kernels
 #include "ctbr.inc"
 
+// ... as a task: gpd_task_eval, gpd_sizeof_ctbr_task / gpd_rollout_ctbr_task and their kernels (reward, episode ends and the auto-reset in the launch)
+#include "ctbr_task.inc"
+
 // ... and the planner over them: gpd_mppi_ctbr and its kernel (mppi.inc's two passes on ctbr_math.inc's rate loop)
 #include "mppi_ctbr.inc"
 

@@ -36,6 +36,29 @@ __device__ __forceinline__ CtbrRow ctbr_row(const float* __restrict__ rows, uint
     }
 }
 
+// One physics sub-step under the rate loop, for gpd_rollout_ctbr_kernel and ctbr_task_kernel (ctbr_task.inc) alike: the command is held,
+// the body rates are the integrator's own, and the drag term sees the RPMs applied one sub-step earlier (state.last_rpm on the launch's
+// very first one).  AV: this sub-step's world angular velocity is observed.
+template <bool EXT, bool AV, class PL>
+__device__ __forceinline__ void ctbr_substep(const GpdParams& P, const GpdCtbr& B, const PL& Q, const GpdStepCfg& C, const uint32_t flags,
+                                             const bool drag, const float cmd[4], Carry& c, float& avx, float& avy, float& avz) {
+    Kin& k = c.k;
+    float rpm[4], g[4];
+    gpd_ctbr_rate_loop(&B, P.M, P.J[0], P.J[1], P.J[2], cmd, k.wx, k.wy, k.wz, rpm);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) g[i] = thrust_dev(Q, rpm[i]);
+    const float drag_sum = drag ? ((c.l0 + c.l1) + c.l2) + c.l3 : 0.0f;
+    substep<EXT, AV>(Q, C.pyb_dt, flags, g, drag_sum, 0.0f, k, avx, avy, avz);
+    c.l0 = rpm[0]; c.l1 = rpm[1]; c.l2 = rpm[2]; c.l3 = rpm[3];
+}
+// the S sub-steps of one control step: only the last one's world angular velocity is observed
+template <bool EXT, class PL>
+__device__ __forceinline__ void ctbr_substeps(const GpdParams& P, const GpdCtbr& B, const PL& Q, const GpdStepCfg& C, const uint32_t flags,
+                                              const bool drag, const float cmd[4], Carry& c, float& avx, float& avy, float& avz) {
+    for (int ss = 1; ss < C.substeps; ++ss) ctbr_substep<EXT, false>(P, B, Q, C, flags, drag, cmd, c, avx, avy, avz);
+    ctbr_substep<EXT, true>(P, B, Q, C, flags, drag, cmd, c, avx, avy, avz);
+}
+
 template <int MODE, bool EXT, bool PLANT>
 __global__ __launch_bounds__(kBlock) void gpd_rollout_ctbr_kernel(
     const GpdParams P, const GpdCtbr B, float* __restrict__ kin, float* __restrict__ last_rpm, int32_t* __restrict__ step_counter,
@@ -65,18 +88,7 @@ __global__ __launch_bounds__(kBlock) void gpd_rollout_ctbr_kernel(
         else { cmd[0] = row.a.x; cmd[1] = row.a.y; cmd[2] = row.a.z; cmd[3] = row.a.w; }
         if (cmd_out) *reinterpret_cast<float4*>(reinterpret_cast<char*>(cmd_out + t * cstride) + n * 16u) = make_float4(cmd[0], cmd[1], cmd[2], cmd[3]);
         // ---- S sub-steps, the rate loop in each: the command is held, the body rates are the integrator's own
-        auto sub = [&](auto av) {
-            float rpm[4], g[4];
-            gpd_ctbr_rate_loop(&B, P.M, P.J[0], P.J[1], P.J[2], cmd, k.wx, k.wy, k.wz, rpm);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) g[i] = thrust_dev(Q, rpm[i]);
-            // the drag term sees the RPMs applied one sub-step earlier (state.last_rpm on the launch's very first one)
-            const float drag_sum = drag ? ((c.l0 + c.l1) + c.l2) + c.l3 : 0.0f;
-            substep<EXT, decltype(av)::value>(Q, C.pyb_dt, flags, g, drag_sum, 0.0f, k, avx, avy, avz);
-            c.l0 = rpm[0]; c.l1 = rpm[1]; c.l2 = rpm[2]; c.l3 = rpm[3];
-        };
-        for (int ss = 1; ss < C.substeps; ++ss) sub(Const<false>{});
-        sub(Const<true>{});               // only the last sub-step's world angular velocity is observed
+        ctbr_substeps<EXT>(P, B, Q, C, flags, drag, cmd, c, avx, avy, avz);
         quat_to_rpy(k.qx, k.qy, k.qz, k.qw, c.roll, c.pitch, c.yaw);
         c.counter += C.substeps;
         if (ostride != 0 || t == K - 1) store_obs12(obs12 + t * ostride, n, k.px, k.py, k.pz, c.roll, c.pitch, c.yaw, k.vx, k.vy, k.vz, avx, avy, avz);

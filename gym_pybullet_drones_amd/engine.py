@@ -628,6 +628,62 @@ class SimCore:
             self.obs12.copy_(obs[K - 1])
         return (obs, cmd) if want_cmd else obs
 
+    def task_eval(self, obs12: torch.Tensor, counter: torch.Tensor):
+        """The single-drone task on rows (`gpd_task_eval`): reward, terminated, truncated -- fresh `[E]` tensors -- of this core's task
+        for the `obs12 [E, 12]` rows and the `counter [E]` int32 step counters from BEFORE the step that left the rows, computed by
+        the device function `step()` runs inside its kernel.  What gives a composed flight (`rollout_ctbr`, `rollout_mrac`) a task;
+        the core's own state is not touched.  Aviaries of one drone."""
+        if action_needs_fix(obs12, self.device):
+            obs12 = obs12.to(device=self.device, dtype=torch.float32).contiguous()
+        counter = counter.to(device=self.device, dtype=torch.int32).contiguous()
+        if obs12.numel() != self.E * 12 or counter.numel() != self.E:
+            raise ValueError(f"task_eval: obs12 must hold {self.E} x 12 floats and counter {self.E} values")
+        rew = torch.empty((self.E,), dtype=torch.float32, device=self.device)
+        term, trunc = (torch.empty((self.E,), dtype=torch.bool, device=self.device) for _ in range(2))
+        _native.call("gpd_task_eval", self.device, self._stream(), self._cfg, obs12, counter, self.target, rew, term, trunc)
+        return rew, term, trunc
+
+    def rollout_ctbr_task(self, ctrl, actions, num_steps: int = None, last_only: bool = False, task: "_native.GpdCtbrTask" = None,
+                          want_cmd: bool = False, update_latest: bool = True):
+        """K env steps in ONE launch whose ACTION is the thrust and body-rate command (`gpd_rollout_ctbr_task`): `rollout_ctbr`'s
+        flight in "cmd" mode, then this core's task (reward, terminated, truncated), the same-step auto-reset and the terminal rows,
+        as `rollout()` does them.  `ctrl`: a `control.VectorCTBR` with one controller per drone; `actions`, `num_steps`: as in
+        `rollout()`, rows of 4 floats; `task`: a `GpdCtbrTask` -- with `normalized` the command is `fma(a, act_scale, act_bias)` -- or
+        None: the action is the physical command.
+
+        Returns `(obs12 [K,N,12], reward [K,E], terminated [K,E], truncated [K,E])`, the persistent buffers of `rollout()` with its
+        conventions (`last_only`: the latest-step tensors; `keep_terminal_obs`: the `[K,N,12]` terminal block and `term_obs12`;
+        `update_latest=False` leaves the latest-step tensors alone: the launch and nothing else).  `last_only` with more than one
+        step keeps the last step's terminal rows alone, as it keeps the last step's observations: an episode that ends earlier in
+        the launch leaves nothing in `term_obs12` (without `last_only` it holds what K single steps would have left);
+        with `want_cmd` a fifth member, a fresh tensor of the commands each step flew, shaped like `actions`' blocks.  Bit for bit K x
+        (`rollout_ctbr(..., 1)`, `task_eval`, a masked `reset`), and K1 then K2 steps are K1 + K2 in one launch.  Aviaries of one
+        drone, RPM actions, no downwash; a plant table is honoured."""
+        if self.host_visible:
+            raise ValueError("rollout_ctbr_task: a host-visible core steps one aviary at a time (CtrlAviary.step takes RPMs)")
+        if self.act_ring is not None:
+            raise ValueError("rollout_ctbr_task: this core keeps an action history, which the fused rollout would not advance")
+        if getattr(ctrl, "n", None) != self.N or ctrl.device != self.device or not hasattr(ctrl, "thrust_max"):
+            raise ValueError(f"rollout_ctbr_task needs a VectorCTBR of {self.N} controllers on {self.device}")
+        if self.A != 4:
+            raise ValueError("rollout_ctbr_task: the core must take RPM actions (four per drone)")
+        actions, K, a_stride = self._action_blocks(actions, num_steps)
+        if last_only:
+            obs, rew, term, trunc, tobs = self.obs12, self.reward, self.terminated, self.truncated, self.term_obs12
+            o_stride = e_stride = 0
+        else:
+            obs, rew, term, trunc, tobs = self._rollout_buffers(K)
+            o_stride, e_stride = self.N * 12, self.E
+        cmd = torch.empty((self.N, 4) if a_stride == 0 else (K, self.N, 4), dtype=torch.float32, device=self.device) if want_cmd else None
+        self.state_version += 1
+        _native.call("gpd_rollout_ctbr_task", self.device, self._stream(), self._params, ctrl.struct(), self._state, self._cfg, task, K,
+                     actions, a_stride, self.target, self.init_pose, self.plant_rows, obs, tobs, o_stride, rew, term, trunc, e_stride, cmd)
+        if not last_only and update_latest:
+            self._publish_latest(obs, rew, term, trunc, K)
+            if tobs is not None and self.auto_reset:
+                self._latest_terminal(tobs, term, trunc, K)
+        return (obs, rew, term, trunc, cmd) if want_cmd else (obs, rew, term, trunc)
+
     #: output buffers of `rollout_obst`, per (steps kept, row pitch): allocated once
     _obst_cache = None
 

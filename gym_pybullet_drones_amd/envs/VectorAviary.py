@@ -572,6 +572,107 @@ class VectorObstacleAviary(VectorAviary):
         raise NotImplementedError("VectorObstacleAviary: the field is part of the task, given at construction")
 
 
+class VectorCTBRAviary(VectorAviary):
+    """E single-drone aviaries whose ACTION is the thrust and body-rate command (CTBR), the action space agile-flight RL trains on:
+    `obs, r, term, trunc, info = env.step(a)` with `a (E, 1, 4)` in [-1, 1], a body-rate loop closed inside every physics sub-step in
+    place of the firmware (`control.VectorCTBR`, owned by the aviary as `ctrl`).  One launch per `step()` and one per K-step `rollout()`
+    (`gpd_rollout_ctbr_task`): the rate loop, the task's reward and flags, the same-step auto-reset and the terminal observation all
+    happen inside the kernel.
+
+    `normalized=True` (default): thrust = `thrust_center + a_0 thrust_span`, rates = `a_{1..3} rate_span`, hover-centred by default --
+    center = span = the controller's g (9.8 m/s^2: `a = 0` is the hover command, `a = -1` zero thrust), rate_span = the controller's
+    `rate_max`.  `normalized=False`: the action is the physical command (thrust [m/s^2] | rates [rad/s]).  Either way the rate loop's
+    `thrust_max` / `rate_max` clips bound what is flown.  `randomize`, `keep_terminal_obs`, `nan_guard`, `reset(mask=)`: as in
+    `VectorAviary`.  Not served: aviaries of several drones, the action history (`full_obs`), downwash, position targets as the
+    action."""
+
+    def __init__(self, num_envs: int, thrust_center: float = None, thrust_span: float = None, rate_span: float = None, normalized: bool = True,
+                 k_rate=None, thrust_max: float = None, rate_max: float = None, ctrl_freq: int = 48, task: str = "hover", target_pos=None,
+                 num_drones: int = 1, drone_model: DroneModel = DroneModel.CF2X, initial_xyzs=None, initial_rpys=None,
+                 physics: Physics = Physics.DYN, pyb_freq: int = 240, episode_len_sec: float = 8, auto_reset: bool = True,
+                 full_obs: bool = False, keep_terminal_obs: bool = False, track_rpm: bool = False, pyb_like: bool = None,
+                 nan_guard: bool = False, randomize: dict = None, device=None):
+        from ..control.CTBRControl import K_RATE, RATE_MAX, THRUST_MAX, VectorCTBR, to_struct
+        self._refuse(num_drones, task, physics, pyb_like, full_obs)
+        k_rate = K_RATE if k_rate is None else k_rate
+        thrust_max = THRUST_MAX if thrust_max is None else thrust_max
+        rate_max = RATE_MAX if rate_max is None else rate_max
+        gains = to_struct(DroneParams(drone_model), k_rate, thrust_max, rate_max)     # (ValueError for bad gains, before any device work)
+        self._task = self.task_struct(gains.g, gains.rate_max, thrust_center, thrust_span, rate_span, normalized)
+        super().__init__(num_envs=num_envs, num_drones=1, drone_model=drone_model, initial_xyzs=initial_xyzs, initial_rpys=initial_rpys,
+                         physics=physics, pyb_freq=pyb_freq, ctrl_freq=ctrl_freq, act="raw_rpm", task=task, target_pos=target_pos,
+                         episode_len_sec=episode_len_sec, auto_reset=auto_reset, keep_terminal_obs=keep_terminal_obs, track_rpm=track_rpm,
+                         pyb_like=pyb_like, nan_guard=nan_guard, randomize=randomize, device=device)
+        self.ctrl = VectorCTBR(self.NUM_ENVS, drone_model, device=self.device, k_rate=k_rate, thrust_max=thrust_max, rate_max=rate_max)
+        self.NORMALIZED = bool(normalized)
+        self.ACT_DIM, self.OBS_DIM = 4, 12
+
+    @staticmethod
+    def _refuse(num_drones, task, physics, pyb_like, full_obs):
+        """what the fused CTBR task does not serve (include/gpd.h gpd_rollout_ctbr_task), before any device work"""
+        if int(num_drones) != 1:
+            raise NotImplementedError("VectorCTBRAviary: num_drones > 1 (the command flies a single drone)")
+        if full_obs:
+            raise NotImplementedError("VectorCTBRAviary: full_obs (the action history) is not served by the fused CTBR task")
+        if task not in ("hover", "none"):
+            raise NotImplementedError("VectorCTBRAviary: task must be 'hover' or 'none'")
+        flags = physics.mask(pyb_like) if isinstance(physics, Physics) else int(physics)
+        if flags & 4:
+            raise NotImplementedError("VectorCTBRAviary: downwash needs mates, the command flies a single drone")
+
+    @staticmethod
+    def task_struct(g, rate_max, thrust_center=None, thrust_span=None, rate_span=None, normalized=True) -> "_native.GpdCtbrTask":
+        """the `GpdCtbrTask` of the arguments: cmd = (thrust_center + a_0 thrust_span, a_1 rate_span, a_2 rate_span, a_3 rate_span), the
+        defaults hover-centred (center = span = `g`, rate_span = `rate_max`); ValueError for values that are not finite"""
+        center = float(g) if thrust_center is None else float(thrust_center)
+        span = float(g) if thrust_span is None else float(thrust_span)
+        rspan = float(rate_max) if rate_span is None else float(rate_span)
+        if not all(math.isfinite(v) for v in (center, span, rspan)):
+            raise ValueError(f"thrust_center, thrust_span and rate_span must be finite, got {(center, span, rspan)}")
+        t = _native.GpdCtbrTask(normalized=int(bool(normalized)))
+        t.act_scale[0], t.act_bias[0] = span, center
+        for i in (1, 2, 3):
+            t.act_scale[i], t.act_bias[i] = rspan, 0.0
+        return t
+
+    def command(self, action: torch.Tensor) -> torch.Tensor:
+        """the physical command (thrust [m/s^2] | rates [rad/s]) of `action`, in its shape: the kernel's map as torch operations (a
+        diagnostic; rounds once more than the kernel's fused multiply-add)"""
+        if not self.NORMALIZED:
+            return action
+        scale = torch.tensor(list(self._task.act_scale), dtype=torch.float32, device=action.device)
+        bias = torch.tensor(list(self._task.act_bias), dtype=torch.float32, device=action.device)
+        return action * scale + bias
+
+    def action_of(self, cmd: torch.Tensor) -> torch.Tensor:
+        """the action whose command is `cmd` (the inverse of the map, not clipped to [-1, 1])"""
+        if not self.NORMALIZED:
+            return cmd
+        scale = torch.tensor(list(self._task.act_scale), dtype=torch.float32, device=cmd.device)
+        bias = torch.tensor(list(self._task.act_bias), dtype=torch.float32, device=cmd.device)
+        return (cmd - bias) / scale
+
+    def step(self, action: torch.Tensor):
+        """action (E, 1, 4) -> (obs (E, 1, 12), reward [E], terminated [E], truncated [E], info): ONE launch.  With `keep_terminal_obs`,
+        `info["terminal_observation"]` holds the last row of every episode that ended."""
+        _, reward, terminated, truncated = self.core.rollout_ctbr_task(self.ctrl, action, 1, last_only=True, task=self._task)
+        if self.randomize and self.core.auto_reset:          # the aviaries that ended were reset by the step: new airframes
+            self._resample(terminated | truncated)
+        info = {}
+        if self.core.term_obs12 is not None:
+            info["terminal_observation"] = self.core.term_obs12.view(self.NUM_ENVS, 1, 12)
+        return self._obs(), reward, terminated, truncated, info
+
+    def rollout(self, actions: torch.Tensor):
+        """actions (K, E, 1, 4) -> (obs (K, E, 1, 12), reward (K, E), terminated (K, E), truncated (K, E)): K steps in ONE launch, bit for
+        bit K calls of `step()` (with `randomize`, an aviary that ends inside the launch keeps its airframe until the launch ends)."""
+        K = actions.shape[0]
+        obs, reward, terminated, truncated = self.core.rollout_ctbr_task(self.ctrl, actions, task=self._task)
+        if self.randomize and self.core.auto_reset:
+            self._resample((terminated | truncated).any(dim=0))
+        return obs.view(K, self.NUM_ENVS, 1, 12), reward, terminated, truncated
+
+
 class VecEnvAdapter:
     """Stable-Baselines3 `VecEnv`-shaped front end of a `VectorAviary` (duck-typed: SB3 is not installed here).
 

@@ -1101,6 +1101,78 @@ int gpd_rollout_ctbr(const GpdParams* params, const GpdCtbr* ctbr, const GpdStat
                      float* cmd_out, int32_t num_steps, void* stream);
 
 /*
+ * The single-drone task on rows: reward, terminated and truncated of num_envs single-drone aviaries from their obs12 rows, exactly as
+ * gpd_step computes them inside the step (the same device function; envs/HoverAviary.py:68-132).  One lane per drone, asynchronous on
+ * `stream`, capturable.  The building block that gives a composed flight -- gpd_rollout_ctbr, gpd_rollout_mrac -- a task.
+ *   cfg          read: task, xy_bound, z_bound, tilt_bound, term_dist, trunc_counter, target_per_env, num_envs (drones_per_env must be 1)
+ *   obs12        [num_envs][12], 16-byte aligned: position and roll / pitch are read from the row
+ *   counter      [num_envs] int32: the aviary's step counter BEFORE the step's increment (what state.step_counter held before the step)
+ *   target_pos   [3], or [num_envs][3] with target_per_env; NULL allowed with GPD_TASK_NONE
+ *   reward [num_envs], terminated / truncated [num_envs] uint8 out.  GPD_TASK_NONE: -1, 0, 0, as gpd_step answers
+ * With auto_reset = 0, gpd_step's obs12 rows and the counters from before the step give gpd_step's reward and flags bit for bit.
+ * Validated before any device work.  GPD_EINVAL: a NULL pointer, num_envs <= 0, an unknown task, a task without target_pos, obs12 not
+ * 16-byte aligned.  GPD_ENOTSUP: drones_per_env != 1, GPD_TASK_MULTIHOVER.  GPD_ERANGE: num_envs > 2^26.
+ */
+int gpd_task_eval(const GpdStepCfg* cfg, const float* obs12, const int32_t* counter, const float* target_pos, float* reward,
+                  uint8_t* terminated, uint8_t* truncated, void* stream);
+
+/*
+ * CTBR as a task: the action of a single-drone aviary IS the thrust and body-rate command.  num_steps = 1 is the env.step() of such an
+ * environment, num_steps = K its rollout; one launch either way.  Per step and drone, in env_step's order:
+ *   1. the command: the [N][4] action row at actions + t*action_step_stride (stride 0 holds one block) as it is -- thrust [m/s^2], rates
+ *      [rad/s] -- or, with task->normalized, cmd_i = fma(a_i, act_scale[i], act_bias[i]).  No clamp of its own: the rate loop's
+ *      thrust_max / rate_max clips bound it;
+ *   2. `substeps` sub-steps exactly as gpd_rollout_ctbr takes them (the same device function), then the rpy refresh;
+ *   3. the task's reward and flags on the aviary's counter before the increment, as gpd_step computes them (GPD_TASK_NONE: -1, 0, 0);
+ *   4. with cfg.auto_reset, the same-step reset on terminated | truncated, as gpd_step does it: the row of the finished episode goes to
+ *      term_obs12, the pose and its rpy are restored (init_per_env 0 / 1), velocity, body rates, the observed angular velocity, the
+ *      carried RPMs and the step counter become zero;
+ *   5. the obs12 row of the state the step LEAVES BEHIND, reward / terminated / truncated.
+ * Bit for bit what gpd_rollout_ctbr (GPD_CTBR_CMD, one step), gpd_task_eval on its rows with the counters from before the step, and
+ * gpd_reset masked by terminated | truncated give; K1 then K2 steps = K1 + K2 in one launch.
+ */
+typedef struct GpdCtbrTask {
+    float   act_scale[4];   /* normalized: cmd_i = fma(a_i, act_scale[i], act_bias[i]) -- hover-centred: (g, rate_max x 3) ... */
+    float   act_bias[4];    /* ... and (g, 0, 0, 0): a = 0 is the hover command, a = -1 zero thrust */
+    int32_t normalized;     /* 0: the action is the physical command, scale and bias are not read; 1: the affine map */
+    int32_t pad_[3];        /* (to a multiple of 16 bytes) */
+} GpdCtbrTask;
+
+/* sizeof(GpdCtbrTask) -> *size_out, for a binding to verify its mirror (as gpd_sizeof_ctbr).  GPD_EINVAL: NULL. */
+int gpd_sizeof_ctbr_task(int32_t* size_out);
+
+/*
+ *   params, ctbr, state, plant_rows   as gpd_rollout_ctbr.  state.bad, state.last_rpm and state.step_counter are written once per
+ *                  launch, from the state the last step leaves (a drone reset in that step: its reset pose)
+ *   cfg            drones_per_env = 1, GPD_TASK_NONE or GPD_TASK_HOVER, auto_reset 0 / 1, target_per_env and init_per_env 0 / 1,
+ *                  act_type GPD_ACT_RAW_RPM or GPD_ACT_DIRECT_RPM, any sub-step count; GPD_PHYS_GND / DRAG / GROUND / DAMP allowed
+ *   task           HOST pointer or NULL (= not normalized)
+ *   target_pos     [3] or [N][3] (target_per_env); NULL allowed with GPD_TASK_NONE.  init_pose [7] or [N][7] (init_per_env): position,
+ *                  quaternion x y z w; NULL allowed without auto_reset
+ *   obs12          step t writes [N][12] at obs12 + t*obs_step_stride; stride 0 keeps only the last step's rows.  16-byte aligned
+ *   term_obs12     NULL, or laid out as obs12: the rows of the drones whose episode ended at step t, before the reset; the other rows
+ *                  are not written.  16-byte aligned, not obs12 itself.  With obs_step_stride = 0 it keeps, like obs12, the LAST
+ *                  step only: an episode that ends at an earlier step of a K-step launch leaves no terminal row (give a stride to
+ *                  keep every step's)
+ *   reward [N] float, terminated / truncated [N] uint8 per step, env_step_stride elements apart; stride 0 keeps the last step only
+ *   cmd_out        NULL, or [N][4] per step at cmd_out + t*action_step_stride, 16-byte aligned: the command flown, BEFORE the rate loop's
+ *                  clips.  Must not alias actions
+ * Validated before any device work.
+ *   GPD_EINVAL   as gpd_rollout_ctbr, and: NULL actions / obs12 / reward / terminated / truncated, an unknown task, a task without
+ *                target_pos, auto_reset without init_pose, a non-zero env_step_stride below num_envs, term_obs12 not 16-byte aligned or
+ *                equal to obs12, cmd_out == actions, task->normalized neither 0 nor 1
+ *   GPD_ENOTSUP  drones_per_env != 1, GPD_TASK_MULTIHOVER, an act_type other than the two RPM ones, GPD_PHYS_DW or state.dw_force,
+ *                state.act_ring (the history would not be advanced)
+ *   GPD_ERANGE   num_envs > 2^26 (32-bit byte offsets)
+ * GPD_CTBR_POS targets are not offered as the action: a policy's action is the command.
+ */
+int gpd_rollout_ctbr_task(const GpdParams* params, const GpdCtbr* ctbr, const GpdState* state, const GpdStepCfg* cfg,
+                          const GpdCtbrTask* task, int32_t num_steps, const float* actions, int64_t action_step_stride,
+                          const float* target_pos, const float* init_pose, const float* plant_rows, float* obs12, float* term_obs12,
+                          int64_t obs_step_stride, float* reward, uint8_t* terminated, uint8_t* truncated, int64_t env_step_stride,
+                          float* cmd_out, void* stream);
+
+/*
  * Gather the 20-float state vectors of BaseAviary._getDroneStateVector
  * (envs/BaseAviary.py:541-561): pos3 | quat4 | rpy3 | vel3 | ang_v3 | last_clipped_action4,
  * from the SoA state and the obs12 rows of the latest step.  state20 is [n][20].
