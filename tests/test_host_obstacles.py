@@ -1,7 +1,10 @@
 """Obstacle fields, the part that needs no GPU: the float64 yardstick (tests/helpers/obstacles_f64.py) pinned by analytic known
 answers, csrc/obstacle_math.inc compiled for the host under ASan + UBSan (tests/c/obstacle_host.c) against the yardstick on the
-test scene, every refusal of `gpd_obstacles` (all before the first device call), and the packing helpers of `obstacles.py`."""
+test scene and, with nothing left out, on the scenes of degenerate geometry (tests/helpers/obstacles_edges.py: axis rays, points on the
+obstacle, exact ties and thresholds), every refusal of `gpd_obstacles` (all before the first device call), and the packing helpers of
+`obstacles.py`."""
 import ctypes
+import functools
 import math
 import os
 import sys
@@ -12,6 +15,7 @@ import pytest
 from conftest import REPO
 
 sys.path.insert(0, os.path.join(REPO, "tests", "helpers"))
+import obstacles_edges as ed  # noqa: E402
 import obstacles_f64 as y  # noqa: E402
 
 INF = np.inf
@@ -164,14 +168,14 @@ def test_scene_exercises_both_branches_and_stays_inside_the_caps():
 HOST_BOUND = 5.2e-6
 
 
-def run_host_program(exe, tmp, obst, pos, dirs):
+def run_host_program(exe, tmp, obst, pos, dirs, max_range=y.MAX_RANGE, radius=y.COLLISION_RADIUS):
     """tests/c/obstacle_host.c on float32 inputs -> dict of its outputs"""
     import host_lib
     M, N, R = len(obst), len(pos), dirs.shape[1]
     src, dst = os.path.join(tmp, "scene.bin"), os.path.join(tmp, "values.bin")
     with open(src, "wb") as f:
         f.write(np.array([M, N, R], dtype=np.int32).tobytes())
-        f.write(np.array([y.MAX_RANGE, y.COLLISION_RADIUS], dtype=np.float32).tobytes())
+        f.write(np.array([max_range, radius], dtype=np.float32).tobytes())
         for a in (obst, pos, dirs):
             f.write(np.ascontiguousarray(a, dtype=np.float32).tobytes())
     res = host_lib.run(exe, src, dst)
@@ -204,6 +208,148 @@ def test_host_compiled_math_agrees_with_the_yardstick(tmp_path):
     assert max(pair_d, pair_g, err_d, err_n, err_r) <= HOST_BOUND
     # a miss is +inf for every pair, and an origin inside is 0: never a NaN
     assert not np.isnan(got["t"]).any() and (got["t"] >= 0).all() and (got["t"] == 0).any() and np.isinf(got["t"]).any()
+
+
+# ---- degenerate geometry: axis rays, points on the obstacle, exact ties and thresholds (tests/helpers/obstacles_edges.py) -----------
+def test_edge_scenes_hold_every_category_they_exist_for():
+    """a later edit of a scene cannot silently empty a category: the lattice holds every one, the corridor the ties and the rays along
+    its walls; the counts the scenes were chosen by are pinned"""
+    la, co = ed.census(ed.lattice()), ed.census(ed.corridor())
+    print("MEASURED census of the lattice: " + ", ".join(f"{k} {v}" for k, v in la.items()))
+    print("MEASURED census of the corridor: " + ", ".join(f"{k} {v}" for k, v in co.items()))
+    assert ed.lattice().pos.shape == (1650, 3) and ed.corridor().pos.shape == (68, 3)
+    empty = [k for k, v in la.items() if v == 0] + [f"corridor: {k}" for k in ed.CORRIDOR_CATEGORIES if co[k] == 0]
+    assert not empty, empty
+    assert la["tie_of_the_nearest"] == 90 and co["tie_of_the_nearest"] == 40
+    for name, s in ed.scenes().items():                                     # (the variants keep what their scene has)
+        c = ed.census(s)
+        base = la if name.startswith("lattice") else co
+        assert c["tie_of_the_nearest"] >= base["tie_of_the_nearest"] and c["negative_zero_coordinate"] == base["negative_zero_coordinate"], name
+    # the inputs are dyadic: float32 holds them, and every difference point - centre, exactly
+    for s in ed.scenes().values():
+        assert (s.pos * 16 == np.round(s.pos * 16)).all() and (s.obst * 16 == np.round(s.obst * 16)).all(), s.name
+
+
+def test_yardstick_on_the_edge_scenes_names_the_lower_record():
+    la, co = ed.lattice(), ed.corridor()
+    dirs = ed.per_point(ed.axis_dirs(), len(la.pos))
+    base, base_s = y.clearance(la.obst, la.pos), y.scan(la.obst, la.pos, dirs)
+    first = np.array([0, 2, 4, 6])                                           # where the twins list holds the lattice's records first
+    tw, tw_s = y.clearance(ed.twins(la.obst), la.pos), y.scan(ed.twins(la.obst), la.pos, dirs)
+    np.testing.assert_array_equal(tw["nearest"], first[base["nearest"]])
+    np.testing.assert_array_equal(tw_s["ray_hit"], np.where(base_s["ray_hit"] >= 0, first[base_s["ray_hit"]], -1))
+    assert (tw["second"][base["nearest"] != 3] == tw["d"][base["nearest"] != 3]).all()      # every solid nearest is an exact tie
+    no, no_s = y.clearance(ed.with_none(la.obst), la.pos), y.scan(ed.with_none(la.obst), la.pos, dirs)
+    np.testing.assert_array_equal(no["nearest"], 2 * base["nearest"] + 1)
+    np.testing.assert_array_equal(no_s["ray_hit"], np.where(base_s["ray_hit"] >= 0, 2 * base_s["ray_hit"] + 1, -1))
+    np.testing.assert_array_equal(no["d"], base["d"])
+    c = y.clearance(co.obst, co.pos)
+    tie = c["second"] == c["d"]
+    assert tie.sum() == 40 and set(c["nearest"]) == {0, 2, 4} and set(c["nearest"][tie]) == {0, 2}
+    assert (c["normal"][c["nearest"] == 0] == [0, -1, 0]).all()               # the wall at +y pushes towards -y, never its mirror image
+    level = y.scan(co.obst, co.pos, ed.per_point(ed.axis_dirs(), len(co.pos)))
+    assert (level["ray_hit"][:, :4] != 4).all() and (level["ray_hit"][:, 5] == 4).all()      # a level ray never sees the floor
+
+
+def test_yardstick_at_the_thresholds():
+    """a hit is d < radius and a ray sees what enters before max_range: exactly at either is neither"""
+    obst, cases = ed.thresholds()
+    pts, org, dirs = ed.threshold_points(), ed.threshold_origins(), ed.axis_dirs()
+    c = y.clearance(obst, pts, ed.RADIUS)
+    assert list(c["d"][:5]) == [ed.RADIUS] * 5 and (c["d"][5:] < ed.RADIUS).all() and (c["d"][5:] > ed.RADIUS - 1e-6).all()
+    assert list(c["nearest"]) == [k.record for k in cases] * 2 and list(c["hit"]) == [False] * 5 + [True] * 5
+    assert y.clearance(obst, pts, float(ed.up(ed.RADIUS)))["hit"].all()
+    at, above = (y.scan(obst, org, ed.per_point(dirs, 5), float(r)) for r in (ed.RANGE, ed.up(ed.RANGE)))
+    for i, k in enumerate(cases):
+        assert at["entry"][i, k.ray] == ed.RANGE and at["ranges"][i, k.ray] == ed.RANGE and at["ray_hit"][i, k.ray] == -1, k.name
+        assert above["ranges"][i, k.ray] == ed.RANGE and above["ray_hit"][i, k.ray] == k.record, k.name
+
+
+def test_shifted_lattice_keeps_the_fans_inside_the_caps():
+    """the non-axis scans of tests/test_gpu_obstacles_edges.py: with the lattice moved by SHIFT and 37 yaws the yardstick alone leaves out
+    at most CAP_RAYS of the rays as grazing and CAP_DRONES of the drones for a near tie (unshifted, 19 % of diagonal rays graze)"""
+    from gym_pybullet_drones_amd import obstacles as ob
+    obst = ed.lattice().obst
+    pos, quat = ed.shifted_lattice()
+    assert len(np.unique(quat, axis=0)) == ed.N_YAWS
+    assert y.compare_clearance({}, obst, pos) == (0.0, 0.0)                  # (its caps on near ties and on points near the radius hold)
+    for fan in (ob.fan(16, 2 * math.pi), ob.fan(5, math.pi / 2, -0.5)):
+        dirs = y.rotate(fan, quat, 1)
+        graze, s = y.grazing(obst, pos, dirs), y.scan(obst, pos, dirs)
+        with np.errstate(invalid="ignore"):
+            tie = ((s["second"] - s["entry"] < y.NEAR_TIE) & ~graze).any(axis=1)
+        print(f"MEASURED shifted lattice, {len(fan)} rays: grazing {graze.mean():.4f} tie drones {tie.mean():.4f} seen {(s['ray_hit'] >= 0).mean():.3f}")
+        assert graze.mean() <= y.CAP_RAYS and tie.sum() <= y.CAP_DRONES * len(pos)
+        assert 0.2 <= (s["ray_hit"] >= 0).mean() < 1.0                        # (the fan that looks down sees the floor with most rays)
+
+
+def test_lists_of_the_fused_kernel_keep_their_ties():
+    """what tests/test_gpu_obstacles_edges.py flies: lists of 5, 8, 9 and 65 records, each with exact ties among its 70 and 257 points,
+    and rotating a list's order moves the answer with it"""
+    import obst_task_f64 as yo
+    assert [yo.group_lanes(r) for r in (0, 1, 2, 3, 5, 16, 33, 64)] == [1, 1, 2, 4, 8, 16, 64, 64]
+    lists = ed.task_lists()
+    assert sorted(lists) == [5, 8, 9, 65]
+    for n in (70, 257):
+        pos = ed.task_points(n)
+        assert pos.shape == (n, 3) and n % 64 != 0
+        for M, obst in lists.items():
+            c = y.clearance(obst, pos)
+            tie = c["second"] == c["d"]
+            assert tie.sum() >= (40 if M != 8 else 1) and np.isfinite(c["d"]).all(), (n, M)
+            assert (c["nearest"][tie] < c["nearest"].max()).any()
+            rot = y.clearance(ed.rotated(obst, n), pos)
+            np.testing.assert_array_equal(rot["d"], c["d"])
+            moved = (c["nearest"] - np.arange(n)) % M
+            assert (rot["nearest"] <= moved).all() and (rot["nearest"] == moved)[~tie].all()
+    long = lists[65]
+    assert long[64, 3] == y.FLOOR and (long[[0, 1], 3] == y.BOX).all() and (long[:, 3] == y.NONE).sum() == 54
+
+
+@functools.lru_cache(maxsize=None)
+def obstacle_host():
+    import host_lib
+    from gym_pybullet_drones_amd import _native
+    return host_lib.program("obstacle_host", include=(_native.CSRC,))
+
+
+@pytest.mark.parametrize("name", list(ed.scenes()))
+def test_host_compiled_math_on_degenerate_scenes_with_no_exclusion(tmp_path, name):
+    """The C text on the lattice, the corridor, the twins and the lists with skipped records, under the eight axis directions: the
+    class of every t (inf / 0 / positive) and d (sign, == 0), `nearest`, `hit` and `ray_hit` equal to the yardstick's at EVERY point,
+    record and ray -- ties go to the lower record, points on a surface are on it -- no NaN, and values within 1e-6 (ed.BOUND).
+    MEASURED (clang -O1, the largest over the five scenes): pair d 1.1e-07, gradient 1.3e-07, t 6.8e-08"""
+    s = ed.scenes()[name]
+    dirs = ed.per_point(ed.axis_dirs(), len(s.pos))
+    got = run_host_program(obstacle_host(), str(tmp_path), s.obst, s.pos, dirs)
+    pair_d, pair_g, pair_t = ed.compare_pairs(got, s.obst, s.pos, dirs)
+    err_d, err_n, err_r = ed.compare_all(got, s.obst, s.pos, dirs)
+    print(f"MEASURED host obstacle math on {name}: pair d {pair_d:.3e} pair grad {pair_g:.3e} pair t {pair_t:.3e} d {err_d:.3e} "
+          f"normal {err_n:.3e} ranges {err_r:.3e}")
+    assert max(pair_d, pair_g, pair_t, err_d, err_n, err_r) <= ed.BOUND
+    assert np.isinf(got["t"]).any() and (got["t"] < np.inf).any()
+    if name.startswith("lattice"):
+        assert (got["t"] == 0).any() and (got["d"] == 0).any() and (got["d"][np.isfinite(got["d"])] < 0).any()
+
+
+def test_host_compiled_math_at_the_thresholds(tmp_path):
+    """`hit` is d < radius, an entry AT max_range is not seen: the point exactly RADIUS outside every kind of surface is no hit, one
+    ulp nearer (or with a radius one ulp larger) it is; the axis ray that enters at exactly RANGE reports max_range and -1, and the record
+    with max_range one ulp larger"""
+    obst, cases = ed.thresholds()
+    pts, org = ed.threshold_points(), ed.threshold_origins()
+    dirs = ed.axis_dirs()
+    for radius, hits in ((np.float32(ed.RADIUS), [0] * 5 + [1] * 5), (ed.up(ed.RADIUS), [1] * 10)):
+        got = run_host_program(obstacle_host(), str(tmp_path), obst, pts, ed.per_point(dirs, len(pts)), radius=radius)
+        assert list(got["hit"]) == hits and list(got["nearest"]) == [k.record for k in cases] * 2
+        assert list(got["clear4"][:5, 3]) == [ed.RADIUS] * 5 and (got["clear4"][5:, 3] < ed.RADIUS).all()
+        assert max(ed.compare_all(got, obst, pts, ed.per_point(dirs, len(pts)), radius=float(radius))) <= ed.BOUND
+    for max_range, seen in ((np.float32(ed.RANGE), False), (ed.up(ed.RANGE), True)):
+        got = run_host_program(obstacle_host(), str(tmp_path), obst, org, ed.per_point(dirs, len(org)), max_range=max_range)
+        for i, k in enumerate(cases):
+            assert got["t"][i, k.record, k.ray] == ed.RANGE, k.name
+            assert got["ranges"][i, k.ray] == (ed.RANGE if seen else max_range) and got["ray_hit"][i, k.ray] == (k.record if seen else -1), k.name
+        assert max(ed.compare_all(got, obst, org, ed.per_point(dirs, len(org)), max_range=float(max_range))) <= ed.BOUND
 
 
 # ---- the entry's refusals ---------------------------------------------------------------------------------------------------------------
