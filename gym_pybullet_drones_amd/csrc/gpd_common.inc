@@ -788,9 +788,13 @@ __device__ __forceinline__ void map_action(const PP& P, const GpdStepCfg& C, con
             if (fast_sqrt(d2) <= 1.0f) { tx = act.x; ty = act.y; tz = act.z; }
             else { const float id = fast_rsq(d2); tx = fmaf(dx, id, k.px); ty = fmaf(dy, id, k.py); tz = fmaf(dz, id, k.pz); }
         } else if (AW == 4) {   // GPD_ACT_VEL
-            const float nn2 = fmaf(act.z, act.z, fmaf(act.y, act.y, act.x * act.x));
+            float ax = act.x, ay = act.y, az = act.z;
+            float nn2 = fmaf(az, az, fmaf(ay, ay, ax * ax));
+            // a tiny direction is a direction (include/gpd.h, GPD_ACT_VEL): below 2^-100 the squares are subnormal -- which the
+            // reciprocal square root reads as zero -- or gone; 2^100 is exact and lifts the smallest subnormal's square to 2^-98
+            if (nn2 < 0x1p-100f) { ax *= 0x1p100f; ay *= 0x1p100f; az *= 0x1p100f; nn2 = fmaf(az, az, fmaf(ay, ay, ax * ax)); }
             const float sp = P.speed_limit * fabsf(act.w);
-            if (nn2 != 0.0f) { const float in = fast_rsq(nn2); tvx = sp * (act.x * in); tvy = sp * (act.y * in); tvz = sp * (act.z * in); }
+            if (nn2 != 0.0f) { const float in = fast_rsq(nn2); tvx = sp * (ax * in); tvy = sp * (ay * in); tvz = sp * (az * in); }
             tyaw = c.yaw;                                 // keep the current yaw (:220)
         } else {   // GPD_ACT_ONE_D_PID
             tz = fmaf(0.1f, act.x, k.pz);

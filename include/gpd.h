@@ -47,7 +47,11 @@ enum { GPD_MODEL_CF2X = 0, GPD_MODEL_CF2P = 1, GPD_MODEL_RACE = 2 };
 enum {
     GPD_ACT_RPM = 0,       /* rpm = HOVER_RPM*(1+0.05*a[0:4])      envs/BaseRLAviary.py:191-192 */
     GPD_ACT_PID = 1,       /* a[0:3] = waypoint, DSLPID            envs/BaseRLAviary.py:193-207 */
-    GPD_ACT_VEL = 2,       /* a[0:4] = direction+speed, DSLPID     envs/BaseRLAviary.py:208-223 */
+    GPD_ACT_VEL = 2,       /* a[0:4] = direction+speed, DSLPID     envs/BaseRLAviary.py:208-223.  A direction is zero (no
+                              velocity asked) only if all three components are +-0; any other float32 direction, however small --
+                              subnormal components, squares that underflow -- gives the unit vector of the float64 formula
+                              (the components are rescaled by 2^100 before the norm when their squares sum below 2^-100;
+                              an action whose squares sum to 2^-100 or more is computed as ever) */
     GPD_ACT_ONE_D_RPM = 3, /* rpm = HOVER_RPM*(1+0.05*a[0]) x4     envs/BaseRLAviary.py:224-225 */
     GPD_ACT_ONE_D_PID = 4, /* target = pos + 0.1*[0,0,a[0]], DSLPID envs/BaseRLAviary.py:226-235 */
     GPD_ACT_RAW_RPM = 5,   /* rpm = clip(a[0:4], 0, MAX_RPM)       envs/CtrlAviary.py:140 */
@@ -911,6 +915,11 @@ int gpd_reset(const GpdState* state, const float* init_pose, int32_t init_per_en
  * state (updated in place).  target_rpy / target_vel / target_rpy_rates may be NULL (= zeros,
  * the reference's defaults).  Outputs: rpm [n][4], pos_e [n][3] (may be NULL), yaw_e [n]
  * (may be NULL; computed_target_rpy[2] - cur_rpy[2]).
+ * Singular inputs -- a desired force of exactly zero, or one parallel to the target heading -- make the reference divide by zero and
+ * return NaN RPMs and NaN attitude integrals.  Here every RPM and every member passes a clip, and a clip of a NaN returns one of its
+ * bounds: the RPMs are finite and inside [rpm(MIN_PWM), rpm(MAX_PWM)], the nine members finite and inside their clips (which bound is
+ * not specified), pos_e is target_pos - cur_pos as ever, yaw_e is not defined (it may be NaN).  The same holds for the DSLPID action
+ * types inside gpd_step / gpd_rollout.
  */
 int gpd_pid(const GpdParams* params, float* pid, int64_t ld, float ctrl_dt,
             const float* cur_pos, const float* cur_quat, const float* cur_vel,

@@ -110,6 +110,10 @@ class OracleDSLPID:
         self.PWM2RPM_CONST = 4070.3
         self.MIN_PWM = 20000
         self.MAX_PWM = 65535
+        # the clips of :191-193, :248-251 by name, so that a test can hold them as the device does (float32 values)
+        self.POS_I_CLIP, self.POS_I_Z_CLIP = 2., .15
+        self.RPY_I_CLIP, self.RPY_I_XY_CLIP, self.TORQUE_CLIP = 1500., 1., 3200
+        self.trace = None       # a dict here receives the values in front of every clip of the next call
         if consts.DRONE_MODEL == "cf2x":
             self.MIXER_MATRIX = np.array([[-.5, -.5, -1], [-.5, .5, 1], [.5, .5, -1], [.5, -.5, 1]])
         else:
@@ -133,12 +137,14 @@ class OracleDSLPID:
         # -- position PID -> desired force vector, collective PWM, desired attitude (:187-205)
         e_p = target_pos - cur_pos
         e_v = target_vel - cur_vel
-        acc = np.clip(self.integral_pos_e + e_p * dt, -2., 2.)
-        acc[2] = np.clip(acc[2], -0.15, .15)
+        raw_p = self.integral_pos_e + e_p * dt
+        acc = np.clip(raw_p, -self.POS_I_CLIP, self.POS_I_CLIP)
+        acc[2] = np.clip(acc[2], -self.POS_I_Z_CLIP, self.POS_I_Z_CLIP)
         self.integral_pos_e = acc
         f_des = self.P_COEFF_FOR * e_p + self.I_COEFF_FOR * acc + self.D_COEFF_FOR * e_v
         f_des = f_des + np.array([0, 0, self.GRAVITY])
-        along_body_z = max(0., np.dot(f_des, R[:, 2]))
+        raw_along = np.dot(f_des, R[:, 2])
+        along_body_z = max(0., raw_along)
         base_pwm = (math.sqrt(along_body_z / (4 * self.KF)) - self.PWM2RPM_CONST) / self.PWM2RPM_SCALE
         zb = f_des / np.linalg.norm(f_des)
         heading = np.array([math.cos(target_rpy[2]), math.sin(target_rpy[2]), 0])
@@ -156,12 +162,18 @@ class OracleDSLPID:
         e_R = np.array([skew[2, 1], skew[0, 2], skew[1, 0]])
         e_w = target_rpy_rates - (cur_rpy - self.last_rpy) / dt          # finite difference, no unwrap
         self.last_rpy = cur_rpy
-        acc_r = np.clip(self.integral_rpy_e - e_R * dt, -1500., 1500.)
-        acc_r[0:2] = np.clip(acc_r[0:2], -1., 1.)
+        raw_r = self.integral_rpy_e - e_R * dt
+        acc_r = np.clip(raw_r, -self.RPY_I_CLIP, self.RPY_I_CLIP)
+        acc_r[0:2] = np.clip(acc_r[0:2], -self.RPY_I_XY_CLIP, self.RPY_I_XY_CLIP)
         self.integral_rpy_e = acc_r
-        tau = -self.P_COEFF_TOR * e_R + self.D_COEFF_TOR * e_w + self.I_COEFF_TOR * acc_r
-        tau = np.clip(tau, -3200, 3200)
-        pwm = np.clip(base_pwm + self.MIXER_MATRIX @ tau, self.MIN_PWM, self.MAX_PWM)
+        raw_tau = -self.P_COEFF_TOR * e_R + self.D_COEFF_TOR * e_w + self.I_COEFF_TOR * acc_r
+        tau = np.clip(raw_tau, -self.TORQUE_CLIP, self.TORQUE_CLIP)
+        raw_pwm = base_pwm + self.MIXER_MATRIX @ tau
+        pwm = np.clip(raw_pwm, self.MIN_PWM, self.MAX_PWM)
+        if self.trace is not None:
+            self.trace.update(int_pos=raw_p, along=raw_along, f_des=f_des, yb_norm=np.linalg.norm(np.cross(zb, heading)), int_rpy=raw_r,
+                              tau=raw_tau, pwm=raw_pwm, base_pwm=base_pwm, e_R=e_R, e_w=e_w, target_pos=np.array(target_pos, dtype=np.float64),
+                              target_vel=np.array(target_vel, dtype=np.float64))
         return self.PWM2RPM_SCALE * pwm + self.PWM2RPM_CONST, e_p, des_euler[2] - cur_rpy[2]
 
 
